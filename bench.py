@@ -19,6 +19,10 @@ pass of K steps right behind them.
 Other modes: `--total-scenes S` (cfg4: S scenes split over the ranks, every one rendered and ALL of them
 gathered on rank 0: strong scaling), `--shard capsules` (cfg5: ONE scene, its capsules split over the
 ranks, two exchanges (three all-reduce calls) of per-emitter / per-event scalars inside the step).
+
+`--dump-outputs DIR` (any mode): right after the timed repeats, rank 0 writes what the last timed step computed -- the scene
+buffer(s) and, where the step keeps them, every event's scaled render -- as float32 DIR/<name>.npy (a fixed seeded sample of
+arrays over 4 Mi values; see dump_outputs).  The inputs are seeded, so two builds run with the same arguments compare file for file.
 """
 import argparse
 import json
@@ -689,6 +693,66 @@ def make_renderer(emulate):
     return engine.Renderer()   # raises without the HIP extension or a GPU: no fallback
 
 
+DUMP_SAMPLES = 4 << 20     # float32 values per dumped array at most (16 MB): 32 MB over the files of one dump
+
+
+def _sample_index(n, seed):
+    """Every flat index below n when that fits DUMP_SAMPLES, else a fixed seeded sorted sample of DUMP_SAMPLES of them."""
+    if n <= DUMP_SAMPLES:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, DUMP_SAMPLES, replace=False)).astype(np.int64)
+
+
+def _gather(bufs, sizes, idx, emulate, torch):
+    """The values at flat positions `idx` of the buffers laid end to end (buffer i holds sizes[i] values), as float32 on the
+    host; the gather runs where the buffers are, so only the sample crosses PCIe."""
+    first = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    which = np.searchsorted(first, idx, side="right") - 1
+    out = np.empty(len(idx), dtype=np.float32)
+    for i, buf in enumerate(bufs):
+        sel = np.flatnonzero(which == i)
+        if not len(sel):
+            continue
+        local = idx[sel] - first[i]
+        if local[-1] >= (buf.numel() if hasattr(buf, "numel") else np.asarray(buf).size):   # sorted: the last is the largest
+            raise IndexError(f"dump_outputs: position {int(local[-1])} past the end of buffer {i}")
+        if emulate:
+            out[sel] = np.asarray(buf)[local]
+        else:
+            out[sel] = buf[torch.from_numpy(local).to(buf.device)].cpu().numpy()
+    return out, which
+
+
+def dump_outputs(path, scenes, n_scene, result, emulate, torch):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files under `path`.
+    `scene`: the (C, T) mixdown of every scene of the step (row-major, one scene after another);
+    `event_spatial`: every event's scaled (C, len) render (synthesize's spatial_audio, events one after another; absent where the
+    step keeps no per-event renders); `event_scale`: the per-event level factor.  An array larger than DUMP_SAMPLES values is a
+    fixed sample: flat positions numpy.random.default_rng(seed).choice(n, DUMP_SAMPLES, replace=False), sorted, seed 7001 for
+    `scene` and 7002 for `event_spatial`.  Same arguments, same inputs, same files: two builds compare output for output."""
+    os.makedirs(path, exist_ok=True)
+    files, sampled = {}, {}
+    n = n_scene * len(scenes)
+    files["scene"], _ = _gather(scenes, [n_scene] * len(scenes), _sample_index(n, 7001), emulate, torch)
+    sampled["scene"] = n
+    if result is not None:
+        ev = result.plan.events
+        sizes = result.plan.n_capsules * np.asarray(ev["len"], dtype=np.int64)
+        n = int(sizes.sum())
+        idx = _sample_index(n, 7002)
+        offs = np.asarray(ev["out_off"], dtype=np.int64)
+        # each event's render starts at its out_off in the spatial buffer: gather per event, then scale by its factor
+        vals, which = _gather([result.spatial[int(o):] for o in offs], sizes, idx, emulate, torch)
+        scale = np.asarray(result.scales(), dtype=np.float32)
+        files["event_spatial"] = vals * scale[which]      # the float32 product al_scale_rows forms on the device
+        files["event_scale"] = scale
+        sampled["event_spatial"] = n
+    for name, arr in files.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    return {"dir": path, "arrays": {k: list(v.shape) for k, v in files.items()},
+            "values_before_sampling": sampled, "max_values_per_array": DUMP_SAMPLES}
+
+
 def resident_scene(r, scene, args):
     """Inputs, tables and workspaces of one scene in HBM; returns (batch, mix, mix_plan, plan)."""
     from audiblelight_amd import plan as planning
@@ -768,6 +832,9 @@ def main():
     ap.add_argument("--gather", dest="gather", action="store_true", default=None,
                     help="time an RCCL gather of the rendered scenes to rank 0 after the timed region (default: on for N > 1)")
     ap.add_argument("--no-gather", dest="gather", action="store_false")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed (rank 0's scene buffers and event renders) as "
+                         "float32 DIR/<name>.npy, a fixed seeded sample where an array is large (bench.py::dump_outputs)")
     args = ap.parse_args()
 
     if args.cpu_workers_sweep:
@@ -955,6 +1022,9 @@ def run_scene_per_rank_mode(ctx):
                 events[i][1].record()
 
     rep_s, own_s = timed_repeats(step, args.steps, args.warmup, args.repeats, ctx["barrier"], ctx["device_sync"], ctx["reduce_max"])
+    dumped = None
+    if args.dump_outputs and rank == 0:      # before anything else runs on these buffers
+        dumped = dump_outputs(args.dump_outputs, [mix.scene], scene.n_capsules * mix_plan.n_samples, batch.result(), emulate, torch)
     # one more pass of K steps with HIP events on the launch stream (torch's current stream is the stream every al_* call
     # is given) around every stage: the per-kernel durations, outside the regions `value` is computed from
     ev = [[(ctx["new_event"](), ctx["new_event"]()) for _ in stages] for _ in range(args.steps)]
@@ -986,6 +1056,8 @@ def run_scene_per_rank_mode(ctx):
                       {"scenes_per_step_per_gpu": 1})
     out["timing"]["ms_per_step_by_rank_last_repeat"] = [round(x, 4) for x in by_rank]
     out["timing"]["ms_per_step_with_stage_events"] = instrumented / args.steps * 1e3
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     # what one step IS, rank for rank: the same C-ABI calls in the same order whether N = 1 or N > 1 (every rank runs this very
     # function on its own scene), so the N = 1 line of a scaling sweep must equal the single-GPU bench line
     out["config"]["step_calls"] = stages if not chunked else ["al_render_batch (chunked)", "al_mixdown"]
@@ -1329,12 +1401,17 @@ def run_scene_batch_mode(ctx):
             mixes[j].run()
 
     rep_s, own_s = timed_repeats(step, args.steps, args.warmup, args.repeats, ctx["barrier"], ctx["device_sync"], ctx["reduce_max"])
+    dumped = None
+    if args.dump_outputs and rank == 0:      # the scenes are what a step hands back here (the event renders are per input set)
+        dumped = dump_outputs(args.dump_outputs, outputs, n_out, None, emulate, torch)
     by_rank = ctx["all_ranks"](own_s[-1] / args.steps * 1e3)
     elapsed = float(np.median(rep_s))
     out = base_record(ctx, scene0, pl0, args.steps * args.total_scenes * scene0.duration / elapsed, rep_s, args.steps, "strong",
                       {"total_scenes": args.total_scenes, "scenes_this_rank": len(mine), "distinct_input_sets_per_rank": n_sets,
                        "note": "one step = the whole batch; every scene's mixdown writes into its own output buffer"})
     out["timing"]["ms_per_step_by_rank_last_repeat"] = [round(x, 4) for x in by_rank]
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     algo = scene0.algorithmic_bytes() * args.total_scenes
     out["roofline"] = {"bound": "hbm", "kernel": "whole step (all scenes of the batch)", "peak": HBM_PEAK_GBS, "unit": "GB/s",
                        "achieved": algo / elapsed * args.steps / 1e9 / world, "frac": algo / elapsed * args.steps / 1e9 / world / HBM_PEAK_GBS,
@@ -1412,6 +1489,9 @@ def run_capsule_sharded_mode(ctx):
         mix.run()
 
     rep_s, own_s = timed_repeats(step, args.steps, args.warmup, args.repeats, ctx["barrier"], ctx["device_sync"], ctx["reduce_max"])
+    dumped = None
+    if args.dump_outputs and rank == 0:      # rank 0's capsule rows of the scene and of every event
+        dumped = dump_outputs(args.dump_outputs, [mix.scene], rows * mix_plan.n_samples, batch.result(), emulate, torch)
     ctx["barrier"]()
     for _ in range(args.steps):     # instrumented pass: the two exchanges between HIP events on the launch stream
         step(timers)
@@ -1422,6 +1502,8 @@ def run_capsule_sharded_mode(ctx):
     out = base_record(ctx, scene, pl, args.steps * scene.duration / elapsed, rep_s, args.steps, "strong",
                       {"shard": "capsules", "capsules_this_rank": rows, "scenes_per_step": 1})
     out["timing"]["ms_per_step_by_rank_last_repeat"] = [round(x, 4) for x in by_rank]
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     out["collectives_ms"] = dict(coll, note="mean device time per step between HIP events around each exchange (includes "
                                             "waiting for the slowest rank): per-emitter IR norm sums (SUM) before the accumulate, "
                                             "E x {sum|x|, #non-finite} (SUM) + E x max|x| (MAX) before the level law")
