@@ -154,6 +154,7 @@ SYMBOLS = {
     "al_row_stats_partials": (ct.c_int64, [ct.c_int32, ct.c_int64]),
     "al_fx_apply": (ct.c_int, [ct.c_int, _P, _P, ct.c_int64, _P, _P, _S]),
     "al_fx_frame_shuffle": (ct.c_int, [_P, _P, ct.c_int64, ct.c_int32, ct.c_int32, _P, ct.c_int32, _S]),
+    "al_fx_sos": (ct.c_int, [_P, _P, ct.c_int64, _P, ct.c_int32, _S]),
     "al_pack_ragged_irs": (ct.c_int, [_P, ct.c_int32, _P, _P, ct.c_int64, ct.c_int32, _P, _S]),
     "al_resample_poly": (ct.c_int, [_P, ct.c_int32, ct.c_int64, _P, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.c_int64, ct.c_int64, _S]),
     "al_encode_frames": (ct.c_int, [_P, ct.c_int32, ct.c_int64, ct.c_int32, _P, _S]),
@@ -176,6 +177,7 @@ SYMBOLS = {
 }
 FRAMES_F32, FRAMES_PCM16 = 0, 1
 FX_GAIN, FX_INVERT, FX_REVERSE, FX_FADE, FX_CLIP, FX_TANH, FX_BITCRUSH, FX_PREEMPH, FX_DEEMPH = range(1, 10)
+SOS_MAX_SECTIONS = 16   # AL_SOS_MAX_SECTIONS: second-order sections per al_fx_sos call
 FADE_SHAPES = {"linear": 0, "exponential": 1, "logarithmic": 2, "quarter_sine": 3, "half_sine": 4, "none": 5}
 
 

@@ -2,15 +2,18 @@
 ``to_dict`` layout (audiblelight/augmentation.py).
 
 Covered: Gain, Invert, Reverse, Fade, Clipping, Distortion, Bitcrush, Preemphasis, Deemphasis,
-TimeWarpSilence / Duplicate / Remove / Reverse and the peak normalisation of ``Event.load_audio``.
-The stateful pedalboard effects (filters, dynamics, modulation, codecs, time-stretch) stay on
+TimeWarpSilence / Duplicate / Remove / Reverse, the linear time-invariant filters LowpassFilter,
+HighpassFilter, LowShelfFilter, HighShelfFilter and MultibandEqualizer (cascades of second-order
+sections, one ``al_fx_sos`` launch each) and the peak normalisation of ``Event.load_audio``.
+The other stateful pedalboard effects (dynamics, modulation, delay, codecs, time-stretch) stay on
 the host with the reference implementation: out of scope.
 
 Definitions for effects whose reference arithmetic lives in un-vendored third-party wheels
 (parity unpinned, SURVEY.md 8c): Gain = x*10^(dB/20); Clipping = clamp at +-10^(dB/20);
 Distortion = tanh(x*10^(dB/20)); Bitcrush = rint(x*2^bits)/2^bits (pedalboard 0.9.17);
 Preemphasis / Deemphasis = librosa 0.11 ``effects.preemphasis`` / ``deemphasis`` including their
-linear-extrapolation initial state.
+linear-extrapolation initial state.  The filter FX: see ``_FilterFX`` (first-order low/high-pass, Audio EQ
+Cookbook shelves and peaks, float64 coefficients and state, constant gains at degenerate cutoffs).
 """
 from __future__ import annotations
 
@@ -127,6 +130,22 @@ def _fx(clip: DeviceClip, op: int, p0: float = 0.0, iparams=None, out_of_place: 
                ct.cast(ip, ct.c_void_p) if ip is not None else None, r.mem.stream())
     if out_of_place:
         clip.swap()
+
+
+def _sos(clip: DeviceClip, rows, gain: float = 1.0) -> None:
+    """Filter the clip in place through float64 second-order sections ``rows`` (K x 6: b0 b1 b2 a0 a1 a2) preceded by the
+    constant ``gain``: one al_fx_sos launch per AL_SOS_MAX_SECTIONS sections, the gain folded into the first section's
+    numerator.  No rows: the gain alone (one pointwise launch, none at all for the identity)."""
+    r = clip.r
+    rows = np.array(rows, dtype=np.float64).reshape(-1, 6)
+    if len(rows) == 0:
+        if gain != 1.0:
+            _fx(clip, _hip.FX_GAIN, float(gain))
+        return
+    rows[0, :3] *= gain
+    for k0 in range(0, len(rows), _hip.SOS_MAX_SECTIONS):
+        part = np.ascontiguousarray(rows[k0: k0 + _hip.SOS_MAX_SECTIONS])   # a HOST array: read while the launch is built
+        r.lib.call("al_fx_sos", r.mem.ptr(clip.buf), r.mem.ptr(clip.buf), clip.n, part.ctypes.data, len(part), r.mem.stream())
 
 
 def peak_normalize(audio: np.ndarray) -> np.ndarray:
@@ -414,5 +433,185 @@ class TimeWarpRemove(TimeWarp):
     MODE = "rm"
 
 
+def _positive_q(q) -> float:
+    q = _positive(q)
+    if q == 0.0:
+        raise ValueError(f"Expected q to be greater than 0 but got {q}")
+    return q
+
+
+def lowpass_section(fc: float, fs: float):
+    """(rows, gain) of pedalboard's first-order low-pass (-3 dB at fc): with n = tan(pi fc / fs), b = [n, n],
+    a = [n + 1, n - 1].  fc = 0: gain 0; fc >= fs / 2: identity."""
+    if fc <= 0:
+        return [], 0.0
+    if fc >= fs / 2:
+        return [], 1.0
+    n = np.tan(np.pi * fc / fs)
+    return [[n, n, 0.0, n + 1.0, n - 1.0, 0.0]], 1.0
+
+
+def highpass_section(fc: float, fs: float):
+    """(rows, gain) of the first-order high-pass: b = [1, -1], a = [n + 1, n - 1].  fc = 0: identity; fc >= fs / 2: 0."""
+    if fc <= 0:
+        return [], 1.0
+    if fc >= fs / 2:
+        return [], 0.0
+    n = np.tan(np.pi * fc / fs)
+    return [[1.0, -1.0, 0.0, n + 1.0, n - 1.0, 0.0]], 1.0
+
+
+def shelf_section(fc: float, gain_db: float, q: float, fs: float, high: bool):
+    """(rows, gain) of an Audio EQ Cookbook shelf (slope given by Q): A = 10^(dB/40), w = 2 pi fc / fs,
+    beta = sin(w) sqrt(A) / Q.  The boosted side tends to 10^(dB/20), the other to 1: a low shelf is the identity at
+    fc = 0 and 10^(dB/20) at fc >= fs / 2, a high shelf the reverse."""
+    full = float(10.0 ** (gain_db / 20.0))
+    if fc <= 0:
+        return [], (full if high else 1.0)
+    if fc >= fs / 2:
+        return [], (1.0 if high else full)
+    A = 10.0 ** (gain_db / 40.0)
+    w = 2.0 * np.pi * fc / fs
+    cw, beta = np.cos(w), np.sin(w) * np.sqrt(A) / q
+    if high:
+        b = [A * ((A + 1) + (A - 1) * cw + beta), -2 * A * ((A - 1) + (A + 1) * cw), A * ((A + 1) + (A - 1) * cw - beta)]
+        a = [(A + 1) - (A - 1) * cw + beta, 2 * ((A - 1) - (A + 1) * cw), (A + 1) - (A - 1) * cw - beta]
+    else:
+        b = [A * ((A + 1) - (A - 1) * cw + beta), 2 * A * ((A - 1) - (A + 1) * cw), A * ((A + 1) - (A - 1) * cw - beta)]
+        a = [(A + 1) + (A - 1) * cw + beta, -2 * ((A - 1) + (A + 1) * cw), (A + 1) + (A - 1) * cw - beta]
+    return [b + a], 1.0
+
+
+def peak_section(fc: float, gain_db: float, q: float, fs: float):
+    """(rows, gain) of an Audio EQ Cookbook peak: alpha = sin(w) / (2Q), b = [1 + alpha A, -2 cos w, 1 - alpha A],
+    a = [1 + alpha / A, -2 cos w, 1 - alpha / A].  fc = 0 and fc >= fs / 2: identity."""
+    if fc <= 0 or fc >= fs / 2:
+        return [], 1.0
+    A = 10.0 ** (gain_db / 40.0)
+    w = 2.0 * np.pi * fc / fs
+    alpha, cw = np.sin(w) / (2.0 * q), np.cos(w)
+    return [[1 + alpha * A, -2 * cw, 1 - alpha * A, 1 + alpha / A, -2 * cw, 1 - alpha / A]], 1.0
+
+
+class _FilterFX(EventAugmentation):
+    """Linear time-invariant filter FX: a cascade of second-order sections run on the device by ``al_fx_sos`` (float64
+    coefficients and recursion state, zero initial state like pedalboard's ``reset=True``).  pedalboard is an un-vendored
+    wheel, so the filters are defined here (parity unpinned), with w = 2 pi fc / fs and A = 10^(dB/40):
+
+    * LowpassFilter / HighpassFilter: pedalboard's documented first-order filters, -3 dB at fc; n = tan(pi fc / fs),
+      low-pass b = [n, n], high-pass b = [1, -1], both a = [n + 1, n - 1];
+    * LowShelfFilter / HighShelfFilter / the bands of MultibandEqualizer: the Audio EQ Cookbook (R. Bristow-Johnson)
+      shelf and peak filters, the shelf slope given by Q;
+    * degenerate cutoffs (fc = 0, fc >= fs / 2) are the limit of each formula, a constant gain applied as a scalar:
+      low-pass 0 / identity, high-pass identity / 0, low shelf identity / 10^(dB/20), high shelf 10^(dB/20) / identity,
+      peak identity / identity.  q must be > 0.
+    """
+
+    def sections(self):
+        """(rows, gain): float64 SOS rows {b0 b1 b2 a0 a1 a2} and the constant gain of the degenerate stages."""
+        raise NotImplementedError
+
+    def host_dtype(self, in_dtype):
+        return np.dtype(np.float32)     # pedalboard returns float32
+
+    def apply_device(self, clip):
+        rows, gain = self.sections()
+        _sos(clip, rows, gain)
+
+
+class _FirstOrderFilter(_FilterFX):
+    MIN_FREQ, MAX_FREQ = 5512, 22050
+
+    def __init__(self, sample_rate=config.SAMPLE_RATE, cutoff_frequency_hz=None):
+        super().__init__(sample_rate)
+        self.cutoff_frequency_hz = _positive(_sample(cutoff_frequency_hz, self.MIN_FREQ, self.MAX_FREQ))
+        self.params = dict(cutoff_frequency_hz=self.cutoff_frequency_hz)
+
+
+class LowpassFilter(_FirstOrderFilter):
+    MIN_FREQ, MAX_FREQ = 5512, 22050
+
+    def sections(self):
+        return lowpass_section(self.cutoff_frequency_hz, self.sample_rate)
+
+
+class HighpassFilter(_FirstOrderFilter):
+    MIN_FREQ, MAX_FREQ = 32, 1024
+
+    def sections(self):
+        return highpass_section(self.cutoff_frequency_hz, self.sample_rate)
+
+
+class _ShelfFilter(_FilterFX):
+    MIN_FREQ, MAX_FREQ = 5512, 22050
+    MIN_GAIN, MAX_GAIN = -20, 10
+    MIN_Q, MAX_Q = 0.1, 1.0
+    HIGH = True
+
+    def __init__(self, sample_rate=config.SAMPLE_RATE, gain_db=None, cutoff_frequency_hz=None, q=None):
+        super().__init__(sample_rate)
+        self.cutoff_frequency_hz = _positive(_sample(cutoff_frequency_hz, self.MIN_FREQ, self.MAX_FREQ))
+        self.gain_db = _sample(gain_db, self.MIN_GAIN, self.MAX_GAIN)
+        self.q = _positive_q(_sample(q, self.MIN_Q, self.MAX_Q))
+        self.params = dict(cutoff_frequency_hz=self.cutoff_frequency_hz, gain_db=self.gain_db, q=self.q)
+
+    def sections(self):
+        return shelf_section(self.cutoff_frequency_hz, self.gain_db, self.q, self.sample_rate, self.HIGH)
+
+
+class HighShelfFilter(_ShelfFilter):
+    MIN_FREQ, MAX_FREQ = 5512, 22050
+    HIGH = True
+
+
+class LowShelfFilter(_ShelfFilter):
+    MIN_FREQ, MAX_FREQ = 32, 1024
+    HIGH = False
+
+
+class MultibandEqualizer(_FilterFX):
+    """1..N Audio EQ Cookbook peak filters in series (augmentation.py:510-660): ``n_bands`` is drawn from [1, 8) and
+    truncated by ``int``; each per-band parameter is a scalar (repeated), a list / ndarray of ``n_bands`` values, or a
+    distribution sampled once per band."""
+
+    MIN_BANDS, MAX_BANDS = 1, 8
+    MIN_GAIN, MAX_GAIN = -20, 10
+    MIN_FREQ, MAX_FREQ = 1024, 22050
+    MIN_Q, MAX_Q = 0.1, 1.0
+
+    def __init__(self, sample_rate=config.SAMPLE_RATE, n_bands=None, gain_db=None, cutoff_frequency_hz=None, q=None):
+        super().__init__(sample_rate)
+        self.n_bands = _positive(_sample(n_bands, self.MIN_BANDS, self.MAX_BANDS), int)
+        self.gain_db = self._per_band(gain_db, self.MIN_GAIN, self.MAX_GAIN)
+        self.cutoff_frequency_hz = self._per_band(cutoff_frequency_hz, self.MIN_FREQ, self.MAX_FREQ)
+        self.q = self._per_band(q, self.MIN_Q, self.MAX_Q)
+        self.params = dict(n_bands=self.n_bands, gain_db=self.gain_db, cutoff_frequency_hz=self.cutoff_frequency_hz, q=self.q)
+        # the reference validates every band when it builds its PeakFilter objects (create_filters, :646-660)
+        self._bands = [(_positive(f), g, _positive_q(q)) for g, f, q in zip(self.gain_db, self.cutoff_frequency_hz, self.q)]
+
+    def _per_band(self, override, lo, hi) -> list:
+        """sample_peak_filter_params (augmentation.py:599-644)."""
+        if override is None:
+            return [float(np.random.uniform(lo, hi)) for _ in range(self.n_bands)]
+        if isinstance(override, (list, np.ndarray)):
+            if len(override) != self.n_bands:
+                raise ValueError(f"Expected {self.n_bands} values but got {len(override)}")
+            return override if isinstance(override, list) else override.tolist()
+        if isinstance(override, (int, float, np.integer, np.floating)):
+            return [override for _ in range(self.n_bands)]
+        if hasattr(override, "rvs"):
+            return [float(override.rvs()) for _ in range(self.n_bands)]
+        raise TypeError(f"Cannot handle type {type(override)}")
+
+    def sections(self):
+        rows, gain = [], 1.0
+        for fc, g, q in self._bands:
+            r, k = peak_section(fc, g, q, self.sample_rate)
+            rows += r
+            gain *= k
+        return rows, gain
+
+
 ALL_EVENT_AUGMENTATIONS = [Gain, Invert, Reverse, Fade, Clipping, Distortion, Bitcrush, Preemphasis, Deemphasis,
-                           TimeWarpSilence, TimeWarpDuplicate, TimeWarpRemove, TimeWarpReverse]
+                           TimeWarpSilence, TimeWarpDuplicate, TimeWarpRemove, TimeWarpReverse,
+                           LowpassFilter, HighpassFilter, LowShelfFilter, HighShelfFilter, MultibandEqualizer]

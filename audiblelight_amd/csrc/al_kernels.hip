@@ -19,6 +19,7 @@
 #include "al_fft.h"
 #include "al_bigfft.h"
 #include "al_stft.h"
+#include "al_sos.h"
 
 namespace al {
 
@@ -1624,6 +1625,45 @@ int al_fx_frame_shuffle(const float *src, float *dst, int64_t n, int32_t frame_l
   hipLaunchKernelGGL(al::k_frame_shuffle, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
                      (hipStream_t)stream, src, dst, n, frame_len, row_len, rows, n_rows);
   return check_launch("k_frame_shuffle");
+}
+
+int al_fx_sos(const float *src, float *dst, int64_t n, const double *sos, int32_t n_sections, al_stream_t stream) {
+  if (!src || !dst || !sos) return fail(AL_E_BADARG, "al_fx_sos: null pointer");
+  if (n < 1) return fail(AL_E_BADARG, "al_fx_sos: n must be >= 1");
+  if (n_sections < 1 || n_sections > AL_SOS_MAX_SECTIONS)
+    return fail(AL_E_BADARG, "al_fx_sos: n_sections must be in 1..AL_SOS_MAX_SECTIONS (16); split longer cascades");
+  const int64_t run = al::sos_run_length(n);
+  al::SosArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n_sections = n_sections;
+  char msg[160];
+  for (int k = 0; k < n_sections; ++k) {
+    const double *row = sos + 6 * k;
+    for (int i = 0; i < 6; ++i)
+      if (!isfinite(row[i])) {
+        snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a non-finite coefficient", k);
+        return fail(AL_E_BADARG, msg);
+      }
+    if (row[3] == 0.0) {
+      snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a0 == 0", k);
+      return fail(AL_E_BADARG, msg);
+    }
+    const double c[5] = {row[0] / row[3], row[1] / row[3], row[2] / row[3], row[4] / row[3], row[5] / row[3]};
+    for (int i = 0; i < 5; ++i)
+      if (!isfinite(c[i])) {
+        snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a non-finite coefficient after division by a0", k);
+        return fail(AL_E_BADARG, msg);
+      }
+    // both roots of z^2 + a1 z + a2 inside the unit circle (Jury): |a2| < 1 and |a1| < 1 + a2
+    if (!(fabs(c[4]) < 1.0 && fabs(c[3]) < 1.0 + c[4])) {
+      snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a pole of magnitude >= 1 (unstable filter)", k);
+      return fail(AL_E_BADARG, msg);
+    }
+    for (int i = 0; i < 5; ++i) a.c[k][i] = c[i];
+    al::sos_transition_power(c[3], c[4], run, a.phi[k]);
+  }
+  hipLaunchKernelGGL(al::k_fx_sos, dim3(1), dim3(al::SOS_THREADS), 0, (hipStream_t)stream, src, dst, n, run, a);
+  return check_launch("k_fx_sos");
 }
 
 // ---- arbitrary-length inverse real FFT (ambience)

@@ -279,6 +279,16 @@ int al_fx_apply(int op, const float *src, float *dst, int64_t n, const float *pa
  * by rows); the concatenation is wrap-extended to n samples (Augmentation.process, augmentation.py:117-123). */
 int al_fx_frame_shuffle(const float *src, float *dst, int64_t n, int32_t frame_len, int32_t row_len,
                         const int32_t *rows, int32_t n_rows, al_stream_t stream);
+/* Linear time-invariant filter FX (LowpassFilter, HighpassFilter, LowShelfFilter, HighShelfFilter, MultibandEqualizer;
+ * augmentation.py:303-660): dst = the float32 clip src of n samples filtered through n_sections second-order sections in
+ * series, every section starting from zero state (scipy.signal.sosfilt with zi=None).  `sos` is a HOST array of n_sections
+ * rows {b0, b1, b2, a0, a1, a2} (scipy's sos layout); the library divides each row by its a0.  Coefficients and recursion
+ * state are float64, only src and dst are float32.  One launch per call; longer cascades are split over several calls
+ * (up to AL_SOS_MAX_SECTIONS sections each).  In place (dst == src) is allowed.
+ * AL_E_BADARG for n < 1, n_sections outside 1..AL_SOS_MAX_SECTIONS, a0 == 0, a non-finite coefficient, or a section with a
+ * pole of magnitude >= 1; al_last_error() names the reason and the section. */
+#define AL_SOS_MAX_SECTIONS 16
+int al_fx_sos(const float *src, float *dst, int64_t n, const double *sos, int32_t n_sections, al_stream_t stream);
 /* ---- Ambience (A12): Timmer-Koenig (1/f)^beta noise, audiblelight/ambience.py:271-375.
  * The host draws the two standard-normal sets with numpy's default_rng(seed) (PCG64 + ziggurat, ambience.py:351-356:
  * the reference's RNG stream is data-dependent and is not re-implemented on the device); everything after the draws
