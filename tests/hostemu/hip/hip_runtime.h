@@ -224,14 +224,27 @@ static inline T __shfl_down(T v, unsigned off, int /*width*/ = 64) {
   return r;
 }
 
+// sincospi as the device library has it: exact at multiples of 1/2 and odd in x (sin(-0) = -0).  Quarter turns are taken off
+// exactly, the remainder (|f| <= 1/4) goes through long double, so every result is within one float64 ulp.
 static inline void sincospi(double x, double *s, double *c) {
-  *s = sin(M_PI * x);
-  *c = cos(M_PI * x);
+  if (x == 0.0) { *s = x; *c = 1.0; return; }
+  const double r = remainder(x, 2.0), q = nearbyint(2.0 * r), f = r - 0.5 * q;
+  const long double a = (long double)f * 3.141592653589793238462643383279502884L;
+  const double sf = f == 0.0 ? 0.0 : (double)sinl(a), cf = (double)cosl(a);
+  switch ((int)q & 3) {
+    case 0: *s = sf; *c = cf; break;
+    case 1: *s = cf; *c = -sf; break;
+    case 2: *s = -sf; *c = -cf; break;
+    default: *s = -cf; *c = sf; break;
+  }
+  if (*s == 0.0) *s = copysign(0.0, x);
 }
 static inline float sinpif(float x) { return (float)sin(M_PI * (double)x); }
+// float32 evaluation, as the device's single-precision sincospif is: a few ulp, not the correctly rounded value
 static inline void sincospif(float x, float *s, float *c) {
-  *s = (float)sin(M_PI * (double)x);
-  *c = (float)cos(M_PI * (double)x);
+  const float a = 3.14159265f * x;
+  *s = sinf(a);
+  *c = cosf(a);
 }
 static inline unsigned __float_as_uint(float x) { unsigned u; memcpy(&u, &x, 4); return u; }
 using std::isfinite;
