@@ -1,20 +1,26 @@
 #!/usr/bin/env python
 """Headline benchmark: rendered scene-seconds per second (BASELINE.json metric) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg2]
+    python bench.py --gpus N --steps K --warmup W [--config cfg2] [--full]
 
 One "step" = one full pass of the hot path over one synthetic scene of the chosen config (default
 cfg2: 60 s scene, 32 capsules, 64 static events, 2 s RIRs, 48 kHz): the equivalents of
 render_audio_for_all_scene_events + generate_scene_audio_from_events with clips, IRs and tables
 already resident in HBM.  For N > 1 every rank renders its own scene (weak scaling, no data-path
-collective; the end-of-job gather is timed separately and rank 0 re-renders two peers' scenes to
-check the gathered buffers bit for bit); rank 0 prints ONE JSON line.
+collective); rank 0 prints ONE JSON line.
 
 Timing: W warm-up steps, then `--repeats` (default 3) repeats of EXACTLY K steps, each repeat bracketed by
 barrier + synchronize on both sides, max over ranks per repeat; `ms_per_step` / `value` come from the MEDIAN
 repeat (all repeats are in the JSON), so the driver's short `--steps 20` run does not hang on one outlier.
-Nothing but the launches is inside those regions; the per-kernel HIP-event durations come from one more
-pass of K steps right behind them.
+Nothing but the launches is inside those regions.
+
+A plain run does only what the headline needs: it sets up, warms up, times the repeats, writes `--dump-outputs`
+and prints the line.  `--full` adds every other leg, each outside the timed regions: the per-kernel HIP-event
+durations of one more pass of K steps and the roofline built on them, the float64 oracle on one core and on all
+cores (`cpu_baseline*`), `parity` against that oracle, cfg3 / cfg4 / cfg5 (`other_configs`), the PCIe-inclusive
+legs (`end_to_end`, `end_to_end_dropin`), the capsule-sharded mode's timed exchanges and, for N > 1, the end-of-job
+gather (timed separately; rank 0 re-renders two peers' scenes to check the gathered buffers bit for bit).  An option
+that names a leg (`--cpu-events 4`, `--end-to-end 8`, `--gather`, ...) runs it with or without `--full`.
 
 Other modes: `--total-scenes S` (cfg4: S scenes split over the ranks, every one rendered and ALL of them
 gathered on rank 0: strong scaling), `--shard capsules` (cfg5: ONE scene, its capsules split over the
@@ -800,16 +806,20 @@ def main():
                          "ranks; every scene is rendered and all of them are gathered on rank 0 after the timed region")
     ap.add_argument("--shard", default="scenes", choices=["scenes", "capsules"],
                     help="capsules: ONE scene per step, its capsule rows split over the ranks (SURVEY 8e row 2; cfg5 secondary)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beside the headline (per-kernel pass + roofline, CPU baselines, oracle parity, other "
+                         "configs, PCIe-inclusive legs, collective timings, N > 1 gather); each option below says its default "
+                         "with --full, and without it the default is 0 / off")
     ap.add_argument("--cpu-events", type=int, default=None,
-                    help="events timed for the CPU baseline (0 = skip; default: the whole scene for cfg2 = 18 s on one core, "
-                         "a bounded sample for the larger configurations)")
-    ap.add_argument("--parity-events", type=int, default=-1, metavar="N",
+                    help="events timed for the CPU baseline (0 = skip; default with --full: the whole scene for cfg2 = 18 s on one "
+                         "core, a bounded sample for the larger configurations)")
+    ap.add_argument("--parity-events", type=int, default=None, metavar="N",
                     help="events of the timed scene compared with the float64 oracle, all capsule rows x all samples (JSON `parity`; "
-                         "exit code 1 above 1e-4).  -1: the whole scene for cfg2 / cfg4 (the oracle scene of the cpu_baseline leg is "
-                         "reused), 1 event for cfg3, 2 for cfg5; 0: skip")
-    ap.add_argument("--cpu-workers", type=int, default=-1, metavar="N",
-                    help="also time the oracle on N host processes at once, one whole scene each (all-cores CPU figure; -1 = one per "
-                         "PHYSICAL core, bounded by free memory; 0 = skip; skipped by itself under a profiler)")
+                         "exit code 1 above 1e-4).  -1 (default with --full): the whole scene for cfg2 / cfg4 (the oracle scene of "
+                         "the cpu_baseline leg is reused), 1 event for cfg3, 2 for cfg5; 0: skip")
+    ap.add_argument("--cpu-workers", type=int, default=None, metavar="N",
+                    help="also time the oracle on N host processes at once, one whole scene each (all-cores CPU figure; -1 (default "
+                         "with --full) = one per PHYSICAL core, bounded by free memory; 0 = skip; skipped by itself under a profiler)")
     ap.add_argument("--cpu-workers-sweep", default="", metavar="N1,N2,...",
                     help="CPU-only mode (no GPU is touched): the all-cores oracle leg at each of these worker counts, with and without "
                          "the reference's per-event padded copies, one JSON line {workers_sweep, cpu_quota, knee}; what explains "
@@ -819,18 +829,20 @@ def main():
                          "which takes 128 busy cores about nine minutes at cfg2)")
     ap.add_argument("--end-to-end", type=int, default=None, metavar="N",
                     help="also run N scenes through the pipelined batch driver from HOST buffers (PCIe-inclusive rate; with "
-                         "--gpus > 1 every rank runs it at the same time; default 16 per rank in the headline mode, 0 otherwise)")
+                         "--gpus > 1 every rank runs it at the same time; default with --full 16 per rank in the headline mode, 0 "
+                         "otherwise)")
     ap.add_argument("--dropin", type=int, default=None, metavar="N",
                     help="also time N calls of Scene.generate() (the drop-in API: host numpy clips + IRs in, scene.audio "
-                         "out, synchronous; every rank at the same time with --gpus > 1; default 8 per rank for static configs in the "
-                         "headline mode, 0 otherwise)")
-    ap.add_argument("--other-configs", type=int, default=1, metavar="0|1",
+                         "out, synchronous; every rank at the same time with --gpus > 1; default with --full 8 per rank for static "
+                         "configs in the headline mode, 0 otherwise)")
+    ap.add_argument("--other-configs", type=int, default=None, metavar="0|1",
                     help="on the default single-GPU cfg2 run also time a few steps of cfg3, cfg4 and cfg5 (compact leg "
-                         "`other_configs` of the JSON line; 0 = skip)")
+                         "`other_configs` of the JSON line; default with --full 1; 0 = skip)")
     ap.add_argument("--graph", action="store_true",
                     help="replay the scene as one HIP graph (engine.CapturedScene) instead of seven launches")
     ap.add_argument("--gather", dest="gather", action="store_true", default=None,
-                    help="time an RCCL gather of the rendered scenes to rank 0 after the timed region (default: on for N > 1)")
+                    help="time an RCCL gather of the rendered scenes to rank 0 after the timed region and check it against rank 0's "
+                         "own re-render (default with --full: on for N > 1)")
     ap.add_argument("--no-gather", dest="gather", action="store_false")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps write what the last one computed (rank 0's scene buffers and event renders) as "
@@ -851,22 +863,28 @@ def main():
     if world != args.gpus:
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}; launch one rank per GPU "
                  f"(python bench.py --gpus N spawns them itself)")
-    if args.gather is None:
-        args.gather = world > 1
+    # every leg beside the headline is off unless --full (or its own option) asks for it; --full gives each its old default
+    full = args.full
     if args.cpu_events is None:
-        args.cpu_events = {"cfg2": 64, "cfg3": 1, "cfg4": 32, "cfg5": 4}.get(args.config, 64)
-    plain = args.total_scenes == 0 and args.shard == "scenes"
+        args.cpu_events = {"cfg2": 64, "cfg3": 1, "cfg4": 32, "cfg5": 4}.get(args.config, 64) if full else 0
+    if args.parity_events is None:
+        args.parity_events = -1 if full else 0
+    if args.cpu_workers is None:
+        args.cpu_workers = -1 if full else 0
+    if args.other_configs is None:
+        args.other_configs = 1 if full else 0
+    headline = args.total_scenes == 0 and args.shard == "scenes"
     emulate = os.environ.get("AL_BENCH_EMULATE") == "1"   # tests only: host-emulated kernels, numbers are NOT measurements
     if args.end_to_end is None:     # N > 1: every rank runs the PCIe-inclusive legs at the same time (shared host)
-        args.end_to_end = 16 if (plain and not emulate) else 0    # (the batch driver needs page-locked memory and HIP streams)
+        args.end_to_end = 16 if (full and headline and not emulate) else 0    # (the batch driver needs page-locked memory and HIP streams)
     if args.dropin is None:
-        args.dropin = 8 if plain else 0
+        args.dropin = 8 if (full and headline) else 0
 
     # SURVEY 8d (ii), the all-cores CPU figure: its worker processes are started HERE, before this process initialises the
     # GPU (a GPU-initialised process must not be the parent of an exec on this pool).  Under a profiler the preloaded tool
     # library has ALREADY initialised the GPU when main() starts: the leg is skipped and the JSON says so.
     all_cores = None
-    if rank == 0 and world == 1 and plain and args.cpu_workers != 0 and not emulate:
+    if rank == 0 and world == 1 and headline and args.cpu_workers != 0 and not emulate:
         if under_profiler():
             all_cores = {"skipped": "profiler preload detected (LD_PRELOAD / ROCPROF* / ROCP_TOOL*): this process already holds "
                                     "the GPU, so it must not start worker processes"}
@@ -912,6 +930,8 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device(f"cuda:{device_index}"), timeout=dist_timeout())
         else:
             dist.init_process_group(backend, timeout=dist_timeout())
+    if args.gather is None:   # the end-of-job gather and its check against rank 0's re-render (N > 1, or one rank on RCCL)
+        args.gather = full and use_dist
     new_event, device_sync = make_timers(emulate, torch)
     coll_dev = "cuda" if (backend == "nccl" and not emulate) else "cpu"
     # N ranks on one node: each takes its share of the host (helper pools capped at usable CPUs / local ranks, the process pinned
@@ -990,6 +1010,46 @@ def base_record(ctx, scene, pl, value, rep_s, steps, scaling, extra_config):
     }
 
 
+def stage_roofline(args, scene, pl, mix_plan, stages, chunked, ev, ms_per_step):
+    """`roofline` of the headline line (--full): per-stage durations from the HIP events of the instrumented pass `ev`, held
+    against the algorithmic bytes, the committed PMC traffic and the plan-counted flops."""
+    if chunked:
+        kernel_ms = {"al_render_batch+al_mixdown": ms_per_step}
+    else:
+        kernel_ms = {name: float(np.mean([ev[k][i][0].elapsed_time(ev[k][i][1]) for k in range(args.steps)]))
+                     for i, name in enumerate(stages)}
+    dominant = max(kernel_ms, key=kernel_ms.get)
+    algo_bytes = scene.algorithmic_bytes()
+    achieved = algo_bytes / (kernel_ms[dominant] * 1e-3) / 1e9
+    pmc, pmc_note = (load_pmc_traffic(scene.name, pl.log2_block) if args.scale == 1.0 else (None, "reduced scale"))
+    out = {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+           "frac": achieved / HBM_PEAK_GBS,
+           # the same algorithmic bytes over the WHOLE step (all kernels of the scene), per GPU
+           "path_frac": algo_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+           "traffic": (pmc or {}).get(dominant),
+           # HBM rate on the bytes actually moved (PMC traffic / live duration): what the kernel is up against
+           "traffic_rate": ((pmc or {}).get(dominant) or 0) / (kernel_ms[dominant] * 1e-3) / 1e9 or None,
+           "traffic_note": pmc_note,
+           "scene_traffic": sum(v for v in (pmc or {}).values() if isinstance(v, (int, float))) or None,
+           "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": kernel_ms,
+           # SURVEY 8(d) names TWO contracts.  `frac` / `path_frac` above are the scene-only one (inputs read once +
+           # scene.audio written once); the API also exposes every event's (C, La) render and the kernels DO write it,
+           # so the full-API contract adds those bytes once: both, so a reader can hold the path to either
+           "contracts": {
+               "scene_only": {"algorithmic_bytes": algo_bytes, "frac": achieved / HBM_PEAK_GBS,
+                              "path_frac": algo_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
+               "full_api": {"algorithmic_bytes": scene.algorithmic_bytes_full_api(),
+                            "frac": scene.algorithmic_bytes_full_api() / (kernel_ms[dominant] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                            "path_frac": scene.algorithmic_bytes_full_api() / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
+               "reported_as_frac": "scene_only"},
+           "hbm_bytes_per_launch_pmc": pmc}
+    if not chunked:
+        out.update(secondary_roofline(
+            pl, mix_plan, kernel_ms, load_pmc_valu(scene.name, pl.log2_block) if args.scale == 1.0 else None,
+            out["scene_traffic"], algo_bytes, dominant))
+    return out
+
+
 def run_scene_per_rank_mode(ctx):
     """The headline: one scene per rank per step (weak scaling)."""
     args, rank, world, emulate, torch = ctx["args"], ctx["rank"], ctx["world"], ctx["emulate"], ctx["torch"]
@@ -1025,16 +1085,18 @@ def run_scene_per_rank_mode(ctx):
     dumped = None
     if args.dump_outputs and rank == 0:      # before anything else runs on these buffers
         dumped = dump_outputs(args.dump_outputs, [mix.scene], scene.n_capsules * mix_plan.n_samples, batch.result(), emulate, torch)
-    # one more pass of K steps with HIP events on the launch stream (torch's current stream is the stream every al_* call
-    # is given) around every stage: the per-kernel durations, outside the regions `value` is computed from
-    ev = [[(ctx["new_event"](), ctx["new_event"]()) for _ in stages] for _ in range(args.steps)]
-    ctx["barrier"]()
-    t0 = time.perf_counter()
-    for k in range(args.steps):
-        step(None if chunked else ev[k])
-    ctx["device_sync"]()
-    instrumented = time.perf_counter() - t0
     by_rank = ctx["all_ranks"](own_s[-1] / args.steps * 1e3)
+    instrumented = None
+    if args.full:
+        # one more pass of K steps with HIP events on the launch stream (torch's current stream is the stream every al_* call
+        # is given) around every stage: the per-kernel durations, outside the regions `value` is computed from
+        ev = [[(ctx["new_event"](), ctx["new_event"]()) for _ in stages] for _ in range(args.steps)]
+        ctx["barrier"]()
+        t0 = time.perf_counter()
+        for k in range(args.steps):
+            step(None if chunked else ev[k])
+        ctx["device_sync"]()
+        instrumented = time.perf_counter() - t0
     batch.result().check_finite()
     # parity of WHAT WAS TIMED: the scene buffer the timed steps wrote, on the host before any other leg runs
     want_parity = rank == 0 and world == 1 and args.parity_events != 0
@@ -1043,49 +1105,17 @@ def run_scene_per_rank_mode(ctx):
         timed_scene_host = np.array(r.mem.download(mix.scene)[: scene.n_capsules * mix_plan.n_samples].reshape(scene.n_capsules, -1))
     elapsed = float(np.median(rep_s))
     ms_per_step = elapsed / args.steps * 1e3
-    if chunked:
-        kernel_ms = {"al_render_batch+al_mixdown": ms_per_step}
-    else:
-        kernel_ms = {name: float(np.mean([ev[k][i][0].elapsed_time(ev[k][i][1]) for k in range(args.steps)]))
-                     for i, name in enumerate(stages)}
-    dominant = max(kernel_ms, key=kernel_ms.get)
-    algo_bytes = scene.algorithmic_bytes()
-    achieved = algo_bytes / (kernel_ms[dominant] * 1e-3) / 1e9
-    pmc, pmc_note = (load_pmc_traffic(scene.name, pl.log2_block) if args.scale == 1.0 else (None, "reduced scale"))
     out = base_record(ctx, scene, pl, world * args.steps * scene.duration / elapsed, rep_s, args.steps, "weak",
                       {"scenes_per_step_per_gpu": 1})
     out["timing"]["ms_per_step_by_rank_last_repeat"] = [round(x, 4) for x in by_rank]
-    out["timing"]["ms_per_step_with_stage_events"] = instrumented / args.steps * 1e3
     if dumped is not None:
         out["dump_outputs"] = dumped
     # what one step IS, rank for rank: the same C-ABI calls in the same order whether N = 1 or N > 1 (every rank runs this very
     # function on its own scene), so the N = 1 line of a scaling sweep must equal the single-GPU bench line
     out["config"]["step_calls"] = stages if not chunked else ["al_render_batch (chunked)", "al_mixdown"]
-    out["roofline"] = {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                       "frac": achieved / HBM_PEAK_GBS,
-                       # the same algorithmic bytes over the WHOLE step (all kernels of the scene), per GPU
-                       "path_frac": algo_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                       "traffic": (pmc or {}).get(dominant),
-                       # HBM rate on the bytes actually moved (PMC traffic / live duration): what the kernel is up against
-                       "traffic_rate": ((pmc or {}).get(dominant) or 0) / (kernel_ms[dominant] * 1e-3) / 1e9 or None,
-                       "traffic_note": pmc_note,
-                       "scene_traffic": sum(v for v in (pmc or {}).values() if isinstance(v, (int, float))) or None,
-                       "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": kernel_ms,
-                       # SURVEY 8(d) names TWO contracts.  `frac` / `path_frac` above are the scene-only one (inputs read once +
-                       # scene.audio written once); the API also exposes every event's (C, La) render and the kernels DO write it,
-                       # so the full-API contract adds those bytes once: both, so a reader can hold the path to either
-                       "contracts": {
-                           "scene_only": {"algorithmic_bytes": algo_bytes, "frac": achieved / HBM_PEAK_GBS,
-                                          "path_frac": algo_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                           "full_api": {"algorithmic_bytes": scene.algorithmic_bytes_full_api(),
-                                        "frac": scene.algorithmic_bytes_full_api() / (kernel_ms[dominant] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                        "path_frac": scene.algorithmic_bytes_full_api() / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                           "reported_as_frac": "scene_only"},
-                       "hbm_bytes_per_launch_pmc": pmc}
-    if not chunked:
-        out["roofline"].update(secondary_roofline(
-            pl, mix_plan, kernel_ms, load_pmc_valu(scene.name, pl.log2_block) if args.scale == 1.0 else None,
-            out["roofline"]["scene_traffic"], algo_bytes, dominant))
+    if instrumented is not None:
+        out["timing"]["ms_per_step_with_stage_events"] = instrumented / args.steps * 1e3
+        out["roofline"] = stage_roofline(args, scene, pl, mix_plan, stages, chunked, ev, ms_per_step)
     if args.other_configs and world == 1 and not emulate and args.config == "cfg2" and args.scale == 1.0:
         out["other_configs"] = other_configs_leg(ctx, r)
         if any(not v.get("parity", {}).get("ok", True) for v in out["other_configs"].values()):
@@ -1095,7 +1125,7 @@ def run_scene_per_rank_mode(ctx):
         out["end_to_end"] = end_to_end_leg(r, scene, args.end_to_end, multi)
     if args.dropin > 0 and not emulate and not any(sp.is_moving for sp in scene.specs):
         out["end_to_end_dropin"] = dropin_leg(scene, r, args.dropin, multi)
-    if (args.gather and world > 1) or (ctx["use_dist"] and world == 1):
+    if args.gather and ctx["use_dist"]:
         out["gather"], ok = gather_and_validate(ctx, r, scene_tensor(mix, scene, mix_plan, emulate, torch),
                                                 lambda peer: rerender(ctx, r, peer))
         gather_vs_render(out["gather"], ms_per_step, 1, scene, world)
@@ -1416,7 +1446,7 @@ def run_scene_batch_mode(ctx):
     out["roofline"] = {"bound": "hbm", "kernel": "whole step (all scenes of the batch)", "peak": HBM_PEAK_GBS, "unit": "GB/s",
                        "achieved": algo / elapsed * args.steps / 1e9 / world, "frac": algo / elapsed * args.steps / 1e9 / world / HBM_PEAK_GBS,
                        "traffic": None, "algorithmic_bytes_per_step": algo}
-    if ctx["use_dist"]:
+    if ctx["use_dist"] and args.gather:
         as_t = (lambda b: torch.from_numpy(b[:n_out]).reshape(scene0.n_capsules, -1)) if emulate else \
             (lambda b: b[:n_out].reshape(scene0.n_capsules, -1))
         local = {idx: as_t(buf) for idx, buf in zip(mine, outputs)}
@@ -1492,11 +1522,13 @@ def run_capsule_sharded_mode(ctx):
     dumped = None
     if args.dump_outputs and rank == 0:      # rank 0's capsule rows of the scene and of every event
         dumped = dump_outputs(args.dump_outputs, [mix.scene], rows * mix_plan.n_samples, batch.result(), emulate, torch)
-    ctx["barrier"]()
-    for _ in range(args.steps):     # instrumented pass: the two exchanges between HIP events on the launch stream
-        step(timers)
-    ctx["device_sync"]()
-    coll = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in timers.items() if k != "make_event"}
+    coll = None
+    if args.full:
+        ctx["barrier"]()
+        for _ in range(args.steps):     # instrumented pass: the two exchanges between HIP events on the launch stream
+            step(timers)
+        ctx["device_sync"]()
+        coll = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in timers.items() if k != "make_event"}
     by_rank = ctx["all_ranks"](own_s[-1] / args.steps * 1e3)
     elapsed = float(np.median(rep_s))
     out = base_record(ctx, scene, pl, args.steps * scene.duration / elapsed, rep_s, args.steps, "strong",
@@ -1504,15 +1536,16 @@ def run_capsule_sharded_mode(ctx):
     out["timing"]["ms_per_step_by_rank_last_repeat"] = [round(x, 4) for x in by_rank]
     if dumped is not None:
         out["dump_outputs"] = dumped
-    out["collectives_ms"] = dict(coll, note="mean device time per step between HIP events around each exchange (includes "
-                                            "waiting for the slowest rank): per-emitter IR norm sums (SUM) before the accumulate, "
-                                            "E x {sum|x|, #non-finite} (SUM) + E x max|x| (MAX) before the level law")
+    if coll is not None:
+        out["collectives_ms"] = dict(coll, note="mean device time per step between HIP events around each exchange (includes "
+                                                "waiting for the slowest rank): per-emitter IR norm sums (SUM) before the accumulate, "
+                                                "E x {sum|x|, #non-finite} (SUM) + E x max|x| (MAX) before the level law")
     algo = scene.algorithmic_bytes()
     out["roofline"] = {"bound": "hbm", "kernel": "whole step", "peak": HBM_PEAK_GBS, "unit": "GB/s",
                        "achieved": algo / world / (elapsed / args.steps) / 1e9,
                        "frac": algo / world / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, "traffic": None,
                        "algorithmic_bytes_per_launch": algo}
-    if ctx["use_dist"]:
+    if ctx["use_dist"] and args.gather:
         mine = mix.scene[: rows * mix_plan.n_samples].reshape(rows, -1)
         mine = torch.from_numpy(mine) if emulate else mine
         ctx["barrier"]()

@@ -4,7 +4,7 @@ out=gpurun_out/ir_run.txt; : > $out
 for nb in 0 2 3 4 6 12; do
   for cfg in cfg2 cfg3; do
   echo "== $cfg ir nb=$nb" >> $out
-  AL_EXTRA_FLAGS=$((nb<<24)) python bench.py --config $cfg --cpu-events 0 --steps 10 2>&1 | python -c "
+  AL_EXTRA_FLAGS=$((nb<<24)) python bench.py --full --config $cfg --cpu-events 0 --steps 10 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

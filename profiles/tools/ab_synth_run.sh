@@ -1,6 +1,6 @@
 for nb in 0 2 3 4 6 8 12 24; do
   echo "nb=$nb" >> gpurun_out/synth_run.txt
-  AL_EXTRA_FLAGS=$((nb<<16)) python bench.py --cpu-events 0 --steps 20 2>&1 | python -c "
+  AL_EXTRA_FLAGS=$((nb<<16)) python bench.py --full --cpu-events 0 --steps 20 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

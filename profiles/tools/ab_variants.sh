@@ -5,7 +5,7 @@ out=gpurun_out/variants.txt; : > $out
 for rep in 1 2; do
 for lib in profiles/tools/variants/lib_*.so; do
   echo "== $lib (pass $rep)" >> $out
-  AUDIBLELIGHT_HIP_LIB=$PWD/$lib python bench.py --cpu-events 0 --steps 100 --end-to-end 0 --dropin 0 $1 2>&1 | python -c "
+  AUDIBLELIGHT_HIP_LIB=$PWD/$lib python bench.py --full --cpu-events 0 --steps 100 --end-to-end 0 --dropin 0 $1 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

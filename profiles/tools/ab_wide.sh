@@ -5,7 +5,7 @@ out=gpurun_out/wide.txt; : > $out
 for cfg in "cfg2 0" "cfg2 4" "cfg2 --log2-block=14 0" "cfg2 --log2-block=14 4" "cfg3 0" "cfg3 4" "cfg5 0" "cfg5 4"; do
   set -- $cfg; flags=${@: -1}; args="${@:1:$#-1}"
   echo "== $args AL_EXTRA_FLAGS=$flags" >> $out
-  AL_EXTRA_FLAGS=$flags python bench.py --config $args --cpu-events 0 --steps 10 2>&1 | python -c "
+  AL_EXTRA_FLAGS=$flags python bench.py --full --config $args --cpu-events 0 --steps 10 2>&1 | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,7 @@
 # Planner rule check (round 5): short IRs -- cfg4's 1 s RIR is 6 partitions of 8192 -- at B = 4096 (12 partitions, the 4096-point
 # transform shape, clips of 47 blocks through the LDS-ring capsule loop) against the planner's B = 8192; cfg2 beside it.
 R=${GRAFT_REPO_ROOT:-.}; cd $R
-Q="--cpu-events 0 --cpu-workers 0 --end-to-end 0 --dropin 0 --other-configs 0 --parity-events 0 --repeats 3"
+Q="--full --cpu-events 0 --cpu-workers 0 --end-to-end 0 --dropin 0 --other-configs 0 --parity-events 0 --repeats 3"
 show() { python3 -c "
 import json, sys
 for l in sys.stdin:

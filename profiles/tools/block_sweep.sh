@@ -1,4 +1,4 @@
-Q="--cpu-events 0 --end-to-end 0 --dropin 0 --steps 20 --warmup 3"
+Q="--full --cpu-events 0 --end-to-end 0 --dropin 0 --steps 20 --warmup 3"
 for cfg in cfg5 cfg3 cfg4 cfg2; do for lb in 12 13 14; do
 python3 bench.py --config $cfg --log2-block $lb $Q 2>/dev/null | python3 -c "
 import json,sys

@@ -24,9 +24,10 @@ for CFG in $CONFIGS; do
 done
 cd $R
 cp gpurun_out/${TAG}_pmc_traffic.json profiles/pmc_traffic.json   # so the bench lines below carry roofline.traffic
-python3 bench.py > gpurun_out/${TAG}_bench_cfg2.json 2> gpurun_out/${TAG}_bench_cfg2.err; echo "bench cfg2 rc=$?"
-python3 bench.py --steps 20 --warmup 5 --cpu-events 0 --cpu-workers 0 --end-to-end 0 --dropin 0 --other-configs 0 > gpurun_out/${TAG}_bench_cfg2_steps20.json 2>/dev/null; echo "bench cfg2 (driver's flags) rc=$?"
-python3 bench.py --config cfg3 --steps 30 --warmup 3 --cpu-events 1 --cpu-workers 0 > gpurun_out/${TAG}_bench_cfg3.json 2>/dev/null; echo "cfg3 rc=$?"
-python3 bench.py --config cfg5 --steps 30 --warmup 3 --cpu-events 1 --cpu-workers 0 --end-to-end 8 --dropin 0 > gpurun_out/${TAG}_bench_cfg5.json 2>/dev/null; echo "cfg5 rc=$?"
-python3 bench.py --config cfg4 --steps 100 --warmup 3 --cpu-workers 0 > gpurun_out/${TAG}_bench_cfg4.json 2>/dev/null; echo "cfg4 rc=$?"
+# the bench lines go where profiles/tools/design_tables.py reads them; every one but the plain run of the driver's command is --full
+python3 bench.py --full > profiles/${TAG}_bench_cfg2.json; echo "bench cfg2 rc=$?"
+python3 bench.py --steps 20 --warmup 5 > profiles/${TAG}_bench_cfg2_steps20.json 2>/dev/null; echo "bench cfg2 (the driver's command) rc=$?"
+python3 bench.py --full --config cfg3 --steps 30 --warmup 3 --cpu-events 1 --cpu-workers 0 > profiles/${TAG}_bench_cfg3.json 2>/dev/null; echo "cfg3 rc=$?"
+python3 bench.py --full --config cfg5 --steps 30 --warmup 3 --cpu-events 1 --cpu-workers 0 --end-to-end 8 --dropin 0 > profiles/${TAG}_bench_cfg5.json 2>/dev/null; echo "cfg5 rc=$?"
+python3 bench.py --full --config cfg4 --steps 100 --warmup 3 --cpu-workers 0 > profiles/${TAG}_bench_cfg4.json 2>/dev/null; echo "cfg4 rc=$?"
 ls -la gpurun_out | grep ${TAG}

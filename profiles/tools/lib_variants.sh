@@ -4,7 +4,7 @@ for CFG in ${1:-cfg3 cfg5 cfg2}; do
   case $CFG in cfg2|cfg4) S=50;; *) S=10;; esac
   for rep in 1 2; do
   for lib in profiles/tools/mfvariants/lib_*.so; do
-    AUDIBLELIGHT_HIP_LIB=$PWD/$lib python3 bench.py --config $CFG --steps $S --warmup 4 --repeats 3 --cpu-events 0 --cpu-workers 0 --dropin 0 --end-to-end 0 --other-configs 0 2>&1 | python3 -c "
+    AUDIBLELIGHT_HIP_LIB=$PWD/$lib python3 bench.py --full --config $CFG --steps $S --warmup 4 --repeats 3 --cpu-events 0 --cpu-workers 0 --dropin 0 --end-to-end 0 --other-configs 0 2>&1 | python3 -c "
 import json, sys
 for l in sys.stdin:
     if l.startswith('{'):

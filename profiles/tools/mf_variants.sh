@@ -1,6 +1,6 @@
 # cfg3 once per timing build of k_moving_fused (profiles/tools/mfvariants/lib_*.so from -DAL_MF_SKIP=...): per-stage ms
 R=${GRAFT_REPO_ROOT:-.}; cd $R
-Q="--config cfg3 --steps 10 --warmup 3 --repeats 1 --cpu-events 0 --cpu-workers 0 --dropin 0 --end-to-end 0 --other-configs 0"
+Q="--full --config cfg3 --steps 10 --warmup 3 --repeats 1 --cpu-events 0 --cpu-workers 0 --dropin 0 --end-to-end 0 --other-configs 0"
 for lib in profiles/tools/mfvariants/lib_*.so; do
   AUDIBLELIGHT_HIP_LIB=$PWD/$lib python3 bench.py $Q 2>&1 | python3 -c "
 import json, sys

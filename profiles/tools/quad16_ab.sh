@@ -1,7 +1,7 @@
 # Round 4: B = 16384 in four 4096-point transforms (csrc/al_quad16.h) against the default B = 8192, and against the one- / two-
 # transform kernels at B = 16384; same box, alternating:  gpurun -- 'bash profiles/tools/quad16_ab.sh'
 R=${GRAFT_REPO_ROOT:-.}; cd $R
-Q="--steps 10 --warmup 4 --repeats 3 --cpu-events 0 --cpu-workers 0 --dropin 0 --end-to-end 0 --other-configs 0"
+Q="--full --steps 10 --warmup 4 --repeats 3 --cpu-events 0 --cpu-workers 0 --dropin 0 --end-to-end 0 --other-configs 0"
 run() {  # label, config, env..., -- extra args
   label=$1; cfg=$2; shift 2
   env "$@" python3 bench.py --config $cfg $Q $EXTRA 2>/dev/null | python3 -c "

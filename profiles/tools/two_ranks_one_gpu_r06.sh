@@ -7,11 +7,12 @@
 # run, agree on their barriers and report.  Usage: bash profiles/tools/two_ranks_one_gpu_r06.sh > gpurun_out/r06_two_ranks_one_gpu.txt
 cd $GRAFT_REPO_ROOT
 export AL_DIST_BACKEND=gloo AL_BENCH_DEVICE=0
-python bench.py --gpus 2 --config cfg2 --steps 5 --warmup 2 --repeats 2 --cpu-events 0 --end-to-end 8 --dropin 4 > gpurun_out/two_r06_line.txt 2> gpurun_out/two_r06_err.txt
+export LOGS=${LOGS:-$(mktemp -d)}    # the line and the stderr of (1) (set LOGS to keep them somewhere else)
+python bench.py --gpus 2 --config cfg2 --steps 5 --warmup 2 --repeats 2 --cpu-events 0 --end-to-end 8 --dropin 4 --full > $LOGS/two_r06_line.txt 2> $LOGS/two_r06_err.txt
 echo "exit code $?"
 python - <<'PY'
-import json
-for l in open("gpurun_out/two_r06_line.txt"):
+import json, os
+for l in open(os.path.join(os.environ["LOGS"], "two_r06_line.txt")):
     if l.startswith("{"):
         d = json.loads(l)
         strip = lambda x: {k: v for k, v in x.items() if k != "note"}
@@ -21,7 +22,7 @@ for l in open("gpurun_out/two_r06_line.txt"):
         print("gather           ", strip(d["gather"]))
         print("host_share       ", strip(d["host_share"]))
 PY
-tail -3 gpurun_out/two_r06_err.txt
+tail -3 $LOGS/two_r06_err.txt
 echo "---- a rank killed mid-run"
 T0=$(date +%s)
 python bench.py --gpus 2 --config cfg2 --steps 2000000 --warmup 2 --repeats 1 --cpu-events 0 --end-to-end 0 --dropin 0 > gpurun_out/two_r06_dead.txt 2>&1 &

@@ -5,7 +5,7 @@
 #   k_moving_fused  (csrc/al_quad.h, AL_FUSED_MOVING=1) on cfg3
 # Kill criterion: not >= 8 % faster per cfg4 scene -> both leave the product library.
 R=${GRAFT_REPO_ROOT:-.}; cd $R
-Q="--cpu-events 0 --cpu-workers 0 --end-to-end 0 --dropin 0 --other-configs 0 --parity-events 0 --repeats 3"
+Q="--full --cpu-events 0 --cpu-workers 0 --end-to-end 0 --dropin 0 --other-configs 0 --parity-events 0 --repeats 3"
 show() { python3 -c "
 import json, sys
 for l in sys.stdin:

@@ -154,7 +154,7 @@ def test_bench_gpus_flag_spawns_that_many_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(AL_BENCH_EMULATE="1", AL_DIST_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--config", "cfg1",
-           "--scale", "0.05", "--cpu-events", "0"]
+           "--scale", "0.05", "--cpu-events", "0", "--full"]
     def run(extra):
         res = subprocess.run(cmd + extra, env=env, capture_output=True, text=True, timeout=600)
         assert res.returncode == 0, res.stderr[-2000:]
@@ -208,7 +208,7 @@ def test_bench_line_carries_parity_of_what_it_timed():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK") and not k.startswith("AL_")}
     env.update(AL_BENCH_EMULATE="1")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--repeats", "1", "--config", "cfg2",
-           "--scale", "0.005", "--cpu-workers", "0", "--end-to-end", "0", "--dropin", "0"]
+           "--scale", "0.005", "--cpu-workers", "0", "--end-to-end", "0", "--dropin", "0", "--full"]
 
     def run(extra, **more_env):
         res = subprocess.run(cmd + extra, env=dict(env, **more_env), capture_output=True, text=True, timeout=900)
@@ -229,6 +229,49 @@ def test_bench_line_carries_parity_of_what_it_timed():
     assert out["config"]["switches"] == {"static_mac": False}
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """A plain bench run sets up, warms up, times the repeats, writes --dump-outputs and prints the line: none of the legs of
+    --full (per-kernel pass and roofline, CPU baselines, oracle parity, N > 1 gather) runs, while `--full` still gives them.
+    Both runs time the same steps and dump the same arrays, bit for bit (host-emulated kernels here)."""
+    import json
+    import subprocess
+    import sys
+
+    from tests import hostemu
+
+    hostemu.build()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK") and not k.startswith("AL_")}
+    env.update(AL_BENCH_EMULATE="1", AL_DIST_BACKEND="gloo")
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--config", "cfg1", "--scale", "0.05"]
+
+    def run(extra):
+        res = subprocess.run(cmd + extra, env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    plain = run(["--dump-outputs", str(tmp_path / "plain")])
+    full = run(["--dump-outputs", str(tmp_path / "full"), "--full"])
+    for name in ("scene", "event_spatial", "event_scale"):
+        a, b = (np.load(tmp_path / d / (name + ".npy")) for d in ("plain", "full"))
+        assert a.size and np.array_equal(a, b), name
+    for out in (plain, full):
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(out)
+        assert out["value"] > 0 and out["unit"] == "scene-seconds/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert out["steps"] == 2 and out["warmup"] == 1 and out["timing"]["repeats"] == 3
+    legs = {"roofline", "parity", "cpu_baseline", "cpu_baseline_all_cores", "other_configs", "end_to_end", "end_to_end_dropin", "gather"}
+    assert not legs & set(plain) and "ms_per_step_with_stage_events" not in plain["timing"]
+    assert {"roofline", "parity"} <= set(full) and full["parity"]["ok"] and full["roofline"]["kernel_ms"]
+    assert full["cpu_baseline"]["value"] > 0 and "ms_per_step_with_stage_events" in full["timing"]
+    # an option that names a leg runs it without --full
+    assert set(run(["--parity-events", "1", "--repeats", "1"])) & legs == {"parity"}
+    # N > 1: no end-of-job gather and no re-render on rank 0 unless asked for
+    two = run(["--gpus", "2", "--repeats", "1"])
+    assert two["n_gpus"] == 2 and not legs & set(two)
+
+
 def test_bench_eight_ranks_scene_batch_index_arithmetic():
     """BASELINE configs[3]'s launch shape -- eight ranks, a batch of scenes split round-robin, rank 0 receiving from SEVEN peers --
     on gloo with the host-emulated kernels at a reduced scene size: 19 scenes (uneven shares: three ranks own 3, five own 2),
@@ -246,7 +289,7 @@ def test_bench_eight_ranks_scene_batch_index_arithmetic():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(AL_BENCH_EMULATE="1", AL_DIST_BACKEND="gloo", OMP_NUM_THREADS="1")
     base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--repeats", "1", "--config", "cfg1",
-            "--scale", "0.05", "--cpu-events", "0", "--cpu-workers", "0", "--end-to-end", "0", "--dropin", "0"]
+            "--scale", "0.05", "--cpu-events", "0", "--cpu-workers", "0", "--end-to-end", "0", "--dropin", "0", "--full"]
 
     def run(extra):
         res = subprocess.run(base + extra, env=env, capture_output=True, text=True, timeout=900)
@@ -274,7 +317,8 @@ def test_bench_eight_ranks_scene_batch_index_arithmetic():
     # SURVEY 8e row 2 at eight ranks: one cfg2-shaped scene (32 capsules, shrunk lengths), four capsule rows per rank, the two
     # all-reduces inside the step, rows gathered and compared with rank 0's render of the whole scene
     caps = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--repeats", "1",
-                           "--config", "cfg2", "--scale", "0.02", "--shard", "capsules", "--cpu-events", "0", "--cpu-workers", "0"],
+                           "--config", "cfg2", "--scale", "0.02", "--shard", "capsules", "--cpu-events", "0", "--cpu-workers", "0",
+                           "--full"],
                           env=env, capture_output=True, text=True, timeout=900)
     assert caps.returncode == 0, caps.stderr[-3000:]
     out = json.loads([ln for ln in caps.stdout.splitlines() if ln.startswith("{")][0])
