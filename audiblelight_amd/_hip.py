@@ -155,6 +155,9 @@ SYMBOLS = {
     "al_fx_apply": (ct.c_int, [ct.c_int, _P, _P, ct.c_int64, _P, _P, _S]),
     "al_fx_frame_shuffle": (ct.c_int, [_P, _P, ct.c_int64, ct.c_int32, ct.c_int32, _P, ct.c_int32, _S]),
     "al_fx_sos": (ct.c_int, [_P, _P, ct.c_int64, _P, ct.c_int32, _S]),
+    "al_fx_delay": (ct.c_int, [_P, _P, ct.c_int64, ct.c_int64, ct.c_float, ct.c_float, _S]),
+    "al_fx_chorus": (ct.c_int, [_P, _P, ct.c_int64] + [ct.c_double] * 6 + [_S]),
+    "al_fx_phaser": (ct.c_int, [_P, _P, ct.c_int64] + [ct.c_double] * 6 + [_S]),
     "al_pack_ragged_irs": (ct.c_int, [_P, ct.c_int32, _P, _P, ct.c_int64, ct.c_int32, _P, _S]),
     "al_resample_poly": (ct.c_int, [_P, ct.c_int32, ct.c_int64, _P, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.c_int64, ct.c_int64, _S]),
     "al_encode_frames": (ct.c_int, [_P, ct.c_int32, ct.c_int64, ct.c_int32, _P, _S]),

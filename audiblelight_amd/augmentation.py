@@ -4,16 +4,20 @@
 Covered: Gain, Invert, Reverse, Fade, Clipping, Distortion, Bitcrush, Preemphasis, Deemphasis,
 TimeWarpSilence / Duplicate / Remove / Reverse, the linear time-invariant filters LowpassFilter,
 HighpassFilter, LowShelfFilter, HighShelfFilter and MultibandEqualizer (cascades of second-order
-sections, one ``al_fx_sos`` launch each) and the peak normalisation of ``Event.load_audio``.
-The other stateful pedalboard effects (dynamics, modulation, delay, codecs, time-stretch) stay on
-the host with the reference implementation: out of scope.
+sections, one ``al_fx_sos`` launch each), the delay and modulation FX Delay, Chorus and Phaser
+(linear recursions with feedback, one ``al_fx_delay`` / ``al_fx_chorus`` / ``al_fx_phaser`` launch
+each) and the peak normalisation of ``Event.load_audio``.  The other stateful pedalboard effects
+(dynamics: Compressor, Limiter; codecs: GSMFullRateCompressor, MP3Compressor; time-stretch:
+PitchShift, SpeedUp) stay on the host with the reference implementation: out of scope (SURVEY.md
+section 2, row 3b).
 
 Definitions for effects whose reference arithmetic lives in un-vendored third-party wheels
 (parity unpinned, SURVEY.md 8c): Gain = x*10^(dB/20); Clipping = clamp at +-10^(dB/20);
 Distortion = tanh(x*10^(dB/20)); Bitcrush = rint(x*2^bits)/2^bits (pedalboard 0.9.17);
 Preemphasis / Deemphasis = librosa 0.11 ``effects.preemphasis`` / ``deemphasis`` including their
 linear-extrapolation initial state.  The filter FX: see ``_FilterFX`` (first-order low/high-pass, Audio EQ
-Cookbook shelves and peaks, float64 coefficients and state, constant gains at degenerate cutoffs).
+Cookbook shelves and peaks, float64 coefficients and state, constant gains at degenerate cutoffs).  The delay and
+modulation FX: see ``Delay``, ``Chorus`` and ``Phaser``.
 """
 from __future__ import annotations
 
@@ -612,6 +616,121 @@ class MultibandEqualizer(_FilterFX):
         return rows, gain
 
 
+def _feedback(x) -> float:
+    x = _positive(x)
+    if x >= 1.0:
+        raise ValueError(f"Expected feedback to be below 1 (a stable loop) but got {x}")
+    return x
+
+
+class _DelayModFX(EventAugmentation):
+    """Delay and modulation FX: out of place on the device (``clip.other``), float32 like pedalboard's output."""
+
+    def host_dtype(self, in_dtype):
+        return np.dtype(np.float32)     # pedalboard returns float32
+
+    def launch(self, clip, dst) -> None:
+        raise NotImplementedError
+
+    def apply_device(self, clip):
+        dst = clip.other(clip.n)
+        self.launch(clip, dst)
+        clip.swap()
+
+
+class Delay(_DelayModFX):
+    """pedalboard 0.9.17's ``Delay`` (augmentation.py:1046-1102), restated by definition and not checked against a running
+    pedalboard: D = trunc(delay_seconds fs), clamped to 30 fs; ``delay_seconds == 0`` is the identity; otherwise, with
+    w[m] = 0 for m < 0, d[t] = w[t - D], w[t] = x[t] + feedback d[t], y = (1 - mix) x + mix d (the line is read before it
+    is written: D = 0 gives d = 0).  mix is used as given.  feedback >= 1 is refused (an unstable loop)."""
+
+    MIN_DELAY, MAX_DELAY = 0.01, 1.0
+    MIN_FEEDBACK, MAX_FEEDBACK = 0.1, 0.5
+    MIN_MIX, MAX_MIX = 0.1, 0.5
+    MAX_DELAY_SECONDS = 30          # pedalboard's longest delay line
+
+    def __init__(self, sample_rate=config.SAMPLE_RATE, delay_seconds=None, feedback=None, mix=None):
+        super().__init__(sample_rate)
+        self.delay_seconds = _positive(_sample(delay_seconds, self.MIN_DELAY, self.MAX_DELAY))
+        self.feedback = _feedback(_sample(feedback, self.MIN_FEEDBACK, self.MAX_FEEDBACK))
+        self.mix = _positive(_sample(mix, self.MIN_MIX, self.MAX_MIX))
+        self.params = dict(delay_seconds=self.delay_seconds, feedback=self.feedback, mix=self.mix)
+
+    @property
+    def delay_samples(self) -> int:
+        return min(int(self.delay_seconds * self.sample_rate), self.MAX_DELAY_SECONDS * self.sample_rate)
+
+    def apply_device(self, clip):
+        if self.delay_seconds == 0:
+            return                      # pedalboard special-cases it: the identity
+        super().apply_device(clip)
+
+    def launch(self, clip, dst):
+        r = clip.r
+        r.lib.call("al_fx_delay", r.mem.ptr(clip.buf), r.mem.ptr(dst), clip.n, self.delay_samples, ct.c_float(self.feedback),
+                   ct.c_float(self.mix), r.mem.stream())
+
+
+class _Modulation(_DelayModFX):
+    MIN_RATE, MAX_RATE = 0, 10
+    MIN_DEPTH, MAX_DEPTH = 0.0, 1.0
+    MIN_MIX, MAX_MIX = 0.1, 0.5
+    MIN_FEEDBACK, MAX_FEEDBACK = 0.0, 0.9
+    CENTRE = ""                     # the name of the centre parameter
+    ENTRY = ""
+
+    def __init__(self, sample_rate, rate_hz, depth, centre, feedback, mix):
+        super().__init__(sample_rate)
+        self.rate_hz = _positive(_sample(rate_hz, self.MIN_RATE, self.MAX_RATE))
+        self.depth = _positive(_sample(depth, self.MIN_DEPTH, self.MAX_DEPTH))
+        centre = _positive(_sample(centre, self.MIN_CENTRE, self.MAX_CENTRE))
+        setattr(self, self.CENTRE, centre)
+        self.feedback = _feedback(_sample(feedback, self.MIN_FEEDBACK, self.MAX_FEEDBACK))
+        self.mix = _positive(_sample(mix, self.MIN_MIX, self.MAX_MIX))
+        self.params = {"rate_hz": self.rate_hz, "depth": self.depth, self.CENTRE: centre, "feedback": self.feedback,
+                       "mix": self.mix}
+
+    def launch(self, clip, dst):
+        r = clip.r
+        r.lib.call(self.ENTRY, r.mem.ptr(clip.buf), r.mem.ptr(dst), clip.n, float(self.sample_rate), float(self.rate_hz),
+                   float(self.depth), float(getattr(self, self.CENTRE)), float(self.feedback), float(self.mix), r.mem.stream())
+
+
+class Chorus(_Modulation):
+    """JUCE's ``dsp::Chorus`` as pedalboard 0.9.17 wraps it (augmentation.py:746-829), restated by definition and not checked
+    against a running pedalboard.  lfo_t = sin(2 pi rate t / fs - pi) (JUCE's oscillator returns its old phase minus pi;
+    the phase is exact float64 here, JUCE accumulates it in float32); tau_t = clamp(max(1, 10 depth lfo_t + centre_delay_ms)
+    fs / 1000, 0, ceil(110 fs / 1000)) = i_t + f_t; with u[m] = 0 for m < 0, u[t] = x[t] - feedback v[t-1],
+    v[t] = u[t - i_t] + f_t (u[t - i_t - 1] - u[t - i_t]), y = (1 - m) x + m v with m = min(mix, 1) (JUCE's DryWetMixer
+    clamps it).  feedback >= 1 is refused (an unstable loop)."""
+
+    MIN_CENTRE, MAX_CENTRE = MIN_DELAY, MAX_DELAY = 1.0, 20.0
+    CENTRE = "centre_delay_ms"
+    ENTRY = "al_fx_chorus"
+
+    def __init__(self, sample_rate=config.SAMPLE_RATE, rate_hz=None, depth=None, centre_delay_ms=None, feedback=None,
+                 mix=None):
+        super().__init__(sample_rate, rate_hz, depth, centre_delay_ms, feedback, mix)
+
+
+class Phaser(_Modulation):
+    """JUCE's ``dsp::Phaser`` as pedalboard 0.9.17 wraps it (augmentation.py:963-1043), restated by definition and not checked
+    against a running pedalboard.  fmax = min(20000, 0.49 fs), c = log10(fc / 20) / log10(fmax / 20); the LFO ticks every 4
+    samples: lfo_k = clamp(0.5 depth sin(2 pi rate 4k / fs - pi) + c, 0, 1), f_k = 20 (fmax / 20)^lfo_k; six first-order TPT
+    all-passes share G = g / (1 + g), g = tan(pi f_k / fs), each {v = G (in - s), lp = v + s, s = lp + v, out = 2 lp - in};
+    per sample in_0 = x - L, wet = the sixth stage's output, L = feedback wet; y = (1 - m) x + m wet, m = min(mix, 1).
+    float64 LFO phase and state; feedback >= 1 is refused; 0.49 fs must exceed 20 Hz."""
+
+    MIN_CENTRE, MAX_CENTRE = MIN_FREQ, MAX_FREQ = 260, 6500
+    CENTRE = "centre_frequency_hz"
+    ENTRY = "al_fx_phaser"
+
+    def __init__(self, sample_rate=config.SAMPLE_RATE, rate_hz=None, depth=None, centre_frequency_hz=None, feedback=None,
+                 mix=None):
+        super().__init__(sample_rate, rate_hz, depth, centre_frequency_hz, feedback, mix)
+
+
 ALL_EVENT_AUGMENTATIONS = [Gain, Invert, Reverse, Fade, Clipping, Distortion, Bitcrush, Preemphasis, Deemphasis,
                            TimeWarpSilence, TimeWarpDuplicate, TimeWarpRemove, TimeWarpReverse,
-                           LowpassFilter, HighpassFilter, LowShelfFilter, HighShelfFilter, MultibandEqualizer]
+                           LowpassFilter, HighpassFilter, LowShelfFilter, HighShelfFilter, MultibandEqualizer,
+                           Delay, Chorus, Phaser]

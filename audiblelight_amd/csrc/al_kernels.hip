@@ -20,6 +20,7 @@
 #include "al_bigfft.h"
 #include "al_stft.h"
 #include "al_sos.h"
+#include "al_delayfx.h"
 
 namespace al {
 
@@ -1664,6 +1665,113 @@ int al_fx_sos(const float *src, float *dst, int64_t n, const double *sos, int32_
   }
   hipLaunchKernelGGL(al::k_fx_sos, dim3(1), dim3(al::SOS_THREADS), 0, (hipStream_t)stream, src, dst, n, run, a);
   return check_launch("k_fx_sos");
+}
+
+// ---- delay and modulation FX: out of place, every parameter finite and >= 0, feedback < 1
+namespace {
+bool fx_overlap(const float *a, const float *b, int64_t n) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
+  return pa < pb + bytes && pb < pa + bytes;
+}
+
+// 0, or the error for the first bad argument
+int fx_check(const char *fn, const float *src, const float *dst, int64_t n, const char *const *names, const double *vals,
+             int count) {
+  char msg[200];
+  if (!src || !dst) {
+    snprintf(msg, sizeof(msg), "%s: null pointer", fn);
+    return fail(AL_E_BADARG, msg);
+  }
+  if (n < 1) {
+    snprintf(msg, sizeof(msg), "%s: n must be >= 1", fn);
+    return fail(AL_E_BADARG, msg);
+  }
+  if (fx_overlap(src, dst, n)) {
+    snprintf(msg, sizeof(msg), "%s: dst overlaps src (out of place only)", fn);
+    return fail(AL_E_BADARG, msg);
+  }
+  for (int i = 0; i < count; ++i) {
+    if (!isfinite(vals[i]) || vals[i] < 0.0) {
+      snprintf(msg, sizeof(msg), "%s: %s must be finite and >= 0", fn, names[i]);
+      return fail(AL_E_BADARG, msg);
+    }
+    if (!strcmp(names[i], "feedback") && vals[i] >= 1.0) {
+      snprintf(msg, sizeof(msg), "%s: feedback must be < 1 (unstable loop)", fn);
+      return fail(AL_E_BADARG, msg);
+    }
+  }
+  return AL_OK;
+}
+}  // namespace
+
+int al_fx_delay(const float *src, float *dst, int64_t n, int64_t delay_samples, float feedback, float mix, al_stream_t stream) {
+  static const char *const names[] = {"feedback", "mix"};
+  const double vals[] = {feedback, mix};
+  if (int e = fx_check("al_fx_delay", src, dst, n, names, vals, 2)) return e;
+  if (delay_samples < 0) return fail(AL_E_BADARG, "al_fx_delay: delay_samples must be >= 0");
+  const al::DelayPlan pl = al::delay_plan(n, delay_samples, (double)feedback);
+  const int64_t grid = (pl.residues + pl.G - 1) / pl.G;
+  hipLaunchKernelGGL(al::k_fx_delay, dim3((unsigned)grid), dim3(pl.G * pl.P), 0, (hipStream_t)stream, src, dst, n, pl,
+                     (double)feedback, 1.0 - (double)mix, (double)mix);
+  return check_launch("k_fx_delay");
+}
+
+int al_fx_chorus(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_delay_ms,
+                 double feedback, double mix, al_stream_t stream) {
+  static const char *const names[] = {"fs", "rate_hz", "depth", "centre_delay_ms", "feedback", "mix"};
+  const double vals[] = {fs, rate_hz, depth, centre_delay_ms, feedback, mix};
+  if (int e = fx_check("al_fx_chorus", src, dst, n, names, vals, 6)) return e;
+  const double tau_max = ceil(110.0 * fs / 1000.0);
+  const double b_min = floor(fs / 1000.0);   // tau >= fs / 1000: the 1 ms floor of the delay
+  if (!(b_min >= 1.0) || tau_max + b_min + 2.0 > (double)al::CHO_RING)
+    return fail(AL_E_BADARG, "al_fx_chorus: fs out of range (1000 <= fs and ceil(0.11 fs) + floor(fs / 1000) + 2 <= 16384)");
+  al::ChorusArgs a;
+  a.fs = fs;
+  a.rate = rate_hz;
+  a.depth10 = 10.0 * depth;
+  a.centre_ms = centre_delay_ms;
+  a.tau_max = tau_max;
+  a.fb = feedback;
+  const double m = mix < 1.0 ? mix : 1.0;   // JUCE's DryWetMixer clamps the proportion
+  a.dry = 1.0 - m;
+  a.wet = m;
+  // B = floor of a lower bound of every tau_t, one sample short of it against rounding, never below the 1 ms floor
+  const double lowest = fmin(fmax(1.0, centre_delay_ms - 10.0 * depth) * fs / 1000.0, tau_max);
+  double b = floor(lowest) - 1.0;
+  b = b > b_min ? b : b_min;
+  b = b < (double)al::CHO_MAX_BLOCK ? b : (double)al::CHO_MAX_BLOCK;
+  b = b < (double)al::CHO_RING - tau_max - 2.0 ? b : (double)al::CHO_RING - tau_max - 2.0;
+  a.block = (int64_t)b;
+  if (feedback == 0.0) {
+    const int64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(al::k_fx_chorus_ff, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0,
+                       (hipStream_t)stream, src, dst, n, a);
+    return check_launch("k_fx_chorus_ff");
+  }
+  hipLaunchKernelGGL(al::k_fx_chorus_fb, dim3(1), dim3(al::CHO_THREADS), 0, (hipStream_t)stream, src, dst, n, a);
+  return check_launch("k_fx_chorus_fb");
+}
+
+int al_fx_phaser(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_frequency_hz,
+                 double feedback, double mix, al_stream_t stream) {
+  static const char *const names[] = {"fs", "rate_hz", "depth", "centre_frequency_hz", "feedback", "mix"};
+  const double vals[] = {fs, rate_hz, depth, centre_frequency_hz, feedback, mix};
+  if (int e = fx_check("al_fx_phaser", src, dst, n, names, vals, 6)) return e;
+  if (!(0.49 * fs > 20.0)) return fail(AL_E_BADARG, "al_fx_phaser: fs out of range (0.49 fs must exceed 20 Hz)");
+  const double fmax_hz = fmin(20000.0, 0.49 * fs);
+  al::PhaserArgs a;
+  a.fs = fs;
+  a.rate = rate_hz;
+  a.half_depth = 0.5 * depth;
+  a.c = log10(centre_frequency_hz / 20.0) / log10(fmax_hz / 20.0);   // -inf at fc = 0: the LFO clamps it to 0
+  a.log_ratio = log(fmax_hz / 20.0);
+  a.fb = feedback;
+  const double m = mix < 1.0 ? mix : 1.0;
+  a.dry = 1.0 - m;
+  a.wet = m;
+  hipLaunchKernelGGL(al::k_fx_phaser, dim3(1), dim3(al::PH_THREADS), 0, (hipStream_t)stream, src, dst, n,
+                     al::phaser_run_length(n), a);
+  return check_launch("k_fx_phaser");
 }
 
 // ---- arbitrary-length inverse real FFT (ambience)

@@ -289,6 +289,29 @@ int al_fx_frame_shuffle(const float *src, float *dst, int64_t n, int32_t frame_l
  * pole of magnitude >= 1; al_last_error() names the reason and the section. */
 #define AL_SOS_MAX_SECTIONS 16
 int al_fx_sos(const float *src, float *dst, int64_t n, const double *sos, int32_t n_sections, al_stream_t stream);
+/* Delay and modulation FX (Delay, Chorus, Phaser; augmentation.py:746-829, 963-1043, 1046-1102).  pedalboard is not vendored:
+ * these restate pedalboard 0.9.17's Delay and JUCE's dsp::Chorus / dsp::Phaser as this project reads them, unchecked against
+ * a running pedalboard (DESIGN.md "Delay and modulation FX").  src / dst: float32 clips of n samples; every state starts at
+ * zero; out of place only (dst must not overlap src).  Recursion state is float64; the LFO phase is exact (float64).
+ * AL_E_BADARG, with al_last_error() naming the parameter, for a null pointer, overlap, n < 1, a non-finite or negative
+ * parameter, feedback >= 1 (an unstable loop) or fs out of range.
+ *
+ * al_fx_delay: D = delay_samples (the caller truncates delay_seconds * fs and clamps it to 30 fs); with w[m] = 0 for m < 0,
+ *   d[t] = w[t - D], w[t] = x[t] + feedback d[t], y = (1 - mix) x + mix d.  The line is read before it is written, so D = 0
+ *   (and D >= n) gives d = 0.  mix is used as given.  (delay_seconds == 0 is the identity: the caller makes no call.)
+ * al_fx_chorus: lfo_t = sin(2 pi rate_hz t / fs - pi); tau_t = clamp(max(1, 10 depth lfo_t + centre_delay_ms) fs / 1000, 0,
+ *   ceil(110 fs / 1000)) = i_t + f_t; with u[m] = 0 for m < 0: u[t] = x[t] - feedback v[t-1],
+ *   v[t] = u[t - i_t] + f_t (u[t - i_t - 1] - u[t - i_t]); y = (1 - m) x + m v, m = min(mix, 1).
+ *   fs must satisfy 1000 <= fs and ceil(0.11 fs) + floor(fs / 1000) + 2 <= 16384 (the u history lives in LDS).
+ * al_fx_phaser: fmax = min(20000, 0.49 fs), c = log10(fc / 20) / log10(fmax / 20); the LFO ticks at t = 4k:
+ *   lfo_k = clamp(0.5 depth sin(2 pi rate_hz 4k / fs - pi) + c, 0, 1), f_k = 20 (fmax / 20)^lfo_k, g = tan(pi f_k / fs),
+ *   G = g / (1 + g) for samples 4k .. 4k + 3.  Per sample: in = x - L, six TPT all-passes {v = G (in - s), lp = v + s,
+ *   s = lp + v, in = 2 lp - in}, wet = in, L = feedback wet; y = (1 - m) x + m wet, m = min(mix, 1).  0.49 fs must exceed 20. */
+int al_fx_delay(const float *src, float *dst, int64_t n, int64_t delay_samples, float feedback, float mix, al_stream_t stream);
+int al_fx_chorus(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_delay_ms,
+                 double feedback, double mix, al_stream_t stream);
+int al_fx_phaser(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_frequency_hz,
+                 double feedback, double mix, al_stream_t stream);
 /* ---- Ambience (A12): Timmer-Koenig (1/f)^beta noise, audiblelight/ambience.py:271-375.
  * The host draws the two standard-normal sets with numpy's default_rng(seed) (PCG64 + ziggurat, ambience.py:351-356:
  * the reference's RNG stream is data-dependent and is not re-implemented on the device); everything after the draws
