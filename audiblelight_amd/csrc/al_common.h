@@ -14,8 +14,13 @@
 // protects them is that the result must not depend on the ORDER in which the waves of a workgroup reach their barriers.  A build with
 // AL_SHAKE = 1, 2, ... (tests/shake.py; never the product library) makes every wave sleep a wave-, workgroup- and site-dependent
 // number of cycles after every workgroup barrier of either kind, after every LDS-DMA issue and before every counted wait, so waves
-// leave each barrier out of step by up to a few hundred cycles; tests/test_gpu_shake.py asserts that every kernel family renders bit for
-// bit what the product library renders.  A missing barrier (round 4's al_quad16.h race) shows up as a mismatch there.
+// leave each barrier out of step by up to a few hundred cycles.  tests/test_gpu_shake.py (the render stage, eleven batches) and
+// tests/test_gpu_shake_standalone.py (the barrier kernels only a direct call launches: separate_spectra, fx_sos, fx_delay, fx_chorus,
+// fx_phaser, fx_deemph, stats, encode) assert that every family comes out bit for bit the same from two differently perturbed builds and run to
+// run, and within a derived bound of the product library's output: a few float32 roundings for the render families (the sleep loops
+// split basic blocks, and FMA contraction works per basic block), the sum of the two float64-reference bounds for the standalone
+// ones, and equality where equality has been observed.  A missing barrier (round 4's al_quad16.h race; the AL_TEST_REVERT_* guards of
+// the `revert` build) shows up as a mismatch there.
 #ifndef AL_SHAKE
 #define AL_SHAKE 0
 #endif

@@ -82,7 +82,9 @@ __global__ __launch_bounds__(1024) void k_fx_delay(const float *x, float *y, int
     carry[tid] = w;
     __syncthreads();
     if (p >= d) w = fma(ph, carry[tid - d * pl.G], w);
+#ifndef AL_TEST_REVERT_DELAY_BARRIER   // tests/shake.py `revert`: without it the next step's carry[tid] = w overtakes this step's reads
     __syncthreads();
+#endif
     ph *= ph;
   }
   carry[tid] = w;

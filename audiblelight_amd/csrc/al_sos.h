@@ -74,7 +74,9 @@ __device__ inline void sos_sweep(const float *in, float *out, int64_t n, int64_t
         t2 = fma(-d2, z, c2 * v);
       }
     }
+#ifndef AL_TEST_REVERT_SOS_BARRIER   // tests/shake.py `revert`: without it the copy-out below reads rows their owners still filter
     __syncthreads();
+#endif
     if (write) {
       for (int f = tid; f < SOS_THREADS * SOS_SEG; f += SOS_THREADS) {
         const int t = f / SOS_SEG, i = f - t * SOS_SEG;

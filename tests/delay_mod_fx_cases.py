@@ -178,6 +178,7 @@ def run_delay_edges(r, n, D, fb=0.7, mix=0.4, shift=0):
     call_delay(r, r.mem.ptr(src), out.ptr, n, D, fb, mix)
     got = out.get()
     check(got, ref_delay(x, D, float(np.float32(fb)), float(np.float32(mix))), what=(n, D))
+    return got
 
 
 def run_delay_special():
@@ -238,6 +239,29 @@ def run_edge_lengths(r, n, shift=0, fs=48000):
     out = ke.Guarded(r, n, shift=shift)
     r.lib.call("al_fx_phaser", r.mem.ptr(src), out.ptr, n, float(fs), 8.0, 0.9, 900.0, 0.8, 0.6, r.mem.stream())
     check(out.get(), ref_phaser(x, fs, 8.0, 0.9, 900.0, 0.8, 0.6), what=("phaser", n))
+
+
+def run_chorus_case(r, n, fs, rate_hz, depth, centre_delay_ms, feedback, mix, shift=0):
+    """al_fx_chorus with every parameter the caller's, into a guarded buffer, against the oracle; returns the device output."""
+    x = ke.signal(n, 700 + n, special=True)
+    src = ke.dev(r, x)
+    out = ke.Guarded(r, n, shift=shift)
+    r.lib.call("al_fx_chorus", r.mem.ptr(src), out.ptr, n, float(fs), rate_hz, depth, centre_delay_ms, feedback, mix, r.mem.stream())
+    got = out.get()
+    check(got, ref_chorus(x, fs, rate_hz, depth, centre_delay_ms, feedback, mix), what=("chorus", n, fs, feedback))
+    return got
+
+
+def run_phaser_case(r, n, fs, rate_hz, depth, centre_frequency_hz, feedback, mix, shift=0):
+    """al_fx_phaser likewise."""
+    x = ke.signal(n, 800 + n, special=True)
+    src = ke.dev(r, x)
+    out = ke.Guarded(r, n, shift=shift)
+    r.lib.call("al_fx_phaser", r.mem.ptr(src), out.ptr, n, float(fs), rate_hz, depth, centre_frequency_hz, feedback, mix,
+               r.mem.stream())
+    got = out.get()
+    check(got, ref_phaser(x, fs, rate_hz, depth, centre_frequency_hz, feedback, mix), what=("phaser", n, fs, feedback))
+    return got
 
 
 def run_long(r, kind, n, fs=48000, **kw):

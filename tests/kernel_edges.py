@@ -207,6 +207,7 @@ def run_fx_deemphasis(r, n, coef, shift=0, seed=2):
     record("fx_deemphasis (err/peak * (1-c) / eps)", peak_error(got, ref) * (1 - c) / EPS, 2.0)
     if c <= 0.999:
         assert_parity(got, ref, what=("deemphasis", n, coef))
+    return got
 
 
 def run_fx_fade(r, n, n_in, n_out, shape_in, shape_out, shift=0, seed=3):
@@ -299,12 +300,14 @@ def run_peak_scale(r, n, seed=7):
         "inf": np.concatenate([base[:n // 2], [np.inf], base[n // 2 + 1:]]).astype(np.float32)[:n],
         "nan": np.concatenate([base[:n // 2], [np.nan], base[n // 2 + 1:]]).astype(np.float32)[:n],
     }
+    every = []
     for name, clip in clips.items():
         d = dev(r, clip)
         for s in (1.0, -1.0, float(np.float32(10 ** (12 / 20))), 4.0, 1e-3):
             out = Guarded(r, 1)
             r.lib.call("al_peak_scale", r.mem.ptr(d), n, ct.c_float(s), out.ptr, r.mem.stream())
             got = out.get()[0]
+            every.append(got)
             s32 = float(np.float32(s))
             # fmaxf drops NaN, so the scale comes from the finite samples (the NaN samples themselves still reach the render,
             # whose finite check refuses them); an all-NaN clip leaves max 0
@@ -316,6 +319,7 @@ def run_peak_scale(r, n, seed=7):
                 assert got == 0.0, (name, s, got)
             else:
                 record("peak_scale (ulp)", float(ulps(np.float64(got), ref)), 0.5 + 1e-6)
+    return np.array(every, np.float32)
 
 
 def run_clip_scales(r, lens, seed=17):
@@ -347,6 +351,7 @@ def run_clip_scales(r, lens, seed=17):
         peak = float(np.max(np.abs(audio[offs[e]:offs[e] + n].astype(np.float64))))
         ref = float(np.clip(s32 / (abs(s32) * peak + TINY32), -FLT_MAX, FLT_MAX))
         record("peak_scale (ulp)", float(ulps(np.float64(got[e]), ref)), 0.5 + 1e-6)
+    return got
 
 
 # ----------------------------------------------------------------------------- al_row_stats, al_ambience_scales
@@ -377,7 +382,7 @@ def run_row_stats(r, rows, cols, nonfinite=False, seed=8):
         err = np.abs(got[fin, k] - ref[fin]) / ref[fin]
         record("row_stats sums (rel err / eps)", float(err.max()) / EPS if err.size else 0.0, 40.0)
         np.testing.assert_array_equal(got[~fin, k], ref[~fin])    # Inf stays Inf, NaN (or Inf - Inf) is NaN
-    return x
+    return got
 
 
 def run_ambience_scales(r, rows, cols, seed=9):
@@ -390,17 +395,20 @@ def run_ambience_scales(r, rows, cols, seed=9):
         stats[1] = 0.0                     # a silent channel
     d = dev(r, stats.reshape(-1))
     tiny64 = np.finfo(np.float64).tiny
+    every = []
     for normalize in (0, 1, 2):
         for ref_db in (-65.0, 0.0, 12.5):
             out = Guarded(r, rows)
             r.lib.call("al_ambience_scales", r.mem.ptr(d), rows, cols, ct.c_float(ref_db), normalize, out.ptr, r.mem.stream())
             got = out.get()
+            every.append(got)
             inv = 1.0 / (stats[:, 1] + tiny64) if normalize else np.ones(rows)
             mean_abs = np.sum(stats[:, 0] * inv) / (rows * cols)
             mult = 10.0 ** (float(np.float32(ref_db)) / 20.0) / (mean_abs + tiny64)
             ref = np.clip(inv if normalize == 2 else mult * inv, -FLT_MAX, FLT_MAX)
             assert np.all(np.isfinite(got))
             record("ambience_scales (ulp)", float(ulps(got, ref).max()), 1.0)   # 0.5 rounding + float64 summation order
+    return np.concatenate(every)
 
 
 # ----------------------------------------------------------------------------- al_resample_poly
@@ -629,4 +637,6 @@ def run_encode(r, n_capsules, n_samples, fmt, shift=0, seed=16):
     d = dev(r, flat)
     r.lib.call("al_encode_frames", r.mem.ptr(d), n_capsules, n_samples, fmt, out.ptr, r.mem.stream())
     want = pcm16(scene.T) if fmt == _hip.FRAMES_PCM16 else scene.T
-    assert_bits_equal(out.get(), np.ascontiguousarray(want).reshape(-1), ("encode", n_capsules, n_samples, fmt))
+    got = out.get()
+    assert_bits_equal(got, np.ascontiguousarray(want).reshape(-1), ("encode", n_capsules, n_samples, fmt))
+    return got

@@ -213,6 +213,7 @@ def run_separate_forward_launches(renderer, log2_block, seed=0):
     separate = np.array(renderer.mem.download(batch.run(stages=stages).spatial))
     rows = np.concatenate([np.arange(int(ev["out_off"]), int(ev["out_off"]) + C * int(ev["len"])) for ev in pl.events])
     assert np.isfinite(merged[rows]).all() and np.array_equal(merged[rows], separate[rows])
+    return separate[rows]
 
 
 def run_random_batch(renderer, seed, log2_block=10):

@@ -3,13 +3,21 @@
 ``-DAL_SHAKE=<seed>`` (audiblelight_amd/csrc/al_common.h) makes every wave sleep a wave-, workgroup- and site-dependent number of cycles
 around every workgroup barrier, after every LDS-DMA issue and before every hand-counted ``s_waitcnt``: the inline-asm paths that
 the host-emulation build -- and with it ASan / UBSan and the differential fuzz -- cannot see.  tests/test_gpu_shake.py renders one
-batch per kernel family through each variant and asserts bit-identical output against the product library.
+batch per kernel family through each variant, tests/test_gpu_shake_standalone.py launches the barrier kernels outside the render
+stage (tests/shake_standalone.py: FX scans, statistics, encode) from each; both assert bit-identical output between the perturbed
+builds and run to run, and a derived bound against the product library.
 
 Variants (built in-tree under tests/shake_build/ by ``__graft_entry__.build()`` so that they travel to the GPU box like the product
 .so; about as long to compile as the product library, all of them side by side):
   s1      AL_SHAKE=1: pseudo-random skews
   s3w     AL_SHAKE=3 (wave 0 always last to move on) + AL_Q16_WAVES=1 + AL_SPLIT_WAVES=2 (other register budgets / occupancies)
-  revert  AL_SHAKE=3 + AL_TEST_REVERT_Q16_BARRIER: the round-4 LDS race of al_quad16.h re-introduced -- the variant the test must FAIL on
+  revert  AL_SHAKE=3 + three barriers compiled out, each in a kernel the others' families never launch -- the variant the tests
+          must FAIL on:
+            AL_TEST_REVERT_Q16_BARRIER    the round-4 LDS race of al_quad16.h re-introduced (test_gpu_shake.py)
+            AL_TEST_REVERT_SOS_BARRIER    sos_sweep (al_sos.h) without the barrier between filtering a tile and writing it back
+            AL_TEST_REVERT_DELAY_BARRIER  k_fx_delay (al_delayfx.h) without the second barrier of its scan loop
+          (test_gpu_shake_standalone.py).  The words left unsynchronised are sample / state values, never an index or a loop
+          bound, and every thread still takes the same number of barriers: wrong samples, no fault and no hang.
 """
 import os
 import subprocess
@@ -20,7 +28,7 @@ OUT = os.path.join(ROOT, "tests", "shake_build")
 VARIANTS = {
     "s1": ["-DAL_SHAKE=1"],
     "s3w": ["-DAL_SHAKE=3", "-DAL_Q16_WAVES=1", "-DAL_SPLIT_WAVES=2"],
-    "revert": ["-DAL_SHAKE=3", "-DAL_TEST_REVERT_Q16_BARRIER=1"],
+    "revert": ["-DAL_SHAKE=3", "-DAL_TEST_REVERT_Q16_BARRIER=1", "-DAL_TEST_REVERT_SOS_BARRIER=1", "-DAL_TEST_REVERT_DELAY_BARRIER=1"],
 }
 # further skews, built on demand only (profiles/tools/shake_diag.py s2 s4 s5 s6: a wider sweep than the test suite's two variants)
 EXTRA_VARIANTS = {

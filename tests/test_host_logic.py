@@ -513,6 +513,57 @@ def test_every_accumulate_instantiation_is_named_by_a_gpu_test():
     assert asserted <= have, sorted(asserted - have)
 
 
+def test_every_barrier_kernel_has_a_shake_family():
+    """Every __global__ kernel of the product library that executes a workgroup barrier is claimed by a schedule-perturbation
+    family: tests/shake_standalone.py BARRIER_KERNELS maps it to a row of tests/test_gpu_shake.py FAMILIES (render stage) or to a
+    standalone family.  The list comes from the BUILT code object, not from the sources: the gfx950 bundles are extracted with
+    `llvm-objdump --offloading` and disassembled, and a kernel any of whose instantiations holds an `s_barrier` is a barrier kernel
+    (every barrier helper -- block_reduce3, block_barrier, sos_sweep, sos_carry, the FFT passes -- is inlined; a barrier left in a
+    function of its own fails kernel_inventory).  A new barrier kernel, or a first barrier in an old one, fails here until a family
+    launches it.  The other way round: the kernels said to need no shaking have neither a barrier nor LDS."""
+    from tests import shake_standalone as ss
+    from tests.test_gpu_shake import FAMILIES as render_families
+
+    inv = ss.kernel_inventory()
+    assert len(inv) >= 50, sorted(inv)
+    barrier = {k for k, (with_barrier, _, _) in inv.items() if with_barrier}
+    unclaimed = barrier - set(ss.BARRIER_KERNELS)
+    assert not unclaimed, f"barrier kernels no shake family launches: {sorted(unclaimed)}"
+    stale = set(ss.BARRIER_KERNELS) - barrier
+    assert not stale, f"listed as barrier kernels, but the code object holds no barrier (or no such kernel): {sorted(stale)}"
+    families = set(render_families) | set(ss.FAMILIES)
+    for table in (ss.BARRIER_KERNELS, ss.ONE_WAVE_BARRIER_KERNELS):
+        assert set(table.values()) <= families, set(table.values()) - families
+    assert set(ss.FAMILIES) <= set(ss.BARRIER_KERNELS.values())          # no standalone family without a kernel to its name
+    for k in ss.ONE_WAVE_BARRIER_KERNELS:                                # one wave per workgroup: hipcc drops the instruction
+        assert k in inv and k not in barrier, k
+        assert re.search(r"__launch_bounds__\(64\)\s+void\s+%s\b" % k, open(os.path.join(ROOT, "audiblelight_amd", "csrc", "al_kernels.hip")).read())
+    for k in ss.NO_BARRIER_NO_LDS:
+        assert k in inv, f"{k}: no such kernel in the library"
+        assert inv[k][0] == 0 and inv[k][2] == 0, (k, inv[k])
+    # every kernel is in exactly one of the three lists, or has no barrier (LDS without a barrier: one wave, or tables only)
+    listed = set(ss.BARRIER_KERNELS) | set(ss.ONE_WAVE_BARRIER_KERNELS) | set(ss.NO_BARRIER_NO_LDS)
+    assert not (set(ss.BARRIER_KERNELS) & set(ss.NO_BARRIER_NO_LDS))
+    assert all(inv[k][0] == 0 for k in set(inv) - listed)
+
+
+def test_standalone_shake_rows_reach_the_launch_geometry_they_name():
+    """The (G, P, workgroups) of every k_fx_delay row, the block B of every k_fx_chorus_fb row and the tiles / live runs of the
+    k_fx_sos rows, as restated from the launchers in tests/shake_standalone.py: the rows that are there for a geometry have it."""
+    from tests import shake_standalone as ss
+
+    for n, D, _, geometry in ss.DELAY_ROWS:
+        assert ss.delay_geometry(n, D) == geometry, (n, D)
+    plans = {D: g for _, D, _, g in ss.DELAY_ROWS}
+    assert plans[1] == (1, 1024, 1) and plans[64] == (64, 16, 1) and plans[4801][2] == 76 and 4801 % 64 == 1
+    assert any(D >= n for n, D, _, _ in ss.DELAY_ROWS)
+    for n, fs, _, depth, centre, fb, _, _, block in ss.CHORUS_ROWS:
+        assert ss.chorus_block(fs, depth, centre) == block and n % block != 0
+    assert min(row[-1] for row in ss.CHORUS_ROWS) == 16 and sum(row[5] == 0.0 for row in ss.CHORUS_ROWS) == 1
+    assert {ss.sos_geometry(n) for n, *_ in ss.SOS_ROWS} == {(4, 782), (1, 65)}
+    assert {k for _, k, _, _ in ss.SOS_ROWS} == {1, 3, 16} and _hip.SOS_MAX_SECTIONS == 16
+
+
 # ----------------------------------------------------------------------------- the planner behind the C ABI (csrc/al_plan.cpp)
 def _random_specs(rng, sr):
     specs, col = [], 0
