@@ -23,8 +23,13 @@ FLAG_STATIC_MAC = 64
 FLAG_ONLY_STATIC = 128
 FLAG_NARROW_FFT = 4
 FLAG_QUAD_SPECTRA = 256
-# bits of al_batch.flags that only pick between equivalent code paths (narrow FFT, runs of blocks per workgroup)
-DEBUG_FLAG_MASK = FLAG_NARROW_FFT | (7 << 12) | (0xff << 16) | (0x7f << 24)   # bit 12: static accumulate, one k-tile per workgroup
+# A/B switches of the capsule-loop accumulate (AL_FLAG_MAC_* of the header): one k-tile per workgroup; the register kernel beyond
+# 24 blocks too; at most 12 partitions through the LDS-DMA kernel too
+FLAG_MAC_ONE_KTILE = 1 << 12
+FLAG_MAC_NO_LDS_RING = 1 << 13
+FLAG_MAC_LDS_DMA = 1 << 14
+# bits of al_batch.flags that only pick between equivalent code paths (narrow FFT, accumulate switches, runs of blocks per workgroup)
+DEBUG_FLAG_MASK = (FLAG_NARROW_FFT | FLAG_MAC_ONE_KTILE | FLAG_MAC_NO_LDS_RING | FLAG_MAC_LDS_DMA | (0xff << 16) | (0x7f << 24))
 
 # numpy mirrors of al_event / al_stream (the tables are built on the host and copied to HBM)
 EVENT_DTYPE = np.dtype([

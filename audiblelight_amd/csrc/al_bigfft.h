@@ -164,4 +164,82 @@ __global__ __launch_bounds__(256) void k_blue_post(const float2 *y, int64_t n, i
   x[(int64_t)blockIdx.y * n + m] = make_float2(v.x * inv, v.y * inv);
 }
 
+// ------------------------------------------------------------------ host side: planning and launch sequence
+struct BigPlan {
+  int64_t len;       // complex transform length (n/2 for even n, n for odd n)
+  bool bluestein;
+  int64_t L;         // power-of-two Bluestein length (0 if unused)
+};
+
+inline int64_t strip_small_factors(int64_t m) {
+  for (int f : {2, 3, 5, 7})
+    while (m % f == 0) m /= f;
+  return m;
+}
+
+inline BigPlan big_plan(int64_t n) {
+  BigPlan p;
+  p.len = (n & 1) ? n : n / 2;
+  p.bluestein = strip_small_factors(p.len) != 1;
+  p.L = 0;
+  if (p.bluestein) {
+    p.L = 1;
+    while (p.L < 2 * p.len - 1) p.L <<= 1;
+  }
+  return p;
+}
+
+// Stockham passes over `rows` series of `len` points; returns the buffer holding the result.
+inline float2 *big_fft(float2 *a, float2 *b, int rows, int64_t len, int dir, hipStream_t stream) {
+  int64_t ns = 1, rest = len;
+  float2 *in = a, *out = b;
+  while (rest > 1) {
+    int r = 0;
+    for (int cand : {4, 2, 3, 5, 7})
+      if (rest % cand == 0) { r = cand; break; }
+    const dim3 grid((unsigned)((len / r + 255) / 256), rows);
+    switch (r) {
+      case 2: hipLaunchKernelGGL((k_big_pass<2>), grid, dim3(256), 0, stream, in, out, len, ns, dir); break;
+      case 3: hipLaunchKernelGGL((k_big_pass<3>), grid, dim3(256), 0, stream, in, out, len, ns, dir); break;
+      case 4: hipLaunchKernelGGL((k_big_pass<4>), grid, dim3(256), 0, stream, in, out, len, ns, dir); break;
+      case 5: hipLaunchKernelGGL((k_big_pass<5>), grid, dim3(256), 0, stream, in, out, len, ns, dir); break;
+      default: hipLaunchKernelGGL((k_big_pass<7>), grid, dim3(256), 0, stream, in, out, len, ns, dir); break;
+    }
+    ns *= r;
+    rest /= r;
+    float2 *t = in; in = out; out = t;
+  }
+  return in;
+}
+
+// irfft of rows x (n/2+1) shaped draws; zr == nullptr: the draws come from the device generator under `seed`
+inline void noise_irfft(const float *zr, const float *zi, uint64_t seed, const float *shape, int32_t rows, int64_t n, float inv_sigma,
+                float *out, float *workspace, hipStream_t st) {
+  const BigPlan p = big_plan(n);
+  const int64_t per = p.bluestein ? p.L : p.len;
+  float2 *a = reinterpret_cast<float2 *>(workspace);
+  float2 *b = a + (int64_t)rows * per;
+  const dim3 g_len((unsigned)((p.len + 255) / 256), rows);
+  const float2 *z;
+  if (!p.bluestein) {
+    hipLaunchKernelGGL(k_noise_pack, g_len, dim3(256), 0, st, zr, zi, seed, shape, n, a);
+    z = big_fft(a, b, rows, p.len, +1, st);
+  } else {
+    float2 *kern = b + (int64_t)rows * per;           // 2 * L: chirp kernel and its ping-pong partner
+    float2 *x = kern + 2 * p.L;                        // rows * len: packed spectrum / transform result
+    const dim3 g_L((unsigned)((p.L + 255) / 256), rows), g_L1((unsigned)((p.L + 255) / 256), 1);
+    hipLaunchKernelGGL(k_noise_pack, g_len, dim3(256), 0, st, zr, zi, seed, shape, n, x);
+    hipLaunchKernelGGL(k_blue_kernel, g_L1, dim3(256), 0, st, p.len, p.L, +1, kern);
+    const float2 *kspec = big_fft(kern, kern + p.L, 1, p.L, -1, st);
+    hipLaunchKernelGGL(k_blue_pre, g_L, dim3(256), 0, st, (const float2 *)x, p.len, p.L, +1, a);
+    float2 *A = big_fft(a, b, rows, p.L, -1, st);
+    hipLaunchKernelGGL(k_blue_mul, g_L, dim3(256), 0, st, A, kspec, p.L);
+    float2 *other = (A == a) ? b : a;
+    const float2 *y = big_fft(A, other, rows, p.L, +1, st);
+    hipLaunchKernelGGL(k_blue_post, g_len, dim3(256), 0, st, y, p.len, p.L, +1, x);
+    z = x;
+  }
+  hipLaunchKernelGGL(k_noise_unpack, g_len, dim3(256), 0, st, z, n, inv_sigma / (float)p.len, out);
+}
+
 }  // namespace al

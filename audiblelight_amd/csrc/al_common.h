@@ -1,5 +1,6 @@
 // Pieces shared by the two translation units of the HIP extension (al_transforms.hip: FFT kernels, built
-// with -fno-slp-vectorize; al_kernels.hip: everything else + the C ABI, built with default vectorisation).
+// with -fno-slp-vectorize; al_kernels.hip: the C ABI over the per-domain kernel headers, built with default vectorisation).
+// What more than one of those headers needs belongs here; a kernel never does.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -157,6 +158,14 @@ __device__ __forceinline__ void pipeline_fence() {
 #if defined(__HIP_DEVICE_COMPILE__)
   __builtin_amdgcn_sched_barrier(0);
 #endif
+}
+
+// A float64 scalar as the float32 the kernels multiply samples by, kept FINITE.  The reference forms these scalars in float64 --
+// 1 / tiny = 4.5e307 for an all-zero IR or clip, 10^(dB/20) / tiny for a silent render -- and multiplies ZEROS by them: silence
+// stays silence.  As float32 they would be +-inf and inf * 0 = NaN, so they saturate at +-FLT_MAX (FLT_MAX * 0 = 0).
+__device__ __forceinline__ float finite_f32(double v) {
+  if (v != v) return (float)v;     // NaN stays NaN: non-finite INPUT must still fail the finite check (librosa.util.valid_audio)
+  return (float)fmin(fmax(v, -3.4028234663852886e38), 3.4028234663852886e38);
 }
 
 // ------------------------------------------------------------------ block-wide reductions

@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "al_bigfft.h"
 #include "al_fft.h"
 
 namespace al {
@@ -101,6 +102,38 @@ __global__ __launch_bounds__(256) void k_istft_ola(const float2 *__restrict__ fr
     if (off >= 0 && off < fft_size) acc += frames[(i * n_ch + c) * fft_size + off].x;
   }
   out[idx] = acc;
+}
+
+// ------------------------------------------------------------------ host side: launch helpers
+constexpr int64_t MAX_GRID_ROWS = 32768;  // series per launch group (grid.y limit is 65535)
+
+// Complex FFT of `rows` series of `len` points for ANY len (the reference's numpy rfft / irfft take any fft_size, synthesize.py:135,263):
+// Stockham passes where len factors into 2, 3, 5 and 7, Bluestein's chirp-z on a power-of-two length otherwise (the pieces of
+// al_bigfft.h the ambience synthesis uses).  `x` holds the input, `y` is a second rows x len buffer, `tmp` any_fft_tmp_floats(rows, len)
+// floats (none for smooth lengths).  Returns the buffer that holds the transform (x or y; always y on the Bluestein path).
+inline int64_t bluestein_length(int64_t len) {
+  int64_t L = 1;
+  while (L < 2 * len - 1) L <<= 1;
+  return L;
+}
+inline int64_t any_fft_tmp_floats(int64_t rows, int64_t len) {
+  if (strip_small_factors(len) == 1) return 0;
+  const int64_t L = bluestein_length(len);
+  return 2 * (2 * rows * L + 2 * L);   // two rows x L ping-pong buffers, the chirp kernel and its partner
+}
+inline const float2 *any_fft(float2 *x, float2 *y, float *tmp, int rows, int64_t len, int dir, hipStream_t st) {
+  if (strip_small_factors(len) == 1) return big_fft(x, y, rows, len, dir, st);
+  const int64_t L = bluestein_length(len);
+  float2 *a = reinterpret_cast<float2 *>(tmp), *b = a + (int64_t)rows * L, *kern = b + (int64_t)rows * L;
+  const dim3 g_len((unsigned)((len + 255) / 256), rows), g_L((unsigned)((L + 255) / 256), rows), g_L1((unsigned)((L + 255) / 256), 1);
+  hipLaunchKernelGGL(k_blue_kernel, g_L1, dim3(256), 0, st, len, L, dir, kern);
+  const float2 *kspec = big_fft(kern, kern + L, 1, L, -1, st);
+  hipLaunchKernelGGL(k_blue_pre, g_L, dim3(256), 0, st, (const float2 *)x, len, L, dir, a);
+  float2 *A = big_fft(a, b, rows, L, -1, st);
+  hipLaunchKernelGGL(k_blue_mul, g_L, dim3(256), 0, st, A, kspec, L);
+  const float2 *conv = big_fft(A, (A == a) ? b : a, rows, L, +1, st);
+  hipLaunchKernelGGL(k_blue_post, g_len, dim3(256), 0, st, conv, len, L, dir, y);
+  return y;
 }
 
 }  // namespace al

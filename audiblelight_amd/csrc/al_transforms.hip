@@ -1,7 +1,7 @@
 // FFT kernels of the synthesis path (IR partition spectra, signal block spectra, block synthesis).
 // Compiled WITHOUT SLP vectorisation: hipcc's v_pk_*_f32 packing of the butterfly arithmetic makes the in-LDS
-// transform 10-25 % slower on gfx950 (profiles/r01_fft_probe.txt), while the spectral MAC in al_kernels.hip
-// gains from it; hence two translation units.
+// transform 10-25 % slower on gfx950 (profiles/r01_fft_probe.txt), while the spectral MAC (al_mac.h, included by
+// al_kernels.hip, the C ABI over every other kernel header) gains from it; hence two translation units.
 #include <hip/hip_runtime.h>
 #include <math.h>
 

@@ -58,6 +58,13 @@ extern "C" {
                                     the layout flags for the plan's block size */
 #define AL_FLAG_NARROW_FFT 4 /* A/B switch: 16 complex values per thread at every block size (default: 32 from
                                B = 8192 up, see csrc/al_fft.h) */
+/* A/B switches of the capsule-loop accumulate (AL_FLAG_STATIC_MAC); the default of each is the faster path where both exist
+   (profiles/r02_mac.txt, profiles/r03_p24_ab.txt).  The result is the same to rounding; al_spectral_mac_variant reports the choice. */
+#define AL_FLAG_MAC_ONE_KTILE (1 << 12)   /* one k-tile of 12 blocks per workgroup (default: two from 13 blocks up) */
+#define AL_FLAG_MAC_NO_LDS_RING (1 << 13) /* clips of more than 24 blocks through the register kernel k_spectral_mac_static<12,P,2>
+                                             too (default there: the partition spectra staged through LDS, k_spectral_mac_static_lds) */
+#define AL_FLAG_MAC_LDS_DMA (1 << 14)     /* at most 12 partitions through the LDS-DMA kernel k_spectral_mac_static_glds too, from 13
+                                             blocks up (default: only 13..21 partitions go through it) */
 #define AL_FLAG_SYNTH_RUN(n) (((n) & 0xff) << 16) /* al_block_synthesis: n consecutive blocks per workgroup (0 = 1) */
 #define AL_FLAG_IR_RUN(n) (((n) & 0x7f) << 24)    /* al_ir_spectra: n consecutive partitions per workgroup (0 = 1; the B = 16384 quad-tile
                                                      kernels: 0 = chosen per batch, equal runs, csrc/al_quad16.h) */

@@ -5,11 +5,11 @@ import subprocess
 
 import numpy as np
 
+from audiblelight_amd import _build
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "_build", "libal_hostemu.so")
-CSRC = os.path.join(ROOT, "audiblelight_amd", "csrc")
-SRCS = [os.path.join(CSRC, "al_kernels.hip"), os.path.join(CSRC, "al_transforms.hip"), os.path.join(CSRC, "al_plan.cpp")]
+SRCS = _build.sources()       # the product library's units, compiled for the host
 
 
 def build(sanitize: bool = False) -> str:
@@ -23,9 +23,7 @@ def build(sanitize: bool = False) -> str:
 
 
 def _build_locked(sanitize: bool) -> str:
-    deps = SRCS + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
-        os.path.join(ROOT, "include", "audiblelight_hip.h"), os.path.join(HERE, "hip", "hip_runtime.h")]
-    if os.path.exists(LIB) and all(os.path.getmtime(LIB) > os.path.getmtime(d) for d in deps):
+    if not _build.stale(LIB, _build.dependencies() + [os.path.join(HERE, "hip", "hip_runtime.h")]):
         return LIB
     flags = ["-std=c++17", "-O2", "-g", "-fPIC", "-pthread"] + (["-DHOSTEMU_THREADS", "-fsanitize=address,undefined"] if sanitize else [])
     objs = [os.path.join(os.path.dirname(LIB), os.path.basename(src) + ".o") for src in SRCS]

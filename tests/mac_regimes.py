@@ -1,14 +1,15 @@
-"""Scenarios that pin every dispatch branch of al_spectral_mac (csrc/al_kernels.hip: pick_mac) against the float64
+"""Scenarios that pin every dispatch branch of al_spectral_mac (csrc/al_mac.h: plan_mac) against the float64
 oracle, EVERY row compared.  Shared by tests/test_hostemu_regimes.py (host emulation, small blocks) and
 tests/test_gpu_mac_regimes.py (gfx950 build, every block size incl. the cfg2 / cfg3 regimes).
 
 Reference semantics: audiblelight/synthesize.py:71-106 (static) and :184-310 (moving).
 """
 import ctypes as ct
+import os
 
 import numpy as np
 
-from audiblelight_amd import plan as planning
+from audiblelight_amd import _hip, plan as planning
 from oracle import synth_oracle as orc
 from tests.conftest import assert_parity, rel_rms
 
@@ -42,7 +43,7 @@ STATIC_LOOP_CASES += [   # hand-picked edges
     ("two_units_one_ktile", 3121404, 7.5, 13.2, 2, 2),         # P = 14, K = 8: the second half of the workgroup idles
     ("cfg5_shape_tile_kernel", 1121202, 23.44, 23.44, 3, 2),   # K = 24, P = 24: cfg5's tile counts (two full partition tiles)
 ]
-# k_spectral_mac_static_glds<12,P> for at most 12 partitions (AL_EXTRA_FLAGS bit 14: an A/B switch, the default there is the
+# k_spectral_mac_static_glds<12,P> for at most 12 partitions (AL_EXTRA_FLAGS = AL_FLAG_MAC_LDS_DMA: an A/B switch, the default there is the
 # register / register-staged kernel): P = 1..12, clips of 13..24 and of more than 24 blocks
 GLDS_CASES = [(f"glds_P{P}_{name}", 3120000 + 100 * P + 4, k_mult + 0.01 * P, P - 0.37, 2 + P % 2, 1 + (P % 3 == 0))
               for P in range(1, 13) for name, k_mult, digit in _CLIP_REGIMES[1:]]
@@ -90,6 +91,41 @@ def asserted_codes():
     return out
 
 
+# The descriptor fields plan_mac reads, swept on both sides of every threshold (tests/golden/make_mac_dispatch_sweep.py records
+# al_spectral_mac_variant over their product, tests/test_host_logic.py compares the library of the day with the recording):
+# max_blocks around 8 (tile shapes), 12 / 24 (one, two, more k-tiles) and 36, plus one long clip; extra_streams = n_streams - n_events
+SWEEP_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mac_dispatch_sweep.npz")
+SWEEP_AXES = (
+    ("log2_block", (10, 11, 12, 13, 14)),
+    ("n_partitions", tuple(range(1, 27))),
+    ("max_blocks", (7, 8, 9, 11, 12, 13, 23, 24, 25, 35, 36, 37, 60)),
+    ("n_capsules", (1, 2, 32)),
+    ("n_events", (1, 64)),
+    ("extra_streams", (0, 3)),
+    ("hspec_zero_block", (-1, 0)),
+    ("flags", tuple(sum(bit for i, bit in enumerate((_hip.FLAG_STATIC_MAC, _hip.FLAG_ONLY_STATIC, _hip.FLAG_MAC_ONE_KTILE,
+                                                     _hip.FLAG_MAC_NO_LDS_RING, _hip.FLAG_MAC_LDS_DMA)) if n >> i & 1) for n in range(32))),
+)
+
+
+def dispatch_sweep(lib):
+    """(static_code, moving_code) of al_spectral_mac_variant over the product of SWEEP_AXES, as two int32 arrays shaped by the axes."""
+    import itertools
+
+    shape = tuple(len(values) for _, values in SWEEP_AXES)
+    static, moving = np.empty(shape, np.int32), np.empty(shape, np.int32)
+    desc, s, m = _hip.AlBatch(hop=128), ct.c_int32(), ct.c_int32()
+    variant, args = lib._al_spectral_mac_variant, (ct.byref(desc), ct.byref(s), ct.byref(m))
+    for i, point in enumerate(itertools.product(*(values for _, values in SWEEP_AXES))):
+        (desc.log2_block, desc.n_partitions, desc.max_blocks, desc.n_capsules, desc.n_events, extra, desc.hspec_zero_block,
+         desc.flags) = point
+        desc.n_emitters, desc.n_streams = desc.n_events, desc.n_events + extra
+        desc.ir_len = desc.n_partitions << desc.log2_block
+        assert variant(*args) == 0, (point, lib.last_error())
+        static.flat[i], moving.flat[i] = s.value, m.value
+    return static, moving
+
+
 def mac_codes(renderer, batch, chunk=0):
     s, m = ct.c_int32(-1), ct.c_int32(-1)
     renderer.lib.call("al_spectral_mac_variant", ct.byref(batch.descs[chunk]), ct.byref(s), ct.byref(m))
@@ -106,8 +142,6 @@ def check_event_rows(res, i, want, tol=TOL):
 
 
 def is_split(batch, chunk=0):
-    from audiblelight_amd import _hip
-
     return bool(batch.descs[chunk].flags & _hip.FLAG_SPLIT_SPECTRA)
 
 
@@ -136,7 +170,6 @@ def run_static_case(renderer, log2_block, code, k_mult, p_mult, C=3, E=2, seed=0
     if expect_split is not None:
         assert is_split(batch) == expect_split
     if expect_quad is not None:
-        from audiblelight_amd import _hip
         assert bool(batch.descs[0].flags & _hip.FLAG_QUAD_SPECTRA) == expect_quad
     res = batch.run()
     res.check_finite()

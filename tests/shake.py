@@ -20,10 +20,11 @@ Variants (built in-tree under tests/shake_build/ by ``__graft_entry__.build()`` 
           bound, and every thread still takes the same number of barriers: wrong samples, no fault and no hang.
 """
 import os
-import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "audiblelight_amd", "csrc")
+from audiblelight_amd import _build
+
+ROOT = _build.ROOT
 OUT = os.path.join(ROOT, "tests", "shake_build")
 VARIANTS = {
     "s1": ["-DAL_SHAKE=1"],
@@ -43,37 +44,22 @@ def library_path(name: str) -> str:
     return os.path.join(OUT, f"libaudiblelight_hip_{name}.so")
 
 
-def _stale(target, deps):
-    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in deps)
-
-
 def build(names=None) -> dict:
-    """Compile the named variants (default: all) with hipcc for gfx950; returns {name: path}.  Needs no GPU."""
+    """Compile the named variants (default: all) with hipcc for gfx950; returns {name: path}.  Needs no GPU.  Every variant is the
+    product recipe (audiblelight_amd/_build.py) plus its defines, all of them side by side over one planner object."""
     names = list(VARIANTS) if names is None else list(names)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip", ".cpp"))]
-    deps += [os.path.join(ROOT, "include", "audiblelight_hip.h"), os.path.abspath(__file__)]
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    os.makedirs(OUT, exist_ok=True)
-    jobs, todo = [], []
-    plan_obj = os.path.join(OUT, "al_plan.o")
-    for name in names:
-        if not _stale(library_path(name), deps):
-            continue
-        objs = []
-        for src, extra in (("al_kernels.hip", []), ("al_transforms.hip", ["-fno-slp-vectorize"])):
-            obj = os.path.join(OUT, f"{os.path.splitext(src)[0]}_{name}.o")
-            jobs.append(subprocess.Popen([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c"] + extra + {**VARIANTS, **EXTRA_VARIANTS}[name]
-                                         + [os.path.join(CSRC, src), "-o", obj]))
-            objs.append(obj)
-        todo.append((name, objs))
+    deps = _build.dependencies() + [os.path.abspath(__file__), os.path.abspath(_build.__file__)]
+    todo = [name for name in names if _build.stale(library_path(name), deps)]
     if todo:
-        jobs.append(subprocess.Popen(["g++", "-O2", "-std=c++17", "-fPIC", "-Wall", "-c", os.path.join(CSRC, "al_plan.cpp"), "-o", plan_obj]))
-        if any(j.wait() != 0 for j in jobs):
-            raise RuntimeError("hipcc failed on a schedule-perturbed variant")
-        for name, objs in todo:
-            subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + [plan_obj, "-o", library_path(name)])
-            for o in objs:
-                os.remove(o)
+        os.makedirs(OUT, exist_ok=True)
+        plan_obj = os.path.join(OUT, "al_plan.o")
+        if _build.compile_planner(plan_obj).wait() != 0:
+            raise RuntimeError("g++ failed on the planner")
+        defines = {**VARIANTS, **EXTRA_VARIANTS}
+        with ThreadPoolExecutor(len(todo)) as pool:
+            for objs in pool.map(lambda name: _build.compile_library(library_path(name), defines[name], "_" + name, plan_obj), todo):
+                for o in objs:
+                    os.remove(o)
     return {name: library_path(name) for name in names}
 
 

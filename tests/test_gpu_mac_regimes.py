@@ -1,4 +1,4 @@
-"""Every dispatch branch of al_spectral_mac (csrc/al_kernels.hip: pick_mac) on the gfx950 build, through the C ABI,
+"""Every dispatch branch of al_spectral_mac (csrc/al_mac.h: plan_mac) on the gfx950 build, through the C ABI,
 EVERY row against the float64 oracle; each test asserts which instantiation ran (al_spectral_mac_variant).
 
 Covers what the headline bench executes: k_spectral_mac<12,12,2,KSPLIT> at K = 24 / P = 12 (cfg2) and
@@ -10,6 +10,7 @@ from tests.conftest import set_switch
 
 from tests.conftest import set_switch
 
+from audiblelight_amd import _hip
 from tests import mac_regimes as mr
 
 pytestmark = pytest.mark.gpu
@@ -50,7 +51,7 @@ def test_static_capsule_loop_glds_kernel(gpu, monkeypatch, log2_block, name, cod
     where it is an A/B switch (13..24 partitions take it by default: test_static_capsule_loop_kernel): every partition count
     1..12, second k-tile full / ragged / idle, one and several workgroups per (event, bin tile); every row against the oracle."""
     set_switch(monkeypatch, "AL_STATIC_MAC", None)
-    set_switch(monkeypatch, "AL_EXTRA_FLAGS", str(1 << 14))
+    set_switch(monkeypatch, "AL_EXTRA_FLAGS", str(_hip.FLAG_MAC_LDS_DMA))
     mr.run_static_case(gpu, log2_block, code, k_mult, p_mult, C=C, E=E)
 
 

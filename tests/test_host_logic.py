@@ -513,6 +513,24 @@ def test_every_accumulate_instantiation_is_named_by_a_gpu_test():
     assert asserted <= have, sorted(asserted - have)
 
 
+def test_accumulate_dispatch_reproduces_the_recorded_sweep():
+    """al_spectral_mac_variant over every descriptor field plan_mac reads (tests/mac_regimes.py::SWEEP_AXES: both sides of every
+    threshold, every combination of the static / only-static flags and the three A/B switches) against the recording made before the
+    dispatch became one table (tests/golden/make_mac_dispatch_sweep.py): every (static_code, moving_code) pair, exactly."""
+    from tests import hostemu, mac_regimes as mr
+
+    want = np.load(mr.SWEEP_FIXTURE)
+    for name, values in mr.SWEEP_AXES:                       # the recording was made over these very axes
+        assert np.array_equal(want[name], values), name
+    static, moving = mr.dispatch_sweep(_hip.Library(hostemu.build()))
+    assert static.shape == want["static_code"].shape and static.size == 1297920
+    assert np.array_equal(static, want["static_code"]), np.argwhere(static != want["static_code"])[:5]
+    assert np.array_equal(moving, want["moving_code"]), np.argwhere(moving != want["moving_code"])[:5]
+    for code in (1121202, 240401, 81201, 80401, 612, 624, 0, *(3120000 + 100 * p + d for p in range(1, 13) for d in (1, 2, 3, 4)),
+                 *(3120000 + 100 * p + 3 for p in range(13, 17)), *(3120000 + 100 * p + 4 for p in range(13, 22))):
+        assert code in static or code in moving, f"the sweep never reaches {code}"
+
+
 def test_every_barrier_kernel_has_a_shake_family():
     """Every __global__ kernel of the product library that executes a workgroup barrier is claimed by a schedule-perturbation
     family: tests/shake_standalone.py BARRIER_KERNELS maps it to a row of tests/test_gpu_shake.py FAMILIES (render stage) or to a
@@ -535,9 +553,11 @@ def test_every_barrier_kernel_has_a_shake_family():
     for table in (ss.BARRIER_KERNELS, ss.ONE_WAVE_BARRIER_KERNELS):
         assert set(table.values()) <= families, set(table.values()) - families
     assert set(ss.FAMILIES) <= set(ss.BARRIER_KERNELS.values())          # no standalone family without a kernel to its name
+    csrc = os.path.join(ROOT, "audiblelight_amd", "csrc")
+    csrc_text = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".h", ".hip")))
     for k in ss.ONE_WAVE_BARRIER_KERNELS:                                # one wave per workgroup: hipcc drops the instruction
         assert k in inv and k not in barrier, k
-        assert re.search(r"__launch_bounds__\(64\)\s+void\s+%s\b" % k, open(os.path.join(ROOT, "audiblelight_amd", "csrc", "al_kernels.hip")).read())
+        assert re.search(r"__launch_bounds__\(64\)\s+void\s+%s\b" % k, csrc_text)
     for k in ss.NO_BARRIER_NO_LDS:
         assert k in inv, f"{k}: no such kernel in the library"
         assert inv[k][0] == 0 and inv[k][2] == 0, (k, inv[k])
@@ -806,8 +826,9 @@ def test_source_hash_ignores_comments_but_not_code(tmp_path, monkeypatch):
     shutil.copytree(os.path.join(root, "audiblelight_amd", "csrc"), copy, ignore=shutil.ignore_patterns("*.o", "*.so"))
     monkeypatch.setattr(bench, "ROOT", str(tmp_path))
     assert bench.source_hash() == here
-    src = copy / "al_kernels.hip"
+    src = copy / "al_levels.h"
     text = src.read_text()
+    assert "__launch_bounds__(64)" in text
     src.write_text("// a new first line\n" + text.replace("\n", "   \n", 40).replace("{\n", "{  /* why */\n", 5))
     assert bench.source_hash() == here, "a comment / white-space edit changed the hash"
     src.write_text(text.replace("__launch_bounds__(64)", "__launch_bounds__(128)", 1))

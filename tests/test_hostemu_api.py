@@ -517,7 +517,7 @@ def test_degenerate_events_render_like_the_reference():
     """Silence stays silence (G15: the reference's own renders of degenerate events): snr = 0, a negative snr, an all-zero IR, an
     all-zero clip, a moving event with one all-zero IR among its emitters, the dry render of an all-zero clip.  The reference forms
     1 / tiny and 10^(dB/20) / tiny in float64 and multiplies zeros by them; the device keeps every such scalar finite in float32
-    (csrc/al_kernels.hip: finite_f32, emitter_gain_of).  Then the same events in ONE scene with a silent ambience and a silent clip
+    (csrc/al_common.h: finite_f32, csrc/al_levels.h: emitter_gain_of).  Then the same events in ONE scene with a silent ambience and a silent clip
     under a +12 dB gain: the mix is finite and equals the oracle's."""
     import os
 

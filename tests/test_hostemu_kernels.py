@@ -1,4 +1,4 @@
-"""Run the real kernel SOURCE (audiblelight_amd/csrc/al_kernels.hip) compiled for the host by the
+"""Run the real kernel SOURCE (audiblelight_amd/csrc/al_kernels.hip and the kernel headers it includes) compiled for the host by the
 test-only emulation layer in tests/hostemu, and compare with the oracle / reference goldens.
 
 This checks the index arithmetic of the HIP code (Stockham passes, real-FFT packing, overlap-save

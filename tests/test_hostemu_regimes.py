@@ -43,7 +43,7 @@ def test_emu_every_capsule_loop_instantiation(emu, monkeypatch, name, code, k_mu
 def test_emu_glds_switch_and_no_zero_block(emu, monkeypatch, name, code, k_mult, p_mult, C, E):
     set_switch(monkeypatch, "AL_STATIC_MAC", None)
     if code % 10 == 4:
-        set_switch(monkeypatch, "AL_EXTRA_FLAGS", str(1 << 14))
+        set_switch(monkeypatch, "AL_EXTRA_FLAGS", str(_hip.FLAG_MAC_LDS_DMA))
         mr.run_static_case(emu, 10, code, k_mult, p_mult, C=min(C, 2), E=1)
     else:
         set_switch(monkeypatch, "AL_EXTRA_FLAGS", None)
@@ -54,7 +54,7 @@ def test_emu_static_glds_kernel(emu, monkeypatch):
     """k_spectral_mac_static_glds under emulation (the LDS-DMA pieces as plain copies: ring indexing, piece -> row mapping,
     the repeated last piece where PT * 4 is not a multiple of 8, ragged second k-tile)."""
     set_switch(monkeypatch, "AL_STATIC_MAC", None)
-    set_switch(monkeypatch, "AL_EXTRA_FLAGS", str(1 << 14))
+    set_switch(monkeypatch, "AL_EXTRA_FLAGS", str(_hip.FLAG_MAC_LDS_DMA))
     mr.run_static_case(emu, 10, 3120904, 17.3, 8.6, C=3, E=1)
     mr.run_static_case(emu, 10, 3120304, 26.3, 2.5, C=2, E=1)
 
