@@ -4,7 +4,8 @@ Shared by tests/test_hostemu_kernel_edges.py (host emulation) and tests/test_gpu
 
 Every output is written into a guarded buffer: G elements of a sentinel bit pattern before and after it, checked after the
 call, so a store past either end is seen.  Where the ABI does not demand 16-byte alignment the interior pointer is also run one
-element off alignment.
+element off alignment.  The workspaces of al_noise_irfft, al_stft and al_istft_ola are guarded buffers too, of exactly the
+number of floats the matching al_*_workspace_floats call returns: a formula that comes up short is a guard violation.
 
 Bounds (eps = float32 machine epsilon 2^-23, u = eps / 2 the unit roundoff):
   data movement (reverse, invert, clip, bitcrush, wrap copy, frame shuffle, packs, encode)   bit-exact
@@ -37,15 +38,15 @@ EDGE_N = (2, 255, 256, 257, 1023, 1024, 1025)
 
 # ----------------------------------------------------------------------------- guarded buffers
 class Guarded:
-    """A device buffer of n elements of `dtype` with G sentinel elements on each side; ``shift`` moves the interior that many
-    elements off the (at least 16-byte aligned) position it would have.  ``init`` fills the interior."""
+    """A device buffer of n elements of `dtype` with ``guard`` (G unless given) sentinel elements on each side; ``shift`` moves
+    the interior that many elements off the (at least 16-byte aligned) position it would have.  ``init`` fills the interior."""
 
-    def __init__(self, r, n, dtype=np.float32, shift=0, init=None):
+    def __init__(self, r, n, dtype=np.float32, shift=0, init=None, guard=G):
         self.r, self.n, self.dtype = r, int(n), np.dtype(dtype)
         item = self.dtype.itemsize
-        self.lo = (G + shift) * item
+        self.lo = (guard + shift) * item
         self.hi = self.lo + self.n * item
-        total = (self.hi + G * item + 3) // 4 * 4
+        total = (self.hi + guard * item + 3) // 4 * 4
         host = np.resize(SENTINEL, total)
         if init is not None:
             host[self.lo:self.hi] = np.ascontiguousarray(init, dtype=self.dtype).reshape(-1).view(np.uint8)
@@ -61,6 +62,15 @@ class Guarded:
         bad = np.flatnonzero(np.concatenate([raw[:self.lo] != pattern[:self.lo], raw[self.hi:] != pattern[self.hi:]]))
         assert bad.size == 0, f"{bad.size} guard bytes overwritten (first at byte {int(bad[0])} of the guards)"
         return raw[self.lo:self.hi].view(self.dtype).copy()
+
+
+def workspace(r, n_floats):
+    """A transform workspace of exactly n_floats floats (what an al_*_workspace_floats call returned), its guard bands as long
+    as the workspace itself (at most 2^20 floats): a formula that comes up a whole buffer short then still writes into the band,
+    where it is seen, and not into whatever lies behind.  The interior starts as the sentinel NaN, like uninitialised memory."""
+    n_floats = int(n_floats)
+    assert n_floats > 0
+    return Guarded(r, n_floats, guard=max(G, (min(n_floats, 1 << 20) + 3) // 4 * 4))
 
 
 def dev(r, arr):
@@ -493,6 +503,69 @@ def run_pack_ragged(r, lens, pitch, shift=0, seed=12):
 
 
 # ----------------------------------------------------------------------------- al_noise_irfft: the any-size inverse real FFT
+# Lengths n of the inverse real transform, chosen by the COMPLEX length the Stockham passes run (len = n / 2 for even n, n for
+# odd n).  k_big_pass<R> gives one thread to each of the len / R butterflies of a pass, 256 threads to a workgroup, and
+# big_fft takes the radices in the order 4, 2, 3, 5, 7 (ns = the product of the radices already done).  Each row says what it
+# is there for; test_*_kernel_edges.py run them all with rows = 2 (blockIdx.y) and one of them with rows = 3.
+NOISE_STOCKHAM_N = [
+    # the last workgroup of an odd-radix pass exactly full: len / R == 256
+    (1536, "len 768 = 4^4 3: the radix-3 pass is one full workgroup (256 butterflies)"),
+    (2560, "len 1280 = 4^4 5: the radix-5 pass is one full workgroup"),
+    (3584, "len 1792 = 4^4 7: the radix-7 pass is one full workgroup"),
+    # ... and a little over: a second, partly filled workgroup
+    (1920, "len 960 = 4^3 3 5: radix 3 runs 320 butterflies (64 live lanes in workgroup 1), radix 5 192"),
+    (2880, "len 1440 = 4^2 2 3^2 5: radix 5 runs 288 (32 live lanes in workgroup 1), both radix-3 passes 480"),
+    (3780, "len 1890 = 2 3^3 5 7: radix 7 runs 270 (14 live lanes in workgroup 1) at ns = 270"),
+    # pure prime powers: the generic butterfly with its (r q) % R twiddle in every pass, ns growing to len / R; odd n = len
+    # takes the Hermitian-extension branch of k_noise_pack / k_noise_unpack over several workgroups
+    (2187, "len 3^7, odd n: seven radix-3 passes of 729 butterflies (3 workgroups), ns 1 .. 729"),
+    (3125, "len 5^5, odd n: five radix-5 passes of 625 butterflies (3 workgroups), ns 1 .. 625"),
+    (2401, "len 7^4, odd n: four radix-7 passes of 343 butterflies (2 workgroups), ns 1 .. 343"),
+    (16807, "len 7^5, odd n: five radix-7 passes of 2401 butterflies (10 workgroups), ns 1 .. 2401"),
+    # the same len from an even n: the half-length packing (E + iO) with an odd len
+    (4374, "len 3^7 from even n: half-length packing with an odd len"),
+    (4802, "len 7^4 from even n: half-length packing with an odd len"),
+    # all five radices in one transform, in the dispatch order 4, 2, 3, 3, 5, 7, the radix-7 pass in two workgroups
+    (5040, "len 2520 = 2^3 3^2 5 7: passes 4, 2, 3, 3, 5, 7; radix 7 runs 360 butterflies (2 workgroups) at ns = 360"),
+    (11025, "len 11025 = 3^2 5^2 7^2, odd n: an odd mix, passes 3, 3, 5, 5, 7, 7; radix 7 at ns = 225 and 1575 (7 workgroups)"),
+    (22050, "len 11025 from even n"),
+]
+NOISE_STOCKHAM_ROWS3 = 5040       # the rows = 3 case: every radix, the radix-7 pass multi-block
+# a large ns under each odd radix (one odd pass after nine radix-4 or eight radix-4 and one radix-2 pass) and the two long prime
+# powers: emulated workgroups are too slow for these
+NOISE_STOCKHAM_N_GPU = [
+    (2 * 3 * 2 ** 18, "len 3 2^18: the radix-3 pass at ns = 2^18 (1024 workgroups)"),
+    (2 * 5 * 2 ** 17, "len 5 2^17: the radix-5 pass at ns = 2^17 (512 workgroups)"),
+    (2 * 7 * 2 ** 17, "len 7 2^17: the radix-7 pass at ns = 2^17 (512 workgroups)"),
+    (2 * 5 ** 8, "len 5^8 = 390625 from even n: eight radix-5 passes of 78125 butterflies, ns 1 .. 78125"),
+    (7 ** 7, "len 7^7 = 823543, odd n: seven radix-7 passes of 117649 butterflies, ns 1 .. 117649"),
+]
+
+# (fft, win, hop) of al_stft and al_istft_ola beyond the powers of two and the Bluestein sizes of the parametrisations
+STFT_GEOMETRIES = [
+    # smooth, not a power of two: Stockham passes of radix 3 / 5 / 7 behind the STFT entry points
+    (384, 256, 64),      # 2^7 3
+    (480, 240, 120),     # 2^5 3 5
+    (1000, 500, 125),    # 2^3 5^3
+    (210, 105, 35),      # 2 3 5 7, odd window and hop
+    (105, 64, 16),       # odd smooth: 3 5 7
+    (343, 128, 32),      # odd prime power 7^3
+    (2520, 512, 128),    # every radix; the radix-7 pass (360 butterflies) in two workgroups per series
+    # crop: fft < win keeps the first fft samples of each windowed frame (rfft(frames, n=fft)); the inverse overlap-adds
+    # fft-sample frames and still slices from win
+    (48, 64, 16),
+    # win == hop: no left padding, frames do not overlap in the forward direction
+    (32, 16, 16),
+    # tiny: a length-1 transform runs no pass at all and returns its input buffer; win = 1 makes the sin^2 window zero
+    (1, 1, 1), (2, 2, 1), (3, 2, 1),
+]
+# more series than one launch group (MAX_GRID_ROWS = 32768) holds: a smooth size and a Bluestein size (its scratch and
+# chirp spectrum are made again by the second group)
+GROUP_FFTS = (6, 11)
+GROUP_STFT = dict(rows=2, n=40000, win=4, hop=2)        # 20 001 frames, 40 002 series: group 1 starts at frame 12 767 of row 1
+GROUP_ISTFT = dict(n_frames=11000, n_ch=3, win=4, hop=2)  # 33 000 series: series 32 768 is channel 2 of frame 10 922
+
+
 def fft_bound(length):
     """(log2 of the transform length the kernels run, Bluestein?) for a complex transform of `length` points: Stockham
     passes where it factors into 2 / 3 / 5 / 7, else Bluestein on L = the next power of two >= 2 length - 1."""
@@ -515,19 +588,25 @@ def run_noise_irfft(r, rows, n, seed=13):
     give |err|_2 <= c log2(len) u |y|_2.  Against the peak of a noise-like output (peak ~ 4 rms, errors spread evenly) that is a
     max-abs error of about log2(len) u; the real-packing step adds one level.  Bluestein runs three FFTs of length L = 2^k
     >= 2 len - 1 and two chirp multiplications: about 3 log2(L) u.  Asserted: 2 (log2 len + 1) eps (Stockham), and
-    3 (log2 L + 1) eps (Bluestein), relative to max|ref|."""
+    3 (log2 L + 1) eps (Bluestein), relative to max|ref|.
+
+    The constants were argued for radix-2 / 4 passes.  A length made of 5s or 7s runs fewer passes than log2(len), each output
+    of a pass taking R - 1 complex multiply-adds; measured, those lengths sit as far below the bound as the powers of two do
+    (profiles/r10_anyfft_edges.txt: 7^5 0.08, 5^5 0.10, 3^2 5^2 7^2 0.10 of the 2 in the host emulation), so log2(len)
+    stays the count."""
     rng = np.random.default_rng(seed)
     bins = n // 2 + 1
     zr = rng.standard_normal((rows, bins)).astype(np.float32)
     zi = rng.standard_normal((rows, bins)).astype(np.float32)
     shape = (1.0 / np.sqrt(1.0 + np.arange(bins))).astype(np.float32)     # a 1/f-like shaping
     inv_sigma = float(np.float32(0.37))
-    work = r.mem.empty(r.lib.call("al_noise_workspace_floats", rows, n))
+    work = workspace(r, r.lib.call("al_noise_workspace_floats", rows, n))
     out = Guarded(r, rows * n)
     d_zr, d_zi, d_s = dev(r, zr.reshape(-1)), dev(r, zi.reshape(-1)), dev(r, shape)
     r.lib.call("al_noise_irfft", r.mem.ptr(d_zr), r.mem.ptr(d_zi), r.mem.ptr(d_s), rows, n, ct.c_float(inv_sigma), out.ptr,
-               r.mem.ptr(work), r.mem.stream())
+               work.ptr, r.mem.stream())
     got = out.get().reshape(rows, n)
+    work.get()
     S = shape.astype(np.float64) * (zr.astype(np.float64) + 1j * zi.astype(np.float64))
     S[:, 0] = S[:, 0].real * np.sqrt(2)
     if n % 2 == 0:
@@ -543,17 +622,23 @@ def run_noise_irfft(r, rows, n, seed=13):
 
 
 # ----------------------------------------------------------------------------- al_stft / al_istft_ola
-def run_stft(r, rows, n, fft, win, hop, seed=14):
+def run_stft(r, rows, n, fft, win, hop, seed=14, last_written=False):
     """sin^2-windowed rFFT frames (oracle.stft_frames, scipy float64).  Same FFT bound as the noise path, relative to the
-    spectrum's peak; every output guarded (the spectrum is written by k_stft_take_half, one row per series)."""
+    spectrum's peak; every output guarded (the spectrum is written by k_stft_take_half, one row per series), every element
+    compared.  fft < win crops each windowed frame to its first fft samples, as the reference's rfft(frames, n=fft) does.
+    ``last_written``: also assert that the last series is not silent (an unwritten last launch group must not pass)."""
     x = np.stack([signal(n, seed + i, special=False) for i in range(rows)]).astype(np.float32)
     n_frames = orc.frame_count(n, hop)
     nf = fft // 2 + 1
-    work = r.mem.empty(r.lib.call("al_stft_workspace_floats", rows * n_frames, fft))
+    work = workspace(r, r.lib.call("al_stft_workspace_floats", rows * n_frames, fft))
     out = Guarded(r, rows * n_frames * nf * 2)
     d = dev(r, x.reshape(-1))
-    r.lib.call("al_stft", r.mem.ptr(d), rows, n, fft, win, hop, out.ptr, r.mem.ptr(work), r.mem.stream())
+    r.lib.call("al_stft", r.mem.ptr(d), rows, n, fft, win, hop, out.ptr, work.ptr, r.mem.stream())
     got = out.get().view(np.complex64).reshape(rows, n_frames, nf)
+    work.get()
+    if last_written:
+        assert np.abs(got[-1]).max() > 0, "the last row of the spectrum is silent"
+        assert np.abs(got[-1, -1]).max() > 0, "the last series of the last launch group is silent"
     lg, blue = fft_bound(fft)
     bound = 3.0 if blue else 2.0            # in units of (log2 + 1) eps, as for the noise path
     for row in range(rows):
@@ -590,19 +675,25 @@ def run_tv_stft_mac(r, n_frames, n_frames_ir, n_freq, n_ch, n_irs, seed=18):
     record("tv_stft_mac (err / ((n_irs + K + 2) eps sum|S W H|))", float(np.max(np.abs(got - ref) / np.maximum(bound, TINY32))), 1.0)
 
 
-def run_istft(r, n_frames, n_ch, fft, win, hop, seed=15):
+def run_istft(r, n_frames, n_ch, fft, win, hop, seed=15, last_written=False):
     """irfft(n=fft, norm="forward") of every (frame, channel), overlap-add at i*hop, slice [win, n_frames*hop): the
     reference restated with numpy's float64 irfft.  Each output sample sums ceil(fft/hop) frames: FFT bound + that many
-    additions, relative to the output's peak."""
+    additions, relative to the output's peak.  The overlap-add buffer here is long enough for any fft (the reference's own
+    holds (n_frames + 1) hop + win samples, so it raises for fft > 2 hop + win; the slice it returns ends before that tail
+    and is the same).  ``last_written``: also assert that the last output sample, which only frames of the last launch group
+    reach, is not silent."""
     nf = fft // 2 + 1
     rng = np.random.default_rng(seed)
     spec = (rng.standard_normal((n_frames, nf, n_ch)) + 1j * rng.standard_normal((n_frames, nf, n_ch))).astype(np.complex64)
-    work = r.mem.empty(r.lib.call("al_istft_workspace_floats", n_frames, n_ch, fft))
+    work = workspace(r, r.lib.call("al_istft_workspace_floats", n_frames, n_ch, fft))
     n_out = n_frames * hop - win
     out = Guarded(r, n_out * n_ch)
     d = dev(r, spec.view(np.float32).reshape(-1))
-    r.lib.call("al_istft_ola", r.mem.ptr(d), n_frames, nf, n_ch, fft, win, hop, out.ptr, r.mem.ptr(work), r.mem.stream())
+    r.lib.call("al_istft_ola", r.mem.ptr(d), n_frames, nf, n_ch, fft, win, hop, out.ptr, work.ptr, r.mem.stream())
     got = out.get().reshape(n_out, n_ch)
+    work.get()
+    if last_written:
+        assert np.abs(got[-1]).max() > 0, "the last output sample (fed by the last launch group alone) is silent"
     frames = sp_fft.irfft(spec.astype(np.complex128), n=fft, axis=1, norm="forward")     # (F, fft, ch)
     ola = np.zeros((n_frames * hop + fft, n_ch))
     for i in range(n_frames):

@@ -1,6 +1,23 @@
 """tests/kernel_edges.py on the real MI355X (gfx950 build), at full size: the device math library (tanhf, exp2f, log10f,
 sinpif), the 60 s clip lengths on every family, the any-size FFT at 2 880 000 / 2 880 001 points.  The host emulation runs the
-same scenarios in tests/test_hostemu_kernel_edges.py."""
+same scenarios in tests/test_hostemu_kernel_edges.py.
+
+The any-length transform (al_noise_irfft, al_stft, al_istft_ola), by what each length is there for:
+  NOISE_N 1..64                     every small length, each radix alone and mixed: every pass a single, partly filled workgroup
+  256, 1024                         powers of two (len 128, 512: one workgroup)
+  255 .. 2^20 +- 1, 2 880 001       a prime factor above 7: Bluestein, whose power-of-two L is where the radix-4 / 2 passes run
+                                    in many workgroups
+  2 880 000                         len 1 440 000 = 2^8 3^2 5^4, the 60 s ambience
+  ke.NOISE_STOCKHAM_N               the radix-3 / 5 / 7 passes past one workgroup: last workgroup exactly full and just over
+                                    full per radix, pure prime powers up to 7^5 with ns growing, all five radices in one
+                                    transform, both parities of n for one len (each row's reason stands beside it).  With these
+                                    NOISE_N covers every radix in a workgroup other than the first.
+  ke.NOISE_STOCKHAM_N_GPU           a large ns under each odd radix (len 3 2^18, 5 2^17, 7 2^17) and the long prime powers 5^8, 7^7
+  STFT / ISTFT sizes                512, 64 (powers of two), 17, 34, 257, 514, 22 (Bluestein) and ke.STFT_GEOMETRIES: smooth
+                                    sizes that are no power of two, one of them multi-block, fft < win, win == hop, fft 1 / 2 / 3
+  two launch groups                 more than 32 768 series in al_stft (boundary inside a row) and al_istft_ola (boundary
+                                    between the channels of a frame) at a smooth and a Bluestein size, every element compared
+Every workspace of the three is a guarded buffer of exactly al_*_workspace_floats floats."""
 import pytest
 
 from audiblelight_amd import _hip
@@ -121,6 +138,7 @@ def test_pack_ragged(gpu, lens, pitch):
 
 NOISE_N = list(range(1, 65)) + [255, 256, 257, 514, 1023, 1024, 1025, 8191, 65537, 2 ** 17 - 1, 2 ** 17 + 1, 2 ** 20 - 1,
                                  2 ** 20 + 1, ke.CLIP_60S, ke.CLIP_60S + 1]
+NOISE_N += [n for n, _why in ke.NOISE_STOCKHAM_N + ke.NOISE_STOCKHAM_N_GPU]
 
 
 @pytest.mark.parametrize("n", NOISE_N)
@@ -128,11 +146,20 @@ def test_noise_irfft(gpu, n):
     ke.run_noise_irfft(gpu, 2, n)
 
 
+def test_noise_irfft_three_rows(gpu):
+    ke.run_noise_irfft(gpu, 3, ke.NOISE_STOCKHAM_ROWS3)
+
+
 @pytest.mark.parametrize("fft,win,hop", [(512, 256, 128), (17, 16, 4), (34, 32, 8), (257, 256, 64), (514, 512, 128), (22, 20, 5),
-                                         (64, 64, 16)])
+                                         (64, 64, 16)] + ke.STFT_GEOMETRIES)
 @pytest.mark.parametrize("n", [1, 255, 1025, 48000])
 def test_stft(gpu, n, fft, win, hop):
     ke.run_stft(gpu, 2, n, fft, win, hop)
+
+
+@pytest.mark.parametrize("fft", ke.GROUP_FFTS)
+def test_stft_two_launch_groups(gpu, fft):
+    ke.run_stft(gpu, fft=fft, last_written=True, **ke.GROUP_STFT)
 
 
 @pytest.mark.parametrize("n_frames,n_frames_ir,n_freq,n_ch,n_irs", [(1, 1, 1, 1, 1), (7, 3, 257, 2, 5), (9, 12, 33, 3, 1),
@@ -141,10 +168,16 @@ def test_tv_stft_mac(gpu, n_frames, n_frames_ir, n_freq, n_ch, n_irs):
     ke.run_tv_stft_mac(gpu, n_frames, n_frames_ir, n_freq, n_ch, n_irs)
 
 
-@pytest.mark.parametrize("fft,win,hop", [(512, 256, 128), (17, 16, 4), (34, 32, 8), (257, 256, 64), (514, 512, 128), (64, 64, 16)])
+@pytest.mark.parametrize("fft,win,hop", [(512, 256, 128), (17, 16, 4), (34, 32, 8), (257, 256, 64), (514, 512, 128), (64, 64, 16)]
+                         + ke.STFT_GEOMETRIES)
 @pytest.mark.parametrize("n_frames,n_ch", [(5, 1), (9, 3), (377, 4)])
 def test_istft_ola(gpu, n_frames, n_ch, fft, win, hop):
     ke.run_istft(gpu, n_frames, n_ch, fft, win, hop)
+
+
+@pytest.mark.parametrize("fft", ke.GROUP_FFTS)
+def test_istft_ola_two_launch_groups(gpu, fft):
+    ke.run_istft(gpu, fft=fft, last_written=True, **ke.GROUP_ISTFT)
 
 
 @pytest.mark.parametrize("n_capsules", [1, 3, 4, 7, 8, 12, 16, 31, 32, 33, 40, 64, 65])

@@ -1,7 +1,22 @@
 """tests/kernel_edges.py on the host-emulated kernels: edge lengths, one length past every grid cap, guard bands and misaligned
 interior pointers, each family against its float64 restatement (more than 65 535 rows in al_row_stats and the 60 s noise
 lengths only on the GPU: emulated workgroups are too slow for them).  The gfx950 build runs the same scenarios in
-tests/test_gpu_kernel_edges.py."""
+tests/test_gpu_kernel_edges.py.
+
+The any-length transform (al_noise_irfft, al_stft, al_istft_ola), by what each length is there for:
+  NOISE_N 1..64                     every small length, each radix alone and mixed: every pass a single, partly filled workgroup
+  256, 1024                         powers of two (len 128, 512: one workgroup)
+  255, 257, 514, 1023, 1025, 8191,  a prime factor above 7: Bluestein, whose power-of-two L is where the radix-4 / 2 passes run
+  65537, 2^17 +- 1                  in many workgroups
+  ke.NOISE_STOCKHAM_N               the radix-3 / 5 / 7 passes past one workgroup: last workgroup exactly full and just over
+                                    full per radix, pure prime powers up to 7^5 with ns growing, all five radices in one
+                                    transform, both parities of n for one len (each row's reason stands beside it).  With these
+                                    NOISE_N covers every radix in a workgroup other than the first.
+  STFT / ISTFT sizes                512, 64 (powers of two), 17, 34, 257, 22 (Bluestein) and ke.STFT_GEOMETRIES: smooth sizes
+                                    that are no power of two, one of them multi-block, fft < win, win == hop, fft 1 / 2 / 3
+  two launch groups                 more than 32 768 series in al_stft (boundary inside a row) and al_istft_ola (boundary
+                                    between the channels of a frame), every element compared; fft = 6 here, 6 and 11 on the GPU
+Every workspace of the three is a guarded buffer of exactly al_*_workspace_floats floats."""
 import pytest
 
 from audiblelight_amd import _hip, engine
@@ -120,7 +135,8 @@ def test_emu_pack_ragged(emu, lens, pitch):
     ke.run_pack_ragged(emu, lens, pitch, shift=pitch % 8 // 4)
 
 
-NOISE_N = list(range(1, 65)) + [257, 514, 255, 256, 1023, 1024, 1025, 8191, 65537, 2 ** 17 - 1, 2 ** 17 + 1]
+NOISE_N = (list(range(1, 65)) + [257, 514, 255, 256, 1023, 1024, 1025, 8191, 65537, 2 ** 17 - 1, 2 ** 17 + 1]
+           + [n for n, _why in ke.NOISE_STOCKHAM_N])
 
 
 @pytest.mark.parametrize("n", NOISE_N)
@@ -128,10 +144,23 @@ def test_emu_noise_irfft(emu, n):
     ke.run_noise_irfft(emu, 2, n)
 
 
-@pytest.mark.parametrize("fft,win,hop", [(512, 256, 128), (17, 16, 4), (34, 32, 8), (257, 256, 64), (22, 20, 5), (64, 64, 16)])
+def test_emu_noise_irfft_three_rows(emu):
+    ke.run_noise_irfft(emu, 3, ke.NOISE_STOCKHAM_ROWS3)
+
+
+@pytest.mark.parametrize("fft,win,hop", [(512, 256, 128), (17, 16, 4), (34, 32, 8), (257, 256, 64), (22, 20, 5), (64, 64, 16)]
+                         + ke.STFT_GEOMETRIES)
 @pytest.mark.parametrize("n", [1, 255, 1025])
 def test_emu_stft(emu, n, fft, win, hop):
     ke.run_stft(emu, 2, n, fft, win, hop)
+
+
+# An emulated workgroup costs 256 context switches whatever it computes, and a series is at least one workgroup per launch: the
+# two-group cases take 20-30 s with the four launches of fft = 6 and over a minute with Bluestein's fft = 11, so the emulation
+# keeps the smooth size only (the GPU runs both).
+@pytest.mark.parametrize("fft", ke.GROUP_FFTS[:1])
+def test_emu_stft_two_launch_groups(emu, fft):
+    ke.run_stft(emu, fft=fft, last_written=True, **ke.GROUP_STFT)
 
 
 @pytest.mark.parametrize("n_frames,n_frames_ir,n_freq,n_ch,n_irs", [(1, 1, 1, 1, 1), (7, 3, 257, 2, 5), (9, 12, 33, 3, 1),
@@ -140,10 +169,15 @@ def test_emu_tv_stft_mac(emu, n_frames, n_frames_ir, n_freq, n_ch, n_irs):
     ke.run_tv_stft_mac(emu, n_frames, n_frames_ir, n_freq, n_ch, n_irs)
 
 
-@pytest.mark.parametrize("fft,win,hop", [(512, 256, 128), (17, 16, 4), (34, 32, 8), (257, 256, 64), (64, 64, 16)])
+@pytest.mark.parametrize("fft,win,hop", [(512, 256, 128), (17, 16, 4), (34, 32, 8), (257, 256, 64), (64, 64, 16)] + ke.STFT_GEOMETRIES)
 @pytest.mark.parametrize("n_frames,n_ch", [(5, 1), (9, 3)])
 def test_emu_istft_ola(emu, n_frames, n_ch, fft, win, hop):
     ke.run_istft(emu, n_frames, n_ch, fft, win, hop)
+
+
+@pytest.mark.parametrize("fft", ke.GROUP_FFTS[:1])
+def test_emu_istft_ola_two_launch_groups(emu, fft):
+    ke.run_istft(emu, fft=fft, last_written=True, **ke.GROUP_ISTFT)
 
 
 @pytest.mark.parametrize("n_capsules", [1, 3, 4, 7, 8, 12, 16, 31, 32, 33, 40, 64, 65])
