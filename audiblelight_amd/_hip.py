@@ -103,6 +103,20 @@ class AlChunk(ct.Structure):          # al_chunk
                                           "xspec_blocks", "yspec_block0", "yspec_blocks", "max_blocks", "max_nj")]
 
 
+class AlFxSosJob(ct.Structure):       # al_fx_sos_job
+    _fields_ = [("src", ct.c_void_p), ("dst", ct.c_void_p), ("n", ct.c_int64), ("sos", ct.c_void_p), ("n_sections", ct.c_int32),
+                ("reserved", ct.c_int32)]
+
+
+class AlFxModJob(ct.Structure):       # al_fx_mod_job (centre: centre_delay_ms of a Chorus, centre_frequency_hz of a Phaser)
+    _fields_ = [("src", ct.c_void_p), ("dst", ct.c_void_p), ("n", ct.c_int64)] + \
+               [(n, ct.c_double) for n in ("fs", "rate_hz", "depth", "centre", "feedback", "mix")]
+
+
+class AlFxDeemphJob(ct.Structure):    # al_fx_deemph_job
+    _fields_ = [("src", ct.c_void_p), ("dst", ct.c_void_p), ("n", ct.c_int64), ("coef", ct.c_float), ("reserved", ct.c_int32)]
+
+
 class HipError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -163,6 +177,9 @@ SYMBOLS = {
     "al_fx_delay": (ct.c_int, [_P, _P, ct.c_int64, ct.c_int64, ct.c_float, ct.c_float, _S]),
     "al_fx_chorus": (ct.c_int, [_P, _P, ct.c_int64] + [ct.c_double] * 6 + [_S]),
     "al_fx_phaser": (ct.c_int, [_P, _P, ct.c_int64] + [ct.c_double] * 6 + [_S]),
+    "al_fx_batch_desc_bytes": (ct.c_int64, [ct.c_int32]),
+    "al_fx_batch_pack": (ct.c_int, [ct.c_int32, _P, ct.c_int32, _P]),
+    "al_fx_batch_launch": (ct.c_int, [ct.c_int32, _P, ct.c_int32, _S]),
     "al_pack_ragged_irs": (ct.c_int, [_P, ct.c_int32, _P, _P, ct.c_int64, ct.c_int32, _P, _S]),
     "al_resample_poly": (ct.c_int, [_P, ct.c_int32, ct.c_int64, _P, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.c_int64, ct.c_int64, _S]),
     "al_encode_frames": (ct.c_int, [_P, ct.c_int32, ct.c_int64, ct.c_int32, _P, _S]),
@@ -186,6 +203,8 @@ SYMBOLS = {
 FRAMES_F32, FRAMES_PCM16 = 0, 1
 FX_GAIN, FX_INVERT, FX_REVERSE, FX_FADE, FX_CLIP, FX_TANH, FX_BITCRUSH, FX_PREEMPH, FX_DEEMPH = range(1, 10)
 SOS_MAX_SECTIONS = 16   # AL_SOS_MAX_SECTIONS: second-order sections per al_fx_sos call
+FXB_SOS, FXB_CHORUS, FXB_PHASER, FXB_DEEMPH = 1, 2, 3, 4   # AL_FXB_*: the kinds of a batched FX launch (al_fx_batch_*)
+FXB_JOBS = {FXB_SOS: AlFxSosJob, FXB_CHORUS: AlFxModJob, FXB_PHASER: AlFxModJob, FXB_DEEMPH: AlFxDeemphJob}
 FADE_SHAPES = {"linear": 0, "exponential": 1, "logarithmic": 2, "quarter_sine": 3, "half_sine": 4, "none": 5}
 
 

@@ -6,7 +6,11 @@ TimeWarpSilence / Duplicate / Remove / Reverse, the linear time-invariant filter
 HighpassFilter, LowShelfFilter, HighShelfFilter and MultibandEqualizer (cascades of second-order
 sections, one ``al_fx_sos`` launch each), the delay and modulation FX Delay, Chorus and Phaser
 (linear recursions with feedback, one ``al_fx_delay`` / ``al_fx_chorus`` / ``al_fx_phaser`` launch
-each) and the peak normalisation of ``Event.load_audio``.  The other stateful pedalboard effects
+each) and the peak normalisation of ``Event.load_audio``.  The FX whose kernel is a one-workgroup scan (the filters,
+Chorus with feedback, Phaser, Deemphasis) also describe their launch as a job (``batch_job``), and ``run_chains`` runs the
+chains of a whole scene together: the pending scans of one kind on all clips go into ONE launch (``al_fx_batch_pack`` /
+``al_fx_batch_launch``, one workgroup per clip) with the samples of the per-clip launches, bit for bit (DESIGN.md "Batched
+FX launches").  The other stateful pedalboard effects
 (dynamics: Compressor, Limiter; codecs: GSMFullRateCompressor, MP3Compressor; time-stretch:
 PitchShift, SpeedUp) stay on the host with the reference implementation: out of scope (SURVEY.md
 section 2, row 3b).
@@ -136,17 +140,24 @@ def _fx(clip: DeviceClip, op: int, p0: float = 0.0, iparams=None, out_of_place: 
         clip.swap()
 
 
+def _sos_rows(rows, gain: float) -> np.ndarray:
+    """The float64 (K, 6) rows a launch is given: ``gain`` folded into the first section's numerator."""
+    rows = np.array(rows, dtype=np.float64).reshape(-1, 6)
+    if len(rows):
+        rows[0, :3] *= gain
+    return rows
+
+
 def _sos(clip: DeviceClip, rows, gain: float = 1.0) -> None:
     """Filter the clip in place through float64 second-order sections ``rows`` (K x 6: b0 b1 b2 a0 a1 a2) preceded by the
     constant ``gain``: one al_fx_sos launch per AL_SOS_MAX_SECTIONS sections, the gain folded into the first section's
     numerator.  No rows: the gain alone (one pointwise launch, none at all for the identity)."""
     r = clip.r
-    rows = np.array(rows, dtype=np.float64).reshape(-1, 6)
+    rows = _sos_rows(rows, gain)
     if len(rows) == 0:
         if gain != 1.0:
             _fx(clip, _hip.FX_GAIN, float(gain))
         return
-    rows[0, :3] *= gain
     for k0 in range(0, len(rows), _hip.SOS_MAX_SECTIONS):
         part = np.ascontiguousarray(rows[k0: k0 + _hip.SOS_MAX_SECTIONS])   # a HOST array: read while the launch is built
         r.lib.call("al_fx_sos", r.mem.ptr(clip.buf), r.mem.ptr(clip.buf), clip.n, part.ctypes.data, len(part), r.mem.stream())
@@ -167,6 +178,79 @@ def run_chain(clip: DeviceClip, augmentations, normalize: bool = True) -> Device
     if normalize:
         clip.peak_normalize()
     return clip
+
+
+def launch_batch(r, kind: int, jobs) -> None:
+    """One batched launch of ``kind`` (_hip.FXB_*): ``jobs`` is a list of (src pointer, dst pointer, n, fields), ``fields`` the
+    scalars of the kind's job struct (FXB_SOS: ``rows``, the float64 (K, 6) sections).  The library checks and packs the
+    descriptors on the host (al_fx_batch_pack), the table goes to HBM through the memory provider, al_fx_batch_launch runs
+    one workgroup per job.  The table may go once the call returns: the allocator orders its reuse behind the launch (same
+    stream), like TimeWarp's row table."""
+    count = len(jobs)
+    arr = (_hip.FXB_JOBS[kind] * count)()
+    keep = []   # the host SOS rows live until the pack has read them
+    for job, (src, dst, n, fields) in zip(arr, jobs):
+        job.src, job.dst, job.n = src, dst, n
+        if kind == _hip.FXB_SOS:
+            keep.append(np.ascontiguousarray(fields["rows"], dtype=np.float64))
+            job.sos, job.n_sections = keep[-1].ctypes.data, len(keep[-1])
+        else:
+            for name, value in fields.items():
+                setattr(job, name, value)
+    table = np.zeros(count * r.lib.call("al_fx_batch_desc_bytes", kind), dtype=np.uint8)
+    r.lib.call("al_fx_batch_pack", kind, ct.cast(arr, ct.c_void_p), count, table.ctypes.data)
+    device_table = r.mem.upload(table)
+    r.lib.call("al_fx_batch_launch", kind, r.mem.ptr(device_table), count, r.mem.stream())
+
+
+def run_chains(clips, chains, normalize: bool = False) -> list:
+    """``run_chain`` for every (clip, chain) pair of a scene at once, with the same samples bit for bit, in far fewer launches:
+    an FX whose kernel is a one-workgroup scan describes its launch as a job (``batch_job``), and the pending jobs of one kind
+    on all clips run as ONE grid, one workgroup per clip (``launch_batch``).
+
+    Scheduling: every clip runs its FX one by one as ``run_chain`` does until its next FX has a job (or its chain ends); the
+    heads now pending are grouped by kind, each kind is one pack, one upload and one launch; repeat until every chain is done.
+    Everything is enqueued on the one stream, so each clip sees its FX in chain order.
+
+    Random draws: the only draws made while a chain RUNS are TimeWarp's coin flips (Python's ``random``).  Every FX hands the
+    clip on at its input length, so each event's flips depend on nothing the device computes: they are all drawn up front
+    (``draw``), event 0's whole chain, then event 1's, ... -- the order the per-event loop consumes them in -- and the
+    launches made from them later."""
+    chains = [list(chain) for chain in chains]
+    drawn = [[a.draw(clip.n) if hasattr(a, "draw") else None for a in chain] for clip, chain in zip(clips, chains)]
+    pos = [0] * len(clips)
+    while True:
+        pending = {}    # kind -> [(clip index, fields)]
+        for i, (clip, chain) in enumerate(zip(clips, chains)):
+            while pos[i] < len(chain):
+                aug = chain[pos[i]]
+                job = aug.batch_job(clip) if hasattr(aug, "batch_job") else None
+                if job is not None:
+                    pending.setdefault(job[0], []).append((i, job[1]))
+                    break
+                if drawn[i][pos[i]] is None:
+                    aug.process_device(clip)
+                else:
+                    aug.process_device(clip, drawn[i][pos[i]])
+                pos[i] += 1
+        if not pending:
+            break
+        for kind in sorted(pending):
+            in_place = kind == _hip.FXB_SOS    # the other kinds ping-pong like _DelayModFX; every kind keeps the length
+            jobs = []
+            for i, fields in pending[kind]:
+                clip = clips[i]
+                dst = clip.buf if in_place else clip.other(clip.n)
+                jobs.append((clip.r.mem.ptr(clip.buf), clip.r.mem.ptr(dst), clip.n, fields))
+            launch_batch(clips[pending[kind][0][0]].r, kind, jobs)
+            for i, _ in pending[kind]:
+                if not in_place:
+                    clips[i].swap()
+                pos[i] += 1
+    if normalize:
+        for clip in clips:
+            clip.peak_normalize()
+    return list(clips)
 
 
 def fold_scalars(augmentations) -> Optional[float]:
@@ -194,10 +278,24 @@ class Augmentation:
     def apply_device(self, clip: DeviceClip) -> None:
         return None
 
-    def process_device(self, clip: DeviceClip) -> None:
-        """The FX plus the wrap-pad / truncate back to the input length, on a clip that stays in HBM."""
+    def draw(self, n: int):
+        """Whatever ``apply_device`` would draw from a random generator for a clip of ``n`` samples, drawn now (``run_chains``
+        draws a whole scene's up front); None: this FX draws nothing while it runs."""
+        return None
+
+    def batch_job(self, clip: DeviceClip):
+        """(kind, fields) when this FX on ``clip`` is ONE launch of a one-workgroup scan that ``launch_batch`` can run together
+        with other clips' (kind: _hip.FXB_*); None: ``process_device`` runs it."""
+        return None
+
+    def process_device(self, clip: DeviceClip, drawn=None) -> None:
+        """The FX plus the wrap-pad / truncate back to the input length, on a clip that stays in HBM.  ``drawn``: what
+        ``draw(clip.n)`` returned earlier (then nothing is drawn here)."""
         n_in = clip.n
-        self.apply_device(clip)
+        if drawn is None:
+            self.apply_device(clip)
+        else:
+            self.apply_device(clip, drawn)
         if clip.n != n_in:
             r = clip.r
             dst = clip.other(n_in)
@@ -331,6 +429,11 @@ class Preemphasis(EventAugmentation):
 class Deemphasis(Preemphasis):
     _OP = _hip.FX_DEEMPH
 
+    def batch_job(self, clip):
+        if clip.n < 2:
+            return None     # refused by the single-clip entry: let it say so
+        return _hip.FXB_DEEMPH, dict(coef=float(self.coef))
+
 
 class Fade(EventAugmentation):
     MIN_FADE, MAX_FADE = 0.0, 1.0
@@ -405,11 +508,16 @@ class TimeWarp(EventAugmentation):
         # TimeWarpSilence replaces a hit frame by np.zeros(len(frame)) -- float64 -- and np.concatenate widens the rest to it
         return np.result_type(in_dtype, np.float64) if getattr(self, "_spliced_zeros", False) else in_dtype
 
-    def apply_device(self, clip):
+    def draw(self, n):
         self._spliced_zeros = False
-        if self.prob == 0:
+        return self.row_plan(n) if self.prob != 0 else None
+
+    def apply_device(self, clip, drawn=None):
+        if drawn is None:
+            drawn = self.draw(clip.n)
+        if drawn is None:
             return
-        stride, row_len, rows = self.row_plan(clip.n)
+        stride, row_len, rows = drawn
         if not rows:
             return  # every row removed: the reference falls back to the input (augmentation.py:1698-1701)
         r = clip.r
@@ -521,6 +629,12 @@ class _FilterFX(EventAugmentation):
     def apply_device(self, clip):
         rows, gain = self.sections()
         _sos(clip, rows, gain)
+
+    def batch_job(self, clip):
+        rows = _sos_rows(*self.sections())
+        if not 1 <= len(rows) <= _hip.SOS_MAX_SECTIONS:
+            return None     # a constant gain (or nothing at all); a cascade that takes several launches
+        return _hip.FXB_SOS, dict(rows=rows)
 
 
 class _FirstOrderFilter(_FilterFX):
@@ -678,6 +792,7 @@ class _Modulation(_DelayModFX):
     MIN_FEEDBACK, MAX_FEEDBACK = 0.0, 0.9
     CENTRE = ""                     # the name of the centre parameter
     ENTRY = ""
+    KIND = 0                        # _hip.FXB_* of the batched launch
 
     def __init__(self, sample_rate, rate_hz, depth, centre, feedback, mix):
         super().__init__(sample_rate)
@@ -689,6 +804,12 @@ class _Modulation(_DelayModFX):
         self.mix = _positive(_sample(mix, self.MIN_MIX, self.MAX_MIX))
         self.params = {"rate_hz": self.rate_hz, "depth": self.depth, self.CENTRE: centre, "feedback": self.feedback,
                        "mix": self.mix}
+
+    def batch_job(self, clip):
+        if self.KIND == _hip.FXB_CHORUS and self.feedback == 0:
+            return None     # grid-wide already (k_fx_chorus_ff)
+        return self.KIND, dict(fs=float(self.sample_rate), rate_hz=float(self.rate_hz), depth=float(self.depth),
+                               centre=float(getattr(self, self.CENTRE)), feedback=float(self.feedback), mix=float(self.mix))
 
     def launch(self, clip, dst):
         r = clip.r
@@ -707,6 +828,7 @@ class Chorus(_Modulation):
     MIN_CENTRE, MAX_CENTRE = MIN_DELAY, MAX_DELAY = 1.0, 20.0
     CENTRE = "centre_delay_ms"
     ENTRY = "al_fx_chorus"
+    KIND = _hip.FXB_CHORUS
 
     def __init__(self, sample_rate=config.SAMPLE_RATE, rate_hz=None, depth=None, centre_delay_ms=None, feedback=None,
                  mix=None):
@@ -724,6 +846,7 @@ class Phaser(_Modulation):
     MIN_CENTRE, MAX_CENTRE = MIN_FREQ, MAX_FREQ = 260, 6500
     CENTRE = "centre_frequency_hz"
     ENTRY = "al_fx_phaser"
+    KIND = _hip.FXB_PHASER
 
     def __init__(self, sample_rate=config.SAMPLE_RATE, rate_hz=None, depth=None, centre_frequency_hz=None, feedback=None,
                  mix=None):

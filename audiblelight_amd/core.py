@@ -225,7 +225,7 @@ class Event:
 def stage_event_chains(events, ignore_cache: bool = False) -> list:
     """Before a scene is rendered: the raw clips of every event whose FX chain has to RUN on the device (not foldable into a
     scalar, no cached realisation, nothing loaded to the host) go to HBM through one page-locked arena and one asynchronous
-    DMA, and their chains run there (event.py:520-539 does a blocking load + host chain per event)."""
+    DMA, and their chains run there, all together (event.py:520-539 does a blocking load + host chain per event)."""
     from . import augmentation, synthesize
 
     todo = [ev for ev in events
@@ -234,9 +234,15 @@ def stage_event_chains(events, ignore_cache: bool = False) -> list:
             and all(hasattr(a, "process_device") for a in ev.augmentations)]
     if not todo:
         return []
+    from . import ingest
+
     staged = augmentation.stage_clips(synthesize.get_renderer(), [ev._raw for ev in todo])
     for ev, clip in zip(todo, staged):
-        ev._chain(True, staged=clip)
+        ingest.resample_clip(clip, ev.native_sample_rate, ev.sample_rate)
+    # all chains together: the one-workgroup scans of every event in one launch per kind (augmentation.run_chains)
+    augmentation.run_chains(staged, [ev.augmentations for ev in todo])
+    for ev, clip in zip(todo, staged):
+        ev._last_chain = clip
     return todo
 
 

@@ -66,8 +66,22 @@ __global__ __launch_bounds__(256) void k_fx_pointwise(const float *src, float *d
 
 // y[n] = x[n] + c*y[n-1] minus the extrapolation correction: one workgroup, each thread owns a
 // contiguous run; carries are chained by thread 0 (1024 runs), then folded back in.
-__global__ __launch_bounds__(1024) void k_fx_deemph(const float *src, float *dst, int64_t n, float c) {
+struct DeemphJob {
+  const float *src;
+  float *dst;
+  int64_t n;
+  float c;
+};
+
+// Workgroup b takes job b: table[b] of a batched launch (al_fx_batch_launch), or `one` when table == nullptr (grid of 1); the
+// same instantiation either way.
+__global__ __launch_bounds__(1024) void k_fx_deemph(const DeemphJob *__restrict__ table, DeemphJob one) {
   __shared__ float tail[1024], decay[1024], carry[1024];
+  const DeemphJob *job = table ? table + blockIdx.x : nullptr;
+  const float *src = job ? job->src : one.src;
+  float *dst = job ? job->dst : one.dst;
+  const int64_t n = job ? job->n : one.n;
+  const float c = job ? job->c : one.c;
   const int tid = threadIdx.x;
   const int64_t run = (n + 1023) / 1024;
   const int64_t lo = (int64_t)tid * run, hi = lo + run < n ? lo + run : n;

@@ -133,10 +133,24 @@ __global__ __launch_bounds__(256) void k_fx_chorus_ff(const float *x, float *y, 
   }
 }
 
+// One clip's launch of k_fx_chorus_fb: what al_fx_chorus derives from its arguments (one per workgroup of a batched launch).
+struct ChorusJob {
+  const float *src;
+  float *dst;
+  int64_t n;
+  ChorusArgs a;
+};
+
 // u[t] = x[t] - fb v[t-1]; v[t] from u[t - i], u[t - i - 1] with i >= B.  Block [s, s + B): every v, then every u.
-__global__ __launch_bounds__(1024) void k_fx_chorus_fb(const float *x, float *y, int64_t n, ChorusArgs a) {
+// Workgroup b takes job b: table[b], or `one` when table == nullptr (grid of 1); the same instantiation either way.
+__global__ __launch_bounds__(1024) void k_fx_chorus_fb(const ChorusJob *__restrict__ table, ChorusJob one) {
   __shared__ float ring[CHO_RING];   // u[m] at m & (CHO_RING - 1); holds u[s - tau_max - 1, s + B)
   __shared__ double vb[CHO_MAX_BLOCK];
+  const ChorusJob *job = table ? table + blockIdx.x : nullptr;
+  const float *x = job ? job->src : one.src;
+  float *y = job ? job->dst : one.dst;
+  const int64_t n = job ? job->n : one.n;
+  const ChorusArgs a = job ? job->a : one.a;
   const int j = threadIdx.x;
   const int64_t B = a.block;
   double vlast = 0.0;   // v[s - 1]
@@ -205,8 +219,22 @@ __device__ inline double phaser_step(double *st, double G, double fb, double xin
   return in;
 }
 
-__global__ __launch_bounds__(PH_THREADS) void k_fx_phaser(const float *x, float *y, int64_t n, int64_t run, PhaserArgs a) {
+// One clip's launch: what al_fx_phaser derives from its arguments (one per workgroup of a batched launch).
+struct PhaserJob {
+  const float *src;
+  float *dst;
+  int64_t n, run;
+  PhaserArgs a;
+};
+
+// Workgroup b takes job b: table[b], or `one` when table == nullptr (grid of 1); the same instantiation either way.
+__global__ __launch_bounds__(PH_THREADS) void k_fx_phaser(const PhaserJob *__restrict__ table, PhaserJob one) {
   __shared__ double maps[PH_BATCH][PH_DIM * PH_DIM + PH_DIM];   // M row-major, then e; e is replaced by the entering state
+  const PhaserJob *job = table ? table + blockIdx.x : nullptr;
+  const float *x = job ? job->src : one.src;
+  float *y = job ? job->dst : one.dst;
+  const int64_t n = job ? job->n : one.n, run = job ? job->run : one.run;
+  const PhaserArgs a = job ? job->a : one.a;
   const int tid = threadIdx.x;
   const int64_t lo = (int64_t)tid * run;
   const int64_t hi = lo + run < n ? lo + run : n;   // may be <= lo: an empty run (identity map)

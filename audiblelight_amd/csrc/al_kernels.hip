@@ -259,83 +259,15 @@ int al_row_stats(const float *x, int32_t rows, int64_t cols, float *partials, do
   return check_launch("k_row_stats_final");
 }
 
-int al_fx_apply(int op, const float *src, float *dst, int64_t n, const float *params, const int32_t *iparams,
-                al_stream_t stream) {
-  if (!src || !dst || n <= 0) return fail(AL_E_BADARG, "bad fx arguments");
-  if (op < AL_FX_GAIN || op > AL_FX_DEEMPH) return fail(AL_E_UNSUPPORTED, "unknown fx op");
-  const bool out_of_place = (op == AL_FX_REVERSE || op == AL_FX_PREEMPH || op == AL_FX_DEEMPH);
-  if (out_of_place && src == dst) return fail(AL_E_BADARG, "this fx op needs dst != src");
-  if ((op == AL_FX_PREEMPH || op == AL_FX_DEEMPH) && n < 2) return fail(AL_E_BADARG, "emphasis filters need n >= 2");
-  al::FxArgs a{op, params ? params[0] : 0.f, 0, 0, AL_FADE_NONE, AL_FADE_NONE};
-  if (op == AL_FX_FADE) {
-    if (!iparams) return fail(AL_E_BADARG, "fade needs iparams");
-    a.n_in = iparams[0]; a.n_out = iparams[1]; a.shape_in = iparams[2]; a.shape_out = iparams[3];
-  }
-  if (op == AL_FX_DEEMPH) {
-    hipLaunchKernelGGL(al::k_fx_deemph, dim3(1), dim3(1024), 0, (hipStream_t)stream, src, dst, n, a.p0);
-    return check_launch("k_fx_deemph");
-  }
-  const int64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(al::k_fx_pointwise, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
-                     (hipStream_t)stream, src, dst, n, a);
-  return check_launch("k_fx_pointwise");
-}
-
-int al_fx_frame_shuffle(const float *src, float *dst, int64_t n, int32_t frame_len, int32_t row_len,
-                        const int32_t *rows, int32_t n_rows, al_stream_t stream) {
-  if (!src || !dst || !rows || n <= 0 || frame_len <= 0 || row_len <= 0 || n_rows <= 0 || src == dst)
-    return fail(AL_E_BADARG, "bad frame_shuffle arguments");
-  const int64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(al::k_frame_shuffle, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
-                     (hipStream_t)stream, src, dst, n, frame_len, row_len, rows, n_rows);
-  return check_launch("k_frame_shuffle");
-}
-
-int al_fx_sos(const float *src, float *dst, int64_t n, const double *sos, int32_t n_sections, al_stream_t stream) {
-  if (!src || !dst || !sos) return fail(AL_E_BADARG, "al_fx_sos: null pointer");
-  if (n < 1) return fail(AL_E_BADARG, "al_fx_sos: n must be >= 1");
-  if (n_sections < 1 || n_sections > AL_SOS_MAX_SECTIONS)
-    return fail(AL_E_BADARG, "al_fx_sos: n_sections must be in 1..AL_SOS_MAX_SECTIONS (16); split longer cascades");
-  const int64_t run = al::sos_run_length(n);
-  al::SosArgs a;
-  memset(&a, 0, sizeof(a));
-  a.n_sections = n_sections;
-  char msg[160];
-  for (int k = 0; k < n_sections; ++k) {
-    const double *row = sos + 6 * k;
-    for (int i = 0; i < 6; ++i)
-      if (!isfinite(row[i])) {
-        snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a non-finite coefficient", k);
-        return fail(AL_E_BADARG, msg);
-      }
-    if (row[3] == 0.0) {
-      snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a0 == 0", k);
-      return fail(AL_E_BADARG, msg);
-    }
-    const double c[5] = {row[0] / row[3], row[1] / row[3], row[2] / row[3], row[4] / row[3], row[5] / row[3]};
-    for (int i = 0; i < 5; ++i)
-      if (!isfinite(c[i])) {
-        snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a non-finite coefficient after division by a0", k);
-        return fail(AL_E_BADARG, msg);
-      }
-    // both roots of z^2 + a1 z + a2 inside the unit circle (Jury): |a2| < 1 and |a1| < 1 + a2
-    if (!(fabs(c[4]) < 1.0 && fabs(c[3]) < 1.0 + c[4])) {
-      snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a pole of magnitude >= 1 (unstable filter)", k);
-      return fail(AL_E_BADARG, msg);
-    }
-    for (int i = 0; i < 5; ++i) a.c[k][i] = c[i];
-    al::sos_transition_power(c[3], c[4], run, a.phi[k]);
-  }
-  hipLaunchKernelGGL(al::k_fx_sos, dim3(1), dim3(al::SOS_THREADS), 0, (hipStream_t)stream, src, dst, n, run, a);
-  return check_launch("k_fx_sos");
-}
-
-// ---- delay and modulation FX: out of place, every parameter finite and >= 0, feedback < 1
+// ---- FX: the checks and derivations of every entry whose kernel a batched launch can run, shared by the single-clip entries and
+// al_fx_batch_pack.  Each returns 0 with *job filled, or the error of the first bad argument.
 namespace {
-bool fx_overlap(const float *a, const float *b, int64_t n) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
-  return pa < pb + bytes && pb < pa + bytes;
+bool fx_ranges_overlap(const float *a, int64_t na, const float *b, int64_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + (uintptr_t)nb * sizeof(float) && pb < pa + (uintptr_t)na * sizeof(float);
 }
+
+bool fx_overlap(const float *a, const float *b, int64_t n) { return fx_ranges_overlap(a, n, b, n); }
 
 // 0, or the error for the first bad argument
 int fx_check(const char *fn, const float *src, const float *dst, int64_t n, const char *const *names, const double *vals,
@@ -365,22 +297,68 @@ int fx_check(const char *fn, const float *src, const float *dst, int64_t n, cons
   }
   return AL_OK;
 }
-}  // namespace
 
-int al_fx_delay(const float *src, float *dst, int64_t n, int64_t delay_samples, float feedback, float mix, al_stream_t stream) {
-  static const char *const names[] = {"feedback", "mix"};
-  const double vals[] = {feedback, mix};
-  if (int e = fx_check("al_fx_delay", src, dst, n, names, vals, 2)) return e;
-  if (delay_samples < 0) return fail(AL_E_BADARG, "al_fx_delay: delay_samples must be >= 0");
-  const al::DelayPlan pl = al::delay_plan(n, delay_samples, (double)feedback);
-  const int64_t grid = (pl.residues + pl.G - 1) / pl.G;
-  hipLaunchKernelGGL(al::k_fx_delay, dim3((unsigned)grid), dim3(pl.G * pl.P), 0, (hipStream_t)stream, src, dst, n, pl,
-                     (double)feedback, 1.0 - (double)mix, (double)mix);
-  return check_launch("k_fx_delay");
+// al_fx_apply's checks of its clip arguments
+int fx_apply_check(int op, const float *src, const float *dst, int64_t n) {
+  if (!src || !dst || n <= 0) return fail(AL_E_BADARG, "bad fx arguments");
+  if (op < AL_FX_GAIN || op > AL_FX_DEEMPH) return fail(AL_E_UNSUPPORTED, "unknown fx op");
+  const bool out_of_place = (op == AL_FX_REVERSE || op == AL_FX_PREEMPH || op == AL_FX_DEEMPH);
+  if (out_of_place && src == dst) return fail(AL_E_BADARG, "this fx op needs dst != src");
+  if ((op == AL_FX_PREEMPH || op == AL_FX_DEEMPH) && n < 2) return fail(AL_E_BADARG, "emphasis filters need n >= 2");
+  return AL_OK;
 }
 
-int al_fx_chorus(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_delay_ms,
-                 double feedback, double mix, al_stream_t stream) {
+int deemph_prepare(const float *src, float *dst, int64_t n, float c, al::DeemphJob *job) {
+  if (int rc = fx_apply_check(AL_FX_DEEMPH, src, dst, n)) return rc;
+  *job = al::DeemphJob{src, dst, n, c};
+  return AL_OK;
+}
+
+int sos_prepare(const float *src, float *dst, int64_t n, const double *sos, int32_t n_sections, al::SosJob *job) {
+  if (!src || !dst || !sos) return fail(AL_E_BADARG, "al_fx_sos: null pointer");
+  if (n < 1) return fail(AL_E_BADARG, "al_fx_sos: n must be >= 1");
+  if (n_sections < 1 || n_sections > AL_SOS_MAX_SECTIONS)
+    return fail(AL_E_BADARG, "al_fx_sos: n_sections must be in 1..AL_SOS_MAX_SECTIONS (16); split longer cascades");
+  const int64_t run = al::sos_run_length(n);
+  memset(job, 0, sizeof(*job));
+  job->src = src;
+  job->dst = dst;
+  job->n = n;
+  job->run = run;
+  al::SosArgs &a = job->a;
+  a.n_sections = n_sections;
+  char msg[160];
+  for (int k = 0; k < n_sections; ++k) {
+    const double *row = sos + 6 * k;
+    for (int i = 0; i < 6; ++i)
+      if (!isfinite(row[i])) {
+        snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a non-finite coefficient", k);
+        return fail(AL_E_BADARG, msg);
+      }
+    if (row[3] == 0.0) {
+      snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a0 == 0", k);
+      return fail(AL_E_BADARG, msg);
+    }
+    const double c[5] = {row[0] / row[3], row[1] / row[3], row[2] / row[3], row[4] / row[3], row[5] / row[3]};
+    for (int i = 0; i < 5; ++i)
+      if (!isfinite(c[i])) {
+        snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a non-finite coefficient after division by a0", k);
+        return fail(AL_E_BADARG, msg);
+      }
+    // both roots of z^2 + a1 z + a2 inside the unit circle (Jury): |a2| < 1 and |a1| < 1 + a2
+    if (!(fabs(c[4]) < 1.0 && fabs(c[3]) < 1.0 + c[4])) {
+      snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a pole of magnitude >= 1 (unstable filter)", k);
+      return fail(AL_E_BADARG, msg);
+    }
+    for (int i = 0; i < 5; ++i) a.c[k][i] = c[i];
+    al::sos_transition_power(c[3], c[4], run, a.phi[k]);
+  }
+  return AL_OK;
+}
+
+// delay and modulation FX: out of place, every parameter finite and >= 0, feedback < 1
+int chorus_prepare(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_delay_ms,
+                   double feedback, double mix, al::ChorusJob *job) {
   static const char *const names[] = {"fs", "rate_hz", "depth", "centre_delay_ms", "feedback", "mix"};
   const double vals[] = {fs, rate_hz, depth, centre_delay_ms, feedback, mix};
   if (int e = fx_check("al_fx_chorus", src, dst, n, names, vals, 6)) return e;
@@ -388,7 +366,10 @@ int al_fx_chorus(const float *src, float *dst, int64_t n, double fs, double rate
   const double b_min = floor(fs / 1000.0);   // tau >= fs / 1000: the 1 ms floor of the delay
   if (!(b_min >= 1.0) || tau_max + b_min + 2.0 > (double)al::CHO_RING)
     return fail(AL_E_BADARG, "al_fx_chorus: fs out of range (1000 <= fs and ceil(0.11 fs) + floor(fs / 1000) + 2 <= 16384)");
-  al::ChorusArgs a;
+  job->src = src;
+  job->dst = dst;
+  job->n = n;
+  al::ChorusArgs &a = job->a;
   a.fs = fs;
   a.rate = rate_hz;
   a.depth10 = 10.0 * depth;
@@ -405,24 +386,21 @@ int al_fx_chorus(const float *src, float *dst, int64_t n, double fs, double rate
   b = b < (double)al::CHO_MAX_BLOCK ? b : (double)al::CHO_MAX_BLOCK;
   b = b < (double)al::CHO_RING - tau_max - 2.0 ? b : (double)al::CHO_RING - tau_max - 2.0;
   a.block = (int64_t)b;
-  if (feedback == 0.0) {
-    const int64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(al::k_fx_chorus_ff, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0,
-                       (hipStream_t)stream, src, dst, n, a);
-    return check_launch("k_fx_chorus_ff");
-  }
-  hipLaunchKernelGGL(al::k_fx_chorus_fb, dim3(1), dim3(al::CHO_THREADS), 0, (hipStream_t)stream, src, dst, n, a);
-  return check_launch("k_fx_chorus_fb");
+  return AL_OK;
 }
 
-int al_fx_phaser(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_frequency_hz,
-                 double feedback, double mix, al_stream_t stream) {
+int phaser_prepare(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_frequency_hz,
+                   double feedback, double mix, al::PhaserJob *job) {
   static const char *const names[] = {"fs", "rate_hz", "depth", "centre_frequency_hz", "feedback", "mix"};
   const double vals[] = {fs, rate_hz, depth, centre_frequency_hz, feedback, mix};
   if (int e = fx_check("al_fx_phaser", src, dst, n, names, vals, 6)) return e;
   if (!(0.49 * fs > 20.0)) return fail(AL_E_BADARG, "al_fx_phaser: fs out of range (0.49 fs must exceed 20 Hz)");
   const double fmax_hz = fmin(20000.0, 0.49 * fs);
-  al::PhaserArgs a;
+  job->src = src;
+  job->dst = dst;
+  job->n = n;
+  job->run = al::phaser_run_length(n);
+  al::PhaserArgs &a = job->a;
   a.fs = fs;
   a.rate = rate_hz;
   a.half_depth = 0.5 * depth;
@@ -432,9 +410,165 @@ int al_fx_phaser(const float *src, float *dst, int64_t n, double fs, double rate
   const double m = mix < 1.0 ? mix : 1.0;
   a.dry = 1.0 - m;
   a.wet = m;
-  hipLaunchKernelGGL(al::k_fx_phaser, dim3(1), dim3(al::PH_THREADS), 0, (hipStream_t)stream, src, dst, n,
-                     al::phaser_run_length(n), a);
+  return AL_OK;
+}
+}  // namespace
+
+int al_fx_apply(int op, const float *src, float *dst, int64_t n, const float *params, const int32_t *iparams,
+                al_stream_t stream) {
+  if (int rc = fx_apply_check(op, src, dst, n)) return rc;
+  al::FxArgs a{op, params ? params[0] : 0.f, 0, 0, AL_FADE_NONE, AL_FADE_NONE};
+  if (op == AL_FX_FADE) {
+    if (!iparams) return fail(AL_E_BADARG, "fade needs iparams");
+    a.n_in = iparams[0]; a.n_out = iparams[1]; a.shape_in = iparams[2]; a.shape_out = iparams[3];
+  }
+  if (op == AL_FX_DEEMPH) {
+    al::DeemphJob job;
+    if (int rc = deemph_prepare(src, dst, n, a.p0, &job)) return rc;
+    hipLaunchKernelGGL(al::k_fx_deemph, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const al::DeemphJob *)nullptr, job);
+    return check_launch("k_fx_deemph");
+  }
+  const int64_t blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(al::k_fx_pointwise, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
+                     (hipStream_t)stream, src, dst, n, a);
+  return check_launch("k_fx_pointwise");
+}
+
+int al_fx_frame_shuffle(const float *src, float *dst, int64_t n, int32_t frame_len, int32_t row_len,
+                        const int32_t *rows, int32_t n_rows, al_stream_t stream) {
+  if (!src || !dst || !rows || n <= 0 || frame_len <= 0 || row_len <= 0 || n_rows <= 0 || src == dst)
+    return fail(AL_E_BADARG, "bad frame_shuffle arguments");
+  const int64_t blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(al::k_frame_shuffle, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
+                     (hipStream_t)stream, src, dst, n, frame_len, row_len, rows, n_rows);
+  return check_launch("k_frame_shuffle");
+}
+
+int al_fx_sos(const float *src, float *dst, int64_t n, const double *sos, int32_t n_sections, al_stream_t stream) {
+  al::SosJob job;
+  if (int rc = sos_prepare(src, dst, n, sos, n_sections, &job)) return rc;
+  hipLaunchKernelGGL(al::k_fx_sos, dim3(1), dim3(al::SOS_THREADS), 0, (hipStream_t)stream, (const al::SosJob *)nullptr, job);
+  return check_launch("k_fx_sos");
+}
+
+int al_fx_delay(const float *src, float *dst, int64_t n, int64_t delay_samples, float feedback, float mix, al_stream_t stream) {
+  static const char *const names[] = {"feedback", "mix"};
+  const double vals[] = {feedback, mix};
+  if (int e = fx_check("al_fx_delay", src, dst, n, names, vals, 2)) return e;
+  if (delay_samples < 0) return fail(AL_E_BADARG, "al_fx_delay: delay_samples must be >= 0");
+  const al::DelayPlan pl = al::delay_plan(n, delay_samples, (double)feedback);
+  const int64_t grid = (pl.residues + pl.G - 1) / pl.G;
+  hipLaunchKernelGGL(al::k_fx_delay, dim3((unsigned)grid), dim3(pl.G * pl.P), 0, (hipStream_t)stream, src, dst, n, pl,
+                     (double)feedback, 1.0 - (double)mix, (double)mix);
+  return check_launch("k_fx_delay");
+}
+
+int al_fx_chorus(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_delay_ms,
+                 double feedback, double mix, al_stream_t stream) {
+  al::ChorusJob job;
+  if (int rc = chorus_prepare(src, dst, n, fs, rate_hz, depth, centre_delay_ms, feedback, mix, &job)) return rc;
+  if (feedback == 0.0) {
+    const int64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(al::k_fx_chorus_ff, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0,
+                       (hipStream_t)stream, src, dst, n, job.a);
+    return check_launch("k_fx_chorus_ff");
+  }
+  hipLaunchKernelGGL(al::k_fx_chorus_fb, dim3(1), dim3(al::CHO_THREADS), 0, (hipStream_t)stream, (const al::ChorusJob *)nullptr, job);
+  return check_launch("k_fx_chorus_fb");
+}
+
+int al_fx_phaser(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_frequency_hz,
+                 double feedback, double mix, al_stream_t stream) {
+  al::PhaserJob job;
+  if (int rc = phaser_prepare(src, dst, n, fs, rate_hz, depth, centre_frequency_hz, feedback, mix, &job)) return rc;
+  hipLaunchKernelGGL(al::k_fx_phaser, dim3(1), dim3(al::PH_THREADS), 0, (hipStream_t)stream, (const al::PhaserJob *)nullptr, job);
   return check_launch("k_fx_phaser");
+}
+
+// ---- batched FX launches: one workgroup per job, the jobs of one kind in one grid
+namespace {
+int64_t fxb_desc_bytes(int32_t kind) {
+  switch (kind) {
+    case AL_FXB_SOS: return (int64_t)sizeof(al::SosJob);
+    case AL_FXB_CHORUS: return (int64_t)sizeof(al::ChorusJob);
+    case AL_FXB_PHASER: return (int64_t)sizeof(al::PhaserJob);
+    case AL_FXB_DEEMPH: return (int64_t)sizeof(al::DeemphJob);
+    default: return -1;
+  }
+}
+
+// the last error, with the job it belongs to in front
+int fail_job(int rc, int32_t job) {
+  char msg[sizeof(g_err)];
+  snprintf(msg, sizeof(msg), "al_fx_batch_pack: job %d: %.200s", job, g_err);
+  return fail(rc, msg);
+}
+
+struct FxRange {
+  const float *src, *dst;
+  int64_t n;
+};
+}  // namespace
+
+int64_t al_fx_batch_desc_bytes(int32_t kind) { return fxb_desc_bytes(kind); }
+
+int al_fx_batch_pack(int32_t kind, const void *jobs, int32_t count, void *host_table) {
+  if (fxb_desc_bytes(kind) < 0) return fail(AL_E_BADARG, "al_fx_batch_pack: unknown kind");
+  if (!jobs || !host_table) return fail(AL_E_BADARG, "al_fx_batch_pack: null pointer");
+  if (count < 1) return fail(AL_E_BADARG, "al_fx_batch_pack: count must be >= 1");
+  for (int32_t i = 0; i < count; ++i) {
+    int rc = AL_OK;
+    if (kind == AL_FXB_SOS) {
+      const al_fx_sos_job &j = static_cast<const al_fx_sos_job *>(jobs)[i];
+      rc = sos_prepare(j.src, j.dst, j.n, j.sos, j.n_sections, static_cast<al::SosJob *>(host_table) + i);
+    } else if (kind == AL_FXB_DEEMPH) {
+      const al_fx_deemph_job &j = static_cast<const al_fx_deemph_job *>(jobs)[i];
+      rc = deemph_prepare(j.src, j.dst, j.n, j.coef, static_cast<al::DeemphJob *>(host_table) + i);
+    } else {
+      const al_fx_mod_job &j = static_cast<const al_fx_mod_job *>(jobs)[i];
+      if (kind == AL_FXB_CHORUS) {
+        rc = chorus_prepare(j.src, j.dst, j.n, j.fs, j.rate_hz, j.depth, j.centre, j.feedback, j.mix,
+                            static_cast<al::ChorusJob *>(host_table) + i);
+        if (!rc && j.feedback == 0.0)
+          rc = fail(AL_E_BADARG, "al_fx_chorus: feedback == 0 runs grid-wide (k_fx_chorus_ff): not a batch job");
+      } else {
+        rc = phaser_prepare(j.src, j.dst, j.n, j.fs, j.rate_hz, j.depth, j.centre, j.feedback, j.mix,
+                            static_cast<al::PhaserJob *>(host_table) + i);
+      }
+    }
+    if (rc) return fail_job(rc, i);
+  }
+  // the workgroups run concurrently: no job may write where another reads or writes (src, dst, n lead every job struct)
+  const size_t stride = kind == AL_FXB_SOS ? sizeof(al_fx_sos_job) : kind == AL_FXB_DEEMPH ? sizeof(al_fx_deemph_job) : sizeof(al_fx_mod_job);
+  auto range = [&](int32_t i) { return reinterpret_cast<const FxRange *>(static_cast<const char *>(jobs) + stride * i); };
+  for (int32_t i = 0; i < count; ++i)
+    for (int32_t k = 0; k < count; ++k) {
+      const FxRange *a = range(i), *b = range(k);
+      if (k == i || !(fx_ranges_overlap(a->dst, a->n, b->src, b->n) || fx_ranges_overlap(a->dst, a->n, b->dst, b->n))) continue;
+      char msg[160];
+      snprintf(msg, sizeof(msg), "al_fx_batch_pack: job %d: dst overlaps src or dst of job %d (the jobs run concurrently)", i, k);
+      return fail(AL_E_BADARG, msg);
+    }
+  return AL_OK;
+}
+
+int al_fx_batch_launch(int32_t kind, const void *device_table, int32_t count, al_stream_t stream) {
+  if (fxb_desc_bytes(kind) < 0) return fail(AL_E_BADARG, "al_fx_batch_launch: unknown kind");
+  if (!device_table || count < 1) return fail(AL_E_BADARG, "al_fx_batch_launch: needs a table and count >= 1");
+  switch (kind) {
+    case AL_FXB_SOS:
+      hipLaunchKernelGGL(al::k_fx_sos, dim3((unsigned)count), dim3(al::SOS_THREADS), 0, (hipStream_t)stream, static_cast<const al::SosJob *>(device_table), al::SosJob{});
+      return check_launch("k_fx_sos");
+    case AL_FXB_CHORUS:
+      hipLaunchKernelGGL(al::k_fx_chorus_fb, dim3((unsigned)count), dim3(al::CHO_THREADS), 0, (hipStream_t)stream, static_cast<const al::ChorusJob *>(device_table), al::ChorusJob{});
+      return check_launch("k_fx_chorus_fb");
+    case AL_FXB_PHASER:
+      hipLaunchKernelGGL(al::k_fx_phaser, dim3((unsigned)count), dim3(al::PH_THREADS), 0, (hipStream_t)stream, static_cast<const al::PhaserJob *>(device_table), al::PhaserJob{});
+      return check_launch("k_fx_phaser");
+    default:
+      hipLaunchKernelGGL(al::k_fx_deemph, dim3((unsigned)count), dim3(1024), 0, (hipStream_t)stream, static_cast<const al::DeemphJob *>(device_table), al::DeemphJob{});
+      return check_launch("k_fx_deemph");
+  }
 }
 
 // ---- arbitrary-length inverse real FFT (ambience)

@@ -115,24 +115,46 @@ __device__ inline void sos_carry(double &e1, double &e2, const double *phi, doub
   __syncthreads();
 }
 
-// src may equal dst: every tile is read completely before any of it is written back.
-__global__ __launch_bounds__(1024) void k_fx_sos(const float *src, float *dst, int64_t n, int64_t run, SosArgs a) {
+// One clip's launch: what al_fx_sos derives from its arguments.  A batched launch (al_fx_batch_launch) reads one per workgroup
+// from a table in device memory, a single-clip launch carries it by value.
+struct SosJob {
+  const float *src;
+  float *dst;
+  int64_t n, run;
+  SosArgs a;
+};
+
+// {b0 b1 b2 a1 a2, Phi} per section into LDS.  Constant indices only: a job passed by value stays out of scratch.
+__device__ __forceinline__ void sos_stage_coef(const SosArgs &a, double *coef) {
+#pragma unroll
+  for (int i = 0; i < AL_SOS_MAX_SECTIONS * 5; ++i) coef[i / 5 * 9 + i % 5] = a.c[i / 5][i % 5];
+#pragma unroll
+  for (int i = 0; i < AL_SOS_MAX_SECTIONS * 4; ++i) coef[i / 4 * 9 + 5 + i % 4] = a.phi[i / 4][i % 4];
+}
+
+// Workgroup b filters the clip of job b: table[b], or `one` when table == nullptr (grid of 1).  The same instantiation either
+// way, so a batch renders the bits of the single-clip launches.  src may equal dst: every tile is read completely before any
+// of it is written back.
+__global__ __launch_bounds__(1024) void k_fx_sos(const SosJob *__restrict__ table, SosJob one) {
   __shared__ float tile[SOS_THREADS * SOS_PITCH];
   __shared__ double carry[2 * SOS_THREADS];
   __shared__ double coef[AL_SOS_MAX_SECTIONS * 9];   // {b0 b1 b2 a1 a2, Phi} per section
-  if (threadIdx.x == 0) {   // constant indices only: the kernel arguments stay out of scratch
-#pragma unroll
-    for (int i = 0; i < AL_SOS_MAX_SECTIONS * 5; ++i) coef[i / 5 * 9 + i % 5] = a.c[i / 5][i % 5];
-#pragma unroll
-    for (int i = 0; i < AL_SOS_MAX_SECTIONS * 4; ++i) coef[i / 4 * 9 + 5 + i % 4] = a.phi[i / 4][i % 4];
+  const SosJob *job = table ? table + blockIdx.x : nullptr;
+  const float *src = job ? job->src : one.src;
+  float *dst = job ? job->dst : one.dst;
+  const int64_t n = job ? job->n : one.n, run = job ? job->run : one.run;
+  const int n_sections = job ? job->a.n_sections : one.a.n_sections;
+  if (threadIdx.x == 0) {
+    if (job) sos_stage_coef(job->a, coef);
+    else sos_stage_coef(one.a, coef);
   }
   __syncthreads();
   double s1 = 0.0, s2 = 0.0, t1 = 0.0, t2 = 0.0;
   sos_sweep(src, dst, n, run, coef, s1, s2, nullptr, t1, t2, false, tile);   // zero-state end states of section 0
-  for (int k = 0; k < a.n_sections; ++k) {
+  for (int k = 0; k < n_sections; ++k) {
     sos_carry(s1, s2, coef + 9 * k + 5, carry);
     t1 = t2 = 0.0;
-    sos_sweep(k == 0 ? src : dst, dst, n, run, coef + 9 * k, s1, s2, k + 1 < a.n_sections ? coef + 9 * (k + 1) : nullptr, t1,
+    sos_sweep(k == 0 ? src : dst, dst, n, run, coef + 9 * k, s1, s2, k + 1 < n_sections ? coef + 9 * (k + 1) : nullptr, t1,
               t2, true, tile);
     s1 = t1;
     s2 = t2;

@@ -33,7 +33,8 @@ extern "C" {
  * al_plan_batch_flags -- the dispatch policy (layout + accumulate flags per chunk) moves from the hosts into the library --
  * and al_scale_rows_f64; the opt-in fused kernels of versions 2-5 (AL_FLAG_FUSED_STATIC / _FUSED_MOVING / _FUSED_NJ5,
  * al_mac_synthesis, al_fused_supported, al_moving_fused_supported, the quad layout at B = 8192, the fused_moving argument of
- * al_plan_emitter_parts) are gone: measured 20-35 % slower than the stored-spectra path, profiles/r05c_fused_ab.txt). */
+ * al_plan_emitter_parts) are gone: measured 20-35 % slower than the stored-spectra path, profiles/r05c_fused_ab.txt).  The
+ * batched FX entries (al_fx_batch_*) were added within version 6: new entry points only, no struct or entry changed. */
 #define AL_ABI_VERSION 6
 
 #define AL_OK 0
@@ -319,6 +320,50 @@ int al_fx_chorus(const float *src, float *dst, int64_t n, double fs, double rate
                  double feedback, double mix, al_stream_t stream);
 int al_fx_phaser(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_frequency_hz,
                  double feedback, double mix, al_stream_t stream);
+/* Batched FX launches: the one-workgroup scans (al_fx_sos, al_fx_chorus with feedback > 0, al_fx_phaser, the AL_FX_DEEMPH op
+ * of al_fx_apply) on MANY clips in ONE launch, workgroup b running job b exactly as the single-clip entry would (the same
+ * kernel, which a single-clip call launches with a grid of 1: the samples are bit-identical).  Three steps:
+ *   1. al_fx_batch_pack, on the host, touching no device: checks every job with the checks of its single-clip entry, derives
+ *      what that entry derives (run lengths, the transition powers of the sections, the Chorus block, the Phaser constants) and
+ *      writes `count` packed descriptors of al_fx_batch_desc_bytes(kind) bytes each to the HOST buffer host_table;
+ *   2. the caller copies host_table to device memory (stream-ordered before step 3);
+ *   3. al_fx_batch_launch enqueues the one launch of `count` workgroups reading that device table.
+ * The job structs: src / dst are device pointers to n float32 samples; the scalars are those of the single-clip entry
+ * (al_fx_mod_job.centre: centre_delay_ms for AL_FXB_CHORUS, centre_frequency_hz for AL_FXB_PHASER); al_fx_sos_job.sos is a HOST
+ * array of n_sections rows {b0, b1, b2, a0, a1, a2}, read by al_fx_batch_pack only.
+ * al_fx_batch_pack returns AL_E_BADARG for an unknown kind, a null pointer or count < 1, and, with al_last_error() naming the
+ * job ("al_fx_batch_pack: job 3: ..."), for anything the single-clip entry refuses, for an AL_FXB_CHORUS job with
+ * feedback == 0 (that case runs grid-wide through al_fx_chorus) and for a job whose dst range overlaps the src or dst range of
+ * ANOTHER job (the workgroups run concurrently; within a job dst == src stays allowed for AL_FXB_SOS, and only there).
+ * al_fx_batch_desc_bytes returns -1 for an unknown kind.  The packed layout is private to the library build that wrote it. */
+#define AL_FXB_SOS 1
+#define AL_FXB_CHORUS 2
+#define AL_FXB_PHASER 3
+#define AL_FXB_DEEMPH 4
+typedef struct al_fx_sos_job {
+  const float *src;
+  float *dst;
+  int64_t n;
+  const double *sos;
+  int32_t n_sections;
+  int32_t reserved;
+} al_fx_sos_job;
+typedef struct al_fx_mod_job {
+  const float *src;
+  float *dst;
+  int64_t n;
+  double fs, rate_hz, depth, centre, feedback, mix;
+} al_fx_mod_job;
+typedef struct al_fx_deemph_job {
+  const float *src;
+  float *dst;
+  int64_t n;
+  float coef;
+  int32_t reserved;
+} al_fx_deemph_job;
+int64_t al_fx_batch_desc_bytes(int32_t kind);
+int al_fx_batch_pack(int32_t kind, const void *jobs, int32_t count, void *host_table);
+int al_fx_batch_launch(int32_t kind, const void *device_table, int32_t count, al_stream_t stream);
 /* ---- Ambience (A12): Timmer-Koenig (1/f)^beta noise, audiblelight/ambience.py:271-375.
  * The host draws the two standard-normal sets with numpy's default_rng(seed) (PCG64 + ziggurat, ambience.py:351-356:
  * the reference's RNG stream is data-dependent and is not re-implemented on the device); everything after the draws
