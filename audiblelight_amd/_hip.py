@@ -117,6 +117,16 @@ class AlFxDeemphJob(ct.Structure):    # al_fx_deemph_job
     _fields_ = [("src", ct.c_void_p), ("dst", ct.c_void_p), ("n", ct.c_int64), ("coef", ct.c_float), ("reserved", ct.c_int32)]
 
 
+class AlFxCompressorJob(ct.Structure):    # al_fx_compressor_job
+    _fields_ = [("src", ct.c_void_p), ("dst", ct.c_void_p), ("n", ct.c_int64)] + \
+               [(n, ct.c_double) for n in ("fs", "threshold_db", "ratio", "attack_ms", "release_ms")]
+
+
+class AlFxLimiterJob(ct.Structure):       # al_fx_limiter_job
+    _fields_ = [("src", ct.c_void_p), ("dst", ct.c_void_p), ("n", ct.c_int64)] + \
+               [(n, ct.c_double) for n in ("fs", "threshold_db", "release_ms")]
+
+
 class HipError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -177,6 +187,8 @@ SYMBOLS = {
     "al_fx_delay": (ct.c_int, [_P, _P, ct.c_int64, ct.c_int64, ct.c_float, ct.c_float, _S]),
     "al_fx_chorus": (ct.c_int, [_P, _P, ct.c_int64] + [ct.c_double] * 6 + [_S]),
     "al_fx_phaser": (ct.c_int, [_P, _P, ct.c_int64] + [ct.c_double] * 6 + [_S]),
+    "al_fx_compressor": (ct.c_int, [_P, _P, ct.c_int64] + [ct.c_double] * 5 + [_S]),
+    "al_fx_limiter": (ct.c_int, [_P, _P, ct.c_int64] + [ct.c_double] * 3 + [_S]),
     "al_fx_batch_desc_bytes": (ct.c_int64, [ct.c_int32]),
     "al_fx_batch_pack": (ct.c_int, [ct.c_int32, _P, ct.c_int32, _P]),
     "al_fx_batch_launch": (ct.c_int, [ct.c_int32, _P, ct.c_int32, _S]),
@@ -204,7 +216,10 @@ FRAMES_F32, FRAMES_PCM16 = 0, 1
 FX_GAIN, FX_INVERT, FX_REVERSE, FX_FADE, FX_CLIP, FX_TANH, FX_BITCRUSH, FX_PREEMPH, FX_DEEMPH = range(1, 10)
 SOS_MAX_SECTIONS = 16   # AL_SOS_MAX_SECTIONS: second-order sections per al_fx_sos call
 FXB_SOS, FXB_CHORUS, FXB_PHASER, FXB_DEEMPH = 1, 2, 3, 4   # AL_FXB_*: the kinds of a batched FX launch (al_fx_batch_*)
-FXB_JOBS = {FXB_SOS: AlFxSosJob, FXB_CHORUS: AlFxModJob, FXB_PHASER: AlFxModJob, FXB_DEEMPH: AlFxDeemphJob}
+FXB_COMPRESSOR, FXB_LIMITER = 6, 7                         # 5 is not a kind
+DYN_TILE = 1024         # samples per tile of k_fx_dynamics (csrc/al_dynfx.h DYN_TILE)
+FXB_JOBS = {FXB_SOS: AlFxSosJob, FXB_CHORUS: AlFxModJob, FXB_PHASER: AlFxModJob, FXB_DEEMPH: AlFxDeemphJob,
+            FXB_COMPRESSOR: AlFxCompressorJob, FXB_LIMITER: AlFxLimiterJob}
 FADE_SHAPES = {"linear": 0, "exponential": 1, "logarithmic": 2, "quarter_sine": 3, "half_sine": 4, "none": 5}
 
 

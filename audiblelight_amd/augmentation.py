@@ -6,13 +6,15 @@ TimeWarpSilence / Duplicate / Remove / Reverse, the linear time-invariant filter
 HighpassFilter, LowShelfFilter, HighShelfFilter and MultibandEqualizer (cascades of second-order
 sections, one ``al_fx_sos`` launch each), the delay and modulation FX Delay, Chorus and Phaser
 (linear recursions with feedback, one ``al_fx_delay`` / ``al_fx_chorus`` / ``al_fx_phaser`` launch
-each) and the peak normalisation of ``Event.load_audio``.  The FX whose kernel is a one-workgroup scan (the filters,
-Chorus with feedback, Phaser, Deemphasis) also describe their launch as a job (``batch_job``), and ``run_chains`` runs the
-chains of a whole scene together: the pending scans of one kind on all clips go into ONE launch (``al_fx_batch_pack`` /
+each), the dynamics FX Compressor and Limiter (an envelope whose coefficient depends on its state: one wave walks the clip,
+one ``al_fx_compressor`` / ``al_fx_limiter`` launch each) and the peak normalisation of ``Event.load_audio``.  The FX whose
+kernel runs one clip on one workgroup (the filters, Chorus with feedback, Phaser, Deemphasis, Compressor, Limiter) also
+describe their launch as a job (``batch_job``), and ``run_chains`` runs the
+chains of a whole scene together: the pending jobs of one kind on all clips go into ONE launch (``al_fx_batch_pack`` /
 ``al_fx_batch_launch``, one workgroup per clip) with the samples of the per-clip launches, bit for bit (DESIGN.md "Batched
 FX launches").  The other stateful pedalboard effects
-(dynamics: Compressor, Limiter; codecs: GSMFullRateCompressor, MP3Compressor; time-stretch:
-PitchShift, SpeedUp) stay on the host with the reference implementation: out of scope (SURVEY.md
+(codecs: GSMFullRateCompressor, MP3Compressor; time-stretch:
+PitchShift, SpeedUp) are not part of this package: out of scope (SURVEY.md
 section 2, row 3b).
 
 Definitions for effects whose reference arithmetic lives in un-vendored third-party wheels
@@ -21,7 +23,7 @@ Distortion = tanh(x*10^(dB/20)); Bitcrush = rint(x*2^bits)/2^bits (pedalboard 0.
 Preemphasis / Deemphasis = librosa 0.11 ``effects.preemphasis`` / ``deemphasis`` including their
 linear-extrapolation initial state.  The filter FX: see ``_FilterFX`` (first-order low/high-pass, Audio EQ
 Cookbook shelves and peaks, float64 coefficients and state, constant gains at degenerate cutoffs).  The delay and
-modulation FX: see ``Delay``, ``Chorus`` and ``Phaser``.
+modulation FX: see ``Delay``, ``Chorus`` and ``Phaser``.  The dynamics FX: see ``Compressor`` and ``Limiter``.
 """
 from __future__ import annotations
 
@@ -853,7 +855,67 @@ class Phaser(_Modulation):
         super().__init__(sample_rate, rate_hz, depth, centre_frequency_hz, feedback, mix)
 
 
+class _DynamicsFX(_DelayModFX):
+    """Dynamics FX: one launch of ``k_fx_dynamics`` (one wave walks the clip's envelope), out of place; as a job of a batched
+    launch the clips of a scene are walked side by side."""
+
+    ENTRY = ""
+    KIND = 0                        # _hip.FXB_* of the batched launch
+    MIN_THRESHOLD_DB, MAX_THRESHOLD_DB = -40, -20
+    MIN_RELEASE, MAX_RELEASE = 50, 1100
+
+    def _fields(self) -> dict:
+        return dict(fs=float(self.sample_rate), **{k: float(v) for k, v in self.params.items()})
+
+    def batch_job(self, clip):
+        return self.KIND, self._fields()
+
+    def launch(self, clip, dst):
+        r = clip.r
+        r.lib.call(self.ENTRY, r.mem.ptr(clip.buf), r.mem.ptr(dst), clip.n, *self._fields().values(), r.mem.stream())
+
+
+class Compressor(_DynamicsFX):
+    """JUCE's ``dsp::Compressor`` as pedalboard 0.9.17 wraps it (augmentation.py:663-743), restated by definition and not
+    checked against a running pedalboard.  cte(ms) = 0 when ms < 1e-3, else exp(-2 pi 1000 / (ms fs)); cA = cte(attack_ms),
+    cR = cte(release_ms); T = 10^(threshold_db / 20).  Per sample, with e = 0 before the clip: a = |x|, c = cA when a > e, else
+    cR, e <- a + c (e - a), g = 1 when e < T, else (e / T)^(1 / ratio - 1), y = g x.  float64 arithmetic and state (JUCE:
+    float32).  ``ratio`` below 1 is refused."""
+
+    RATIOS = [4, 8, 12, 20]         # the UREI 1176's
+    MIN_ATTACK, MAX_ATTACK = 1, 100
+    ENTRY = "al_fx_compressor"
+    KIND = _hip.FXB_COMPRESSOR
+
+    def __init__(self, sample_rate=config.SAMPLE_RATE, threshold_db=None, ratio=None, attack_ms=None, release_ms=None):
+        super().__init__(sample_rate)
+        self.threshold_db = -abs(int(_sample(threshold_db, self.MIN_THRESHOLD_DB, self.MAX_THRESHOLD_DB)))
+        self.ratio = int(_positive(np.random.choice(self.RATIOS) if ratio is None else _sample(ratio, 0, 0)))
+        if self.ratio < 1:
+            raise ValueError(f"Expected a ratio of at least 1 but got {self.ratio}")
+        self.attack_ms = _positive(_sample(attack_ms, self.MIN_ATTACK, self.MAX_ATTACK))
+        self.release_ms = _positive(_sample(release_ms, self.MIN_RELEASE, self.MAX_RELEASE))
+        self.params = dict(threshold_db=self.threshold_db, ratio=self.ratio, attack_ms=self.attack_ms,
+                           release_ms=self.release_ms)
+
+
+class Limiter(_DynamicsFX):
+    """JUCE's ``dsp::Limiter`` as pedalboard 0.9.17 wraps it (augmentation.py:871-924), restated by definition and not checked
+    against a running pedalboard: a compressor stage (see ``Compressor``) at (-10 dB, ratio 4, 2 ms, 200 ms), a second one on
+    its output at (threshold_db, ratio 1000, cA = 0, release_ms), then y = clamp(G y2, -1, 1) with
+    G = 10^(10 (1 - 1/4) / 40) 10^(-threshold_db / 20).  JUCE's smoothed output gain starts at its target (no ramp)."""
+
+    ENTRY = "al_fx_limiter"
+    KIND = _hip.FXB_LIMITER
+
+    def __init__(self, sample_rate=config.SAMPLE_RATE, threshold_db=None, release_ms=None):
+        super().__init__(sample_rate)
+        self.threshold_db = -abs(int(_sample(threshold_db, self.MIN_THRESHOLD_DB, self.MAX_THRESHOLD_DB)))
+        self.release_ms = _positive(_sample(release_ms, self.MIN_RELEASE, self.MAX_RELEASE))
+        self.params = dict(threshold_db=self.threshold_db, release_ms=self.release_ms)
+
+
 ALL_EVENT_AUGMENTATIONS = [Gain, Invert, Reverse, Fade, Clipping, Distortion, Bitcrush, Preemphasis, Deemphasis,
                            TimeWarpSilence, TimeWarpDuplicate, TimeWarpRemove, TimeWarpReverse,
                            LowpassFilter, HighpassFilter, LowShelfFilter, HighShelfFilter, MultibandEqualizer,
-                           Delay, Chorus, Phaser]
+                           Delay, Chorus, Phaser, Compressor, Limiter]

@@ -1,7 +1,7 @@
 // C ABI of the MI355X synthesis path (gfx950 only): every extern "C" entry point of include/audiblelight_hip.h that launches
 // device code, each one argument validation plus launch.  No kernel and no launch planning lives here: kernels, their device
 // helpers and the host-side choice of instantiation and grid are in the per-domain headers included below (al_mac.h accumulate,
-// al_levels.h level scalars, al_mixdown.h, al_rows.h, al_clipfx.h / al_sos.h / al_delayfx.h FX, al_ingest.h, al_bigfft.h, al_stft.h);
+// al_levels.h level scalars, al_mixdown.h, al_rows.h, al_clipfx.h / al_sos.h / al_delayfx.h / al_dynfx.h FX, al_ingest.h, al_bigfft.h, al_stft.h);
 // the FFT kernels of the pipeline are the other translation unit, al_transforms.hip.  See DESIGN.md for the data layout and
 // per-kernel rooflines.
 //
@@ -22,6 +22,7 @@
 #include "al_bigfft.h"
 #include "al_clipfx.h"
 #include "al_delayfx.h"
+#include "al_dynfx.h"
 #include "al_fft.h"
 #include "al_ingest.h"
 #include "al_levels.h"
@@ -412,6 +413,62 @@ int phaser_prepare(const float *src, float *dst, int64_t n, double fs, double ra
   a.wet = m;
   return AL_OK;
 }
+// dynamics FX: out of place; the checks both entries share, then the stages
+constexpr double DYN_TWO_PI = 6.283185307179586476925286766559;
+
+// cte(ms): the one-pole coefficient of a time constant, 0 below a microsecond (JUCE's BallisticsFilter)
+double dyn_cte(double ms, double fs) { return ms < 1e-3 ? 0.0 : exp(-DYN_TWO_PI * 1000.0 / (ms * fs)); }
+
+al::DynStage dyn_stage(double threshold_db, double ratio, double cA, double cR) {
+  const double T = pow(10.0, threshold_db / 20.0);
+  return al::DynStage{T, 1.0 / T, 1.0 / ratio - 1.0, cA, cR};
+}
+
+int dyn_check(const char *fn, const float *src, const float *dst, int64_t n, double fs, double threshold_db, bool limiter,
+              double ratio, double attack_ms, double release_ms) {
+  if (int e = fx_check(fn, src, dst, n, nullptr, nullptr, 0)) return e;
+  char msg[200];
+  const char *why = nullptr;
+  if (!isfinite(fs) || !(fs > 0.0)) why = "fs must be finite and > 0";
+  else if (!isfinite(threshold_db) || !(threshold_db > -200.0)) why = "threshold_db must be finite and > -200";
+  else if (limiter && !(threshold_db < 100.0)) why = "threshold_db must be < 100";
+  else if (!isfinite(ratio) || !(ratio >= 1.0)) why = "ratio must be finite and >= 1";
+  else if (!isfinite(attack_ms) || attack_ms < 0.0) why = "attack_ms must be finite and >= 0";
+  else if (!isfinite(release_ms) || release_ms < 0.0) why = "release_ms must be finite and >= 0";
+  if (!why) return AL_OK;
+  snprintf(msg, sizeof(msg), "%s: %s", fn, why);
+  return fail(AL_E_BADARG, msg);
+}
+
+int compressor_prepare(const float *src, float *dst, int64_t n, double fs, double threshold_db, double ratio, double attack_ms,
+                       double release_ms, al::DynJob *job) {
+  if (int e = dyn_check("al_fx_compressor", src, dst, n, fs, threshold_db, false, ratio, attack_ms, release_ms)) return e;
+  memset(job, 0, sizeof(*job));
+  job->src = src;
+  job->dst = dst;
+  job->n = n;
+  job->n_stages = 1;
+  job->st[0] = dyn_stage(threshold_db, ratio, dyn_cte(attack_ms, fs), dyn_cte(release_ms, fs));
+  job->st[1] = job->st[0];   // not walked
+  job->out_gain = 1.0;
+  job->ceiling = INFINITY;
+  return AL_OK;
+}
+
+// JUCE's dsp::Limiter: a fixed first compressor, the caller's second one (attack 0.001 ms: cA = 0), the make-up gain, the clamp
+int limiter_prepare(const float *src, float *dst, int64_t n, double fs, double threshold_db, double release_ms, al::DynJob *job) {
+  if (int e = dyn_check("al_fx_limiter", src, dst, n, fs, threshold_db, true, 1000.0, 0.0, release_ms)) return e;
+  memset(job, 0, sizeof(*job));
+  job->src = src;
+  job->dst = dst;
+  job->n = n;
+  job->n_stages = 2;
+  job->st[0] = dyn_stage(-10.0, 4.0, dyn_cte(2.0, fs), dyn_cte(200.0, fs));
+  job->st[1] = dyn_stage(threshold_db, 1000.0, 0.0, dyn_cte(release_ms, fs));
+  job->out_gain = pow(10.0, 10.0 * (1.0 - 1.0 / 4.0) / 40.0) * pow(10.0, -threshold_db / 20.0);
+  job->ceiling = 1.0;
+  return AL_OK;
+}
 }  // namespace
 
 int al_fx_apply(int op, const float *src, float *dst, int64_t n, const float *params, const int32_t *iparams,
@@ -485,6 +542,21 @@ int al_fx_phaser(const float *src, float *dst, int64_t n, double fs, double rate
   return check_launch("k_fx_phaser");
 }
 
+int al_fx_compressor(const float *src, float *dst, int64_t n, double fs, double threshold_db, double ratio, double attack_ms,
+                     double release_ms, al_stream_t stream) {
+  al::DynJob job;
+  if (int rc = compressor_prepare(src, dst, n, fs, threshold_db, ratio, attack_ms, release_ms, &job)) return rc;
+  hipLaunchKernelGGL(al::k_fx_dynamics, dim3(1), dim3(al::DYN_LANES), 0, (hipStream_t)stream, (const al::DynJob *)nullptr, job);
+  return check_launch("k_fx_dynamics");
+}
+
+int al_fx_limiter(const float *src, float *dst, int64_t n, double fs, double threshold_db, double release_ms, al_stream_t stream) {
+  al::DynJob job;
+  if (int rc = limiter_prepare(src, dst, n, fs, threshold_db, release_ms, &job)) return rc;
+  hipLaunchKernelGGL(al::k_fx_dynamics, dim3(1), dim3(al::DYN_LANES), 0, (hipStream_t)stream, (const al::DynJob *)nullptr, job);
+  return check_launch("k_fx_dynamics");
+}
+
 // ---- batched FX launches: one workgroup per job, the jobs of one kind in one grid
 namespace {
 int64_t fxb_desc_bytes(int32_t kind) {
@@ -493,6 +565,8 @@ int64_t fxb_desc_bytes(int32_t kind) {
     case AL_FXB_CHORUS: return (int64_t)sizeof(al::ChorusJob);
     case AL_FXB_PHASER: return (int64_t)sizeof(al::PhaserJob);
     case AL_FXB_DEEMPH: return (int64_t)sizeof(al::DeemphJob);
+    case AL_FXB_COMPRESSOR:
+    case AL_FXB_LIMITER: return (int64_t)sizeof(al::DynJob);
     default: return -1;
   }
 }
@@ -524,6 +598,13 @@ int al_fx_batch_pack(int32_t kind, const void *jobs, int32_t count, void *host_t
     } else if (kind == AL_FXB_DEEMPH) {
       const al_fx_deemph_job &j = static_cast<const al_fx_deemph_job *>(jobs)[i];
       rc = deemph_prepare(j.src, j.dst, j.n, j.coef, static_cast<al::DeemphJob *>(host_table) + i);
+    } else if (kind == AL_FXB_COMPRESSOR) {
+      const al_fx_compressor_job &j = static_cast<const al_fx_compressor_job *>(jobs)[i];
+      rc = compressor_prepare(j.src, j.dst, j.n, j.fs, j.threshold_db, j.ratio, j.attack_ms, j.release_ms,
+                              static_cast<al::DynJob *>(host_table) + i);
+    } else if (kind == AL_FXB_LIMITER) {
+      const al_fx_limiter_job &j = static_cast<const al_fx_limiter_job *>(jobs)[i];
+      rc = limiter_prepare(j.src, j.dst, j.n, j.fs, j.threshold_db, j.release_ms, static_cast<al::DynJob *>(host_table) + i);
     } else {
       const al_fx_mod_job &j = static_cast<const al_fx_mod_job *>(jobs)[i];
       if (kind == AL_FXB_CHORUS) {
@@ -539,7 +620,11 @@ int al_fx_batch_pack(int32_t kind, const void *jobs, int32_t count, void *host_t
     if (rc) return fail_job(rc, i);
   }
   // the workgroups run concurrently: no job may write where another reads or writes (src, dst, n lead every job struct)
-  const size_t stride = kind == AL_FXB_SOS ? sizeof(al_fx_sos_job) : kind == AL_FXB_DEEMPH ? sizeof(al_fx_deemph_job) : sizeof(al_fx_mod_job);
+  const size_t stride = kind == AL_FXB_SOS          ? sizeof(al_fx_sos_job)
+                        : kind == AL_FXB_DEEMPH     ? sizeof(al_fx_deemph_job)
+                        : kind == AL_FXB_COMPRESSOR ? sizeof(al_fx_compressor_job)
+                        : kind == AL_FXB_LIMITER    ? sizeof(al_fx_limiter_job)
+                                                    : sizeof(al_fx_mod_job);
   auto range = [&](int32_t i) { return reinterpret_cast<const FxRange *>(static_cast<const char *>(jobs) + stride * i); };
   for (int32_t i = 0; i < count; ++i)
     for (int32_t k = 0; k < count; ++k) {
@@ -565,6 +650,10 @@ int al_fx_batch_launch(int32_t kind, const void *device_table, int32_t count, al
     case AL_FXB_PHASER:
       hipLaunchKernelGGL(al::k_fx_phaser, dim3((unsigned)count), dim3(al::PH_THREADS), 0, (hipStream_t)stream, static_cast<const al::PhaserJob *>(device_table), al::PhaserJob{});
       return check_launch("k_fx_phaser");
+    case AL_FXB_COMPRESSOR:
+    case AL_FXB_LIMITER:
+      hipLaunchKernelGGL(al::k_fx_dynamics, dim3((unsigned)count), dim3(al::DYN_LANES), 0, (hipStream_t)stream, static_cast<const al::DynJob *>(device_table), al::DynJob{});
+      return check_launch("k_fx_dynamics");
     default:
       hipLaunchKernelGGL(al::k_fx_deemph, dim3((unsigned)count), dim3(1024), 0, (hipStream_t)stream, static_cast<const al::DeemphJob *>(device_table), al::DeemphJob{});
       return check_launch("k_fx_deemph");

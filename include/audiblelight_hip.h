@@ -320,8 +320,29 @@ int al_fx_chorus(const float *src, float *dst, int64_t n, double fs, double rate
                  double feedback, double mix, al_stream_t stream);
 int al_fx_phaser(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_frequency_hz,
                  double feedback, double mix, al_stream_t stream);
+/* Dynamics FX (Compressor, Limiter; augmentation.py:663-743, 871-924).  pedalboard is not vendored: these restate JUCE's
+ * dsp::Compressor, dsp::BallisticsFilter (peak mode) and dsp::Limiter as pedalboard 0.9.17 wraps them and as this project reads
+ * them, unchecked against a running pedalboard (DESIGN.md "Dynamics FX").  src / dst: float32 clips of n samples; every state
+ * starts at zero; out of place only (dst must not overlap src).  All arithmetic and state are float64 (JUCE: float32).
+ *
+ * Coefficients: cte(ms) = 0 when ms < 1e-3, else exp(-2 pi 1000 / (ms fs)); cA = cte(attack_ms), cR = cte(release_ms).
+ * A compressor stage (T_dB, ratio, attack_ms, release_ms), T = 10^(T_dB / 20), e[-1] = 0:
+ *   a_t = |x_t|;  c_t = cA when a_t > e[t-1], else cR;  e_t = a_t + c_t (e[t-1] - a_t);
+ *   g_t = 1 when e_t < T, else (e_t / T)^(1 / ratio - 1);  y_t = g_t x_t.
+ * al_fx_compressor: one stage.
+ * al_fx_limiter: stage 1 = (-10 dB, 4, 2 ms, 200 ms); stage 2 on its output = (threshold_db, 1000, cA = 0, release_ms) (JUCE's
+ *   0.001 ms attack: exp(-2 pi 1e6 / fs) is 0 in any case); y = clamp(G y2, -1, 1), G = 10^(10 (1 - 1/4) / 40) 10^(-threshold_db / 20).
+ *   JUCE's smoothed output gain starts at its target (no ramp).
+ * The envelope's coefficient depends on its state, so the time axis is walked serially: one wave per clip (a batched launch,
+ * below, runs a scene's clips side by side).
+ * AL_E_BADARG, with al_last_error() naming the entry and the reason, for a null pointer, n < 1, dst overlapping src, fs not
+ * finite or <= 0, threshold_db not finite or <= -200 (JUCE maps it to a zero threshold, whose inverse is infinite), for the
+ * limiter threshold_db >= 100, ratio not finite or < 1, attack_ms / release_ms not finite or < 0. */
+int al_fx_compressor(const float *src, float *dst, int64_t n, double fs, double threshold_db, double ratio, double attack_ms,
+                     double release_ms, al_stream_t stream);
+int al_fx_limiter(const float *src, float *dst, int64_t n, double fs, double threshold_db, double release_ms, al_stream_t stream);
 /* Batched FX launches: the one-workgroup scans (al_fx_sos, al_fx_chorus with feedback > 0, al_fx_phaser, the AL_FX_DEEMPH op
- * of al_fx_apply) on MANY clips in ONE launch, workgroup b running job b exactly as the single-clip entry would (the same
+ * of al_fx_apply) and the one-wave walks (al_fx_compressor, al_fx_limiter) on MANY clips in ONE launch, workgroup b running job b exactly as the single-clip entry would (the same
  * kernel, which a single-clip call launches with a grid of 1: the samples are bit-identical).  Three steps:
  *   1. al_fx_batch_pack, on the host, touching no device: checks every job with the checks of its single-clip entry, derives
  *      what that entry derives (run lengths, the transition powers of the sections, the Chorus block, the Phaser constants) and
@@ -340,6 +361,9 @@ int al_fx_phaser(const float *src, float *dst, int64_t n, double fs, double rate
 #define AL_FXB_CHORUS 2
 #define AL_FXB_PHASER 3
 #define AL_FXB_DEEMPH 4
+/* 5 is not a kind: it stays refused as unknown, as it was before the dynamics kinds */
+#define AL_FXB_COMPRESSOR 6
+#define AL_FXB_LIMITER 7
 typedef struct al_fx_sos_job {
   const float *src;
   float *dst;
@@ -361,6 +385,18 @@ typedef struct al_fx_deemph_job {
   float coef;
   int32_t reserved;
 } al_fx_deemph_job;
+typedef struct al_fx_compressor_job {
+  const float *src;
+  float *dst;
+  int64_t n;
+  double fs, threshold_db, ratio, attack_ms, release_ms;
+} al_fx_compressor_job;
+typedef struct al_fx_limiter_job {
+  const float *src;
+  float *dst;
+  int64_t n;
+  double fs, threshold_db, release_ms;
+} al_fx_limiter_job;
 int64_t al_fx_batch_desc_bytes(int32_t kind);
 int al_fx_batch_pack(int32_t kind, const void *jobs, int32_t count, void *host_table);
 int al_fx_batch_launch(int32_t kind, const void *device_table, int32_t count, al_stream_t stream);
