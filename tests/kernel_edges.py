@@ -37,6 +37,11 @@ EDGE_N = (2, 255, 256, 257, 1023, 1024, 1025)
 
 
 # ----------------------------------------------------------------------------- guarded buffers
+def sentinel_bytes(n):
+    """n bytes of the repeated sentinel (np.resize(SENTINEL, n), which takes seconds at the tens of megabytes of a long fill)."""
+    return np.tile(SENTINEL, (n + 3) // 4)[:n]
+
+
 class Guarded:
     """A device buffer of n elements of `dtype` with ``guard`` (G unless given) sentinel elements on each side; ``shift`` moves
     the interior that many elements off the (at least 16-byte aligned) position it would have.  ``init`` fills the interior."""
@@ -47,7 +52,7 @@ class Guarded:
         self.lo = (guard + shift) * item
         self.hi = self.lo + self.n * item
         total = (self.hi + guard * item + 3) // 4 * 4
-        host = np.resize(SENTINEL, total)
+        host = sentinel_bytes(total)
         if init is not None:
             host[self.lo:self.hi] = np.ascontiguousarray(init, dtype=self.dtype).reshape(-1).view(np.uint8)
         self.buf = r.mem.upload(host)
@@ -58,7 +63,7 @@ class Guarded:
         """The interior, after asserting both guard bands still hold the sentinel."""
         self.r.mem.synchronize()
         raw = np.asarray(self.r.mem.download(self.buf)).view(np.uint8)
-        pattern = np.resize(SENTINEL, len(raw))
+        pattern = sentinel_bytes(len(raw))
         bad = np.flatnonzero(np.concatenate([raw[:self.lo] != pattern[:self.lo], raw[self.hi:] != pattern[self.hi:]]))
         assert bad.size == 0, f"{bad.size} guard bytes overwritten (first at byte {int(bad[0])} of the guards)"
         return raw[self.lo:self.hi].view(self.dtype).copy()

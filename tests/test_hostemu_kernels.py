@@ -10,7 +10,7 @@ import pytest
 
 from audiblelight_amd import _hip, engine, plan as planning
 from oracle import synth_oracle as orc
-from tests import hostemu
+from tests import hostemu, lane_cases as lc
 from tests.conftest import assert_parity, rel_rms, set_switch
 
 TOL = 1e-4  # BASELINE.json north_star: outputs within 1e-4 relative RMS of the float64 reference
@@ -176,3 +176,57 @@ def test_energy_only_batches_refuse_the_spectra_stages(emu):
     for call in (lambda: batch.run(), lambda: batch.run_stage("al_spectral_mac"), lambda: batch.run(stages=("al_block_synthesis",))):
         with pytest.raises(RuntimeError, match="without spectra workspaces"):
             call()
+
+
+# ----------------------------------------------------------------------------- lanes and retarget (tests/lane_cases.py)
+def _g8_scene(golden):
+    """The five-event golden scene (static and moving events) as prepare() takes it, and its mixdown plan."""
+    sr, C = 8000, 4
+    specs, clips, irs, col = [], [], [], 0
+    for i, (na, ne, st, snr, mv, dry) in enumerate(golden["g8_specs"]):
+        a = golden[f"g8_audio{i}"]
+        clips.append(a)
+        irs.append(golden[f"g8_irs{i}"])
+        specs.append(planning.EventSpec(n_samples=len(a), n_emitters=int(ne), snr=float(snr), emitter0=col,
+                                        is_moving=bool(mv), duration=len(a) / sr))
+        col += int(ne)
+    mic_ir = np.concatenate(irs, axis=1)
+    pl = planning.plan_batch(specs, n_capsules=C, ir_len=mic_ir.shape[2], sample_rate=sr, log2_block=10)
+    starts = [float(s[2]) for s in golden["g8_specs"]]
+    ends = [s + len(c) / sr for s, c in zip(starts, clips)]
+    mix = planning.plan_mixdown(starts, ends, [len(c) for c in clips], [C] * len(clips), pl.events["out_off"],
+                                list(range(len(clips))), 2.0, sr, C)
+    return pl, clips, mic_ir, mix
+
+
+@pytest.mark.parametrize("lanes", [2, 3])
+def test_emu_lanes_alternate_workspaces_and_give_the_one_chunk_bits(emu, golden, lanes):
+    """prepare(chunk_events=1, lanes=N): chunk i gets workspace i % N (own H / X / Y and zeroed spill blocks, everything else
+    shared); run in order, the chunks leave the bits of the one-chunk render.  (Emulation has one stream: two lanes that shared a
+    workspace would still pass the bit comparison, which is why the descriptors are asserted.)"""
+    pl, clips, mic_ir, _ = _g8_scene(golden)
+    want = lc.render_bits(emu.prepare(pl, clips, mic_ir).run())
+    batch = emu.prepare(pl, clips, mic_ir, chunk_events=1, lanes=lanes)
+    lc.check_lane_descriptors(batch, lanes, n_chunks=len(clips))
+    res = batch.run()
+    assert res.keep == (batch,)
+    lc.assert_same_render(lc.render_bits(res), want, f"{lanes} lanes")
+    np.testing.assert_array_equal(res.scales(), emu.render(pl, clips, mic_ir).scales())
+    lc.check_spill_blocks(batch)
+    lc.assert_same_render(lc.render_bits(batch.run()), want, f"{lanes} lanes, run again over the dirty workspaces")
+    # more lanes than chunks: clamped; one lane: the result does not hold the batch
+    assert emu.prepare(pl, clips, mic_ir, chunk_events=2, lanes=8).lanes == 3
+    single = emu.prepare(pl, clips, mic_ir, chunk_events=1)
+    assert single.lanes == 1 and single.bufs["_lanes"] == [] and single.result().keep == ()
+
+
+@pytest.mark.parametrize("form", ["overwrite", "fused ambience", "accumulate"])
+def test_emu_retargeted_mixdown_writes_the_same_bits_elsewhere(emu, golden, form):
+    pl, clips, mic_ir, mix = _g8_scene(golden)
+    res = emu.render(pl, clips, mic_ir)
+    n = mix.n_capsules * mix.n_samples
+    rng = np.random.default_rng(8)
+    ambience = [(emu.mem.upload(rng.standard_normal(n).astype(np.float32)),
+                 emu.mem.upload(rng.uniform(0.01, 0.1, mix.n_capsules).astype(np.float32)))] if form == "fused ambience" else []
+    prefill = rng.uniform(-1, 1, n).astype(np.float32) if form == "accumulate" else None
+    lc.run_retarget(emu, mix, res, ambience, prefill)
