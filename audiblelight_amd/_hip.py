@@ -189,6 +189,9 @@ SYMBOLS = {
     "al_fx_phaser": (ct.c_int, [_P, _P, ct.c_int64] + [ct.c_double] * 6 + [_S]),
     "al_fx_compressor": (ct.c_int, [_P, _P, ct.c_int64] + [ct.c_double] * 5 + [_S]),
     "al_fx_limiter": (ct.c_int, [_P, _P, ct.c_int64] + [ct.c_double] * 3 + [_S]),
+    "al_fx_time_stretch_workspace_floats": (ct.c_int64, [ct.c_int64, ct.c_double, ct.c_int32]),
+    "al_fx_time_stretch": (ct.c_int, [_P, ct.c_int64, _P, ct.c_int64, ct.c_double, ct.c_int32, _P, _S]),
+    "al_fx_resample_sinc": (ct.c_int, [_P, ct.c_int64, _P, ct.c_int64, _S]),
     "al_fx_batch_desc_bytes": (ct.c_int64, [ct.c_int32]),
     "al_fx_batch_pack": (ct.c_int, [ct.c_int32, _P, ct.c_int32, _P]),
     "al_fx_batch_launch": (ct.c_int, [ct.c_int32, _P, ct.c_int32, _S]),
@@ -218,6 +221,7 @@ SOS_MAX_SECTIONS = 16   # AL_SOS_MAX_SECTIONS: second-order sections per al_fx_s
 FXB_SOS, FXB_CHORUS, FXB_PHASER, FXB_DEEMPH = 1, 2, 3, 4   # AL_FXB_*: the kinds of a batched FX launch (al_fx_batch_*)
 FXB_COMPRESSOR, FXB_LIMITER = 6, 7                         # 5 is not a kind
 DYN_TILE = 1024         # samples per tile of k_fx_dynamics (csrc/al_dynfx.h DYN_TILE)
+PV_TILE = 32            # output frames per tile of the phase scan (csrc/al_stretchfx.h PV_TILE)
 FXB_JOBS = {FXB_SOS: AlFxSosJob, FXB_CHORUS: AlFxModJob, FXB_PHASER: AlFxModJob, FXB_DEEMPH: AlFxDeemphJob,
             FXB_COMPRESSOR: AlFxCompressorJob, FXB_LIMITER: AlFxLimiterJob}
 FADE_SHAPES = {"linear": 0, "exponential": 1, "logarithmic": 2, "quarter_sine": 3, "half_sine": 4, "none": 5}

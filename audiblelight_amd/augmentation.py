@@ -7,15 +7,15 @@ HighpassFilter, LowShelfFilter, HighShelfFilter and MultibandEqualizer (cascades
 sections, one ``al_fx_sos`` launch each), the delay and modulation FX Delay, Chorus and Phaser
 (linear recursions with feedback, one ``al_fx_delay`` / ``al_fx_chorus`` / ``al_fx_phaser`` launch
 each), the dynamics FX Compressor and Limiter (an envelope whose coefficient depends on its state: one wave walks the clip,
-one ``al_fx_compressor`` / ``al_fx_limiter`` launch each) and the peak normalisation of ``Event.load_audio``.  The FX whose
+one ``al_fx_compressor`` / ``al_fx_limiter`` launch each), the time-stretch FX SpeedUp and PitchShift (a phase vocoder,
+``al_fx_time_stretch``, and for PitchShift a Kaiser-windowed sinc resampler behind it, ``al_fx_resample_sinc``: grid-wide
+launches, no job) and the peak normalisation of ``Event.load_audio``.  The FX whose
 kernel runs one clip on one workgroup (the filters, Chorus with feedback, Phaser, Deemphasis, Compressor, Limiter) also
 describe their launch as a job (``batch_job``), and ``run_chains`` runs the
 chains of a whole scene together: the pending jobs of one kind on all clips go into ONE launch (``al_fx_batch_pack`` /
 ``al_fx_batch_launch``, one workgroup per clip) with the samples of the per-clip launches, bit for bit (DESIGN.md "Batched
-FX launches").  The other stateful pedalboard effects
-(codecs: GSMFullRateCompressor, MP3Compressor; time-stretch:
-PitchShift, SpeedUp) are not part of this package: out of scope (SURVEY.md
-section 2, row 3b).
+FX launches").  The two codec emulations (GSMFullRateCompressor, MP3Compressor) are not part of this package: out of scope
+(SURVEY.md section 2, row 3b).
 
 Definitions for effects whose reference arithmetic lives in un-vendored third-party wheels
 (parity unpinned, SURVEY.md 8c): Gain = x*10^(dB/20); Clipping = clamp at +-10^(dB/20);
@@ -23,7 +23,8 @@ Distortion = tanh(x*10^(dB/20)); Bitcrush = rint(x*2^bits)/2^bits (pedalboard 0.
 Preemphasis / Deemphasis = librosa 0.11 ``effects.preemphasis`` / ``deemphasis`` including their
 linear-extrapolation initial state.  The filter FX: see ``_FilterFX`` (first-order low/high-pass, Audio EQ
 Cookbook shelves and peaks, float64 coefficients and state, constant gains at degenerate cutoffs).  The delay and
-modulation FX: see ``Delay``, ``Chorus`` and ``Phaser``.  The dynamics FX: see ``Compressor`` and ``Limiter``.
+modulation FX: see ``Delay``, ``Chorus`` and ``Phaser``.  The dynamics FX: see ``Compressor`` and ``Limiter``.  The time-stretch
+FX: see ``_TimeStretchFX``.
 """
 from __future__ import annotations
 
@@ -915,7 +916,97 @@ class Limiter(_DynamicsFX):
         self.params = dict(threshold_db=self.threshold_db, release_ms=self.release_ms)
 
 
+class _TimeStretchFX(EventAugmentation):
+    """Time-stretch FX.  The reference calls ``pedalboard.time_stretch`` (Rubber Band, an un-vendored wheel; parity unpinned,
+    SURVEY.md 8c), so the effect is pinned by the definition in DESIGN.md "Time-stretch FX", restated and not checked against a
+    running pedalboard or librosa: ``stretch(x, rate, n_fft, n_out)`` is librosa 0.11's ``effects.time_stretch`` (a phase
+    vocoder, hop n_fft / 4, sin^2 window, float64 phase accumulator), one ``al_fx_time_stretch`` call that enqueues its kernels
+    on the stream without a host synchronisation.  The launches are grid-wide already: there is no ``batch_job``."""
+
+    N_FFT = 2048
+    MIN_RATE, MAX_RATE = 0.25, 4.0      # what al_fx_time_stretch accepts
+
+    def host_dtype(self, in_dtype):
+        return np.dtype(np.float32)     # pedalboard returns float32
+
+    @property
+    def identity(self) -> bool:
+        raise NotImplementedError
+
+    def process(self, input_array):
+        if self.identity:
+            return input_array          # the reference's ``process`` hands the input back untouched
+        return super().process(input_array)
+
+    def stretch(self, clip: DeviceClip, rate: float, n_out: int, dst) -> None:
+        """dst[:n_out] = stretch(clip, rate, N_FFT, n_out)."""
+        r = clip.r
+        floats = r.lib.call("al_fx_time_stretch_workspace_floats", clip.n, float(rate), self.N_FFT)
+        work = r.mem.empty(floats)      # may go once the call returns: the allocator orders its reuse behind the launches
+        r.lib.call("al_fx_time_stretch", r.mem.ptr(clip.buf), clip.n, r.mem.ptr(dst), n_out, float(rate), self.N_FFT,
+                   r.mem.ptr(work), r.mem.stream())
+
+
+class SpeedUp(_TimeStretchFX):
+    """``stretch(x, stretch_factor, 2048, n_out)`` with n_out = max(1, round(n / stretch_factor)) (Python's ``round``); the clip
+    then has n_out samples and ``process_device`` wrap-pads or truncates it back to n.  ``stretch_factor == 1`` is the identity:
+    no launch.  A factor outside [0.25, 4] is refused."""
+
+    MIN_SHIFT, MAX_SHIFT = 0.7, 1.5
+
+    def __init__(self, sample_rate=config.SAMPLE_RATE, stretch_factor=None):
+        super().__init__(sample_rate)
+        self.stretch_factor = _positive(_sample(stretch_factor, self.MIN_SHIFT, self.MAX_SHIFT))
+        if not self.MIN_RATE <= self.stretch_factor <= self.MAX_RATE:
+            raise ValueError(f"Expected a stretch factor in [{self.MIN_RATE}, {self.MAX_RATE}] but got {self.stretch_factor}")
+        self.params = dict(stretch_factor=self.stretch_factor)
+
+    @property
+    def identity(self) -> bool:
+        return self.stretch_factor == 1.0
+
+    def apply_device(self, clip):
+        if self.identity:
+            return
+        n_out = max(1, int(round(clip.n / self.stretch_factor)))
+        dst = clip.other(n_out)
+        self.stretch(clip, self.stretch_factor, n_out, dst)
+        clip.swap(n_out)
+
+
+class PitchShift(_TimeStretchFX):
+    """r = 2^(-semitones / 12), m = max(1, round(n / r)), y1 = stretch(x, r, 2048, m), then y1 resampled to exactly n samples by
+    a Kaiser-windowed sinc (``al_fx_resample_sinc``: c = 0.95 min(1, n / m), half-width 16 / c, beta 8.6, float64 per output
+    sample).  ``semitones`` is truncated by ``int``; 0 is the identity: no launch.  |semitones| > 24 is refused."""
+
+    MIN_SEMITONES, MAX_SEMITONES = -3, 3
+    SEMITONES_LIMIT = 24                # r stays in [0.25, 4]
+
+    def __init__(self, sample_rate=config.SAMPLE_RATE, semitones=None):
+        super().__init__(sample_rate)
+        self.semitones = int(_sample(semitones, self.MIN_SEMITONES, self.MAX_SEMITONES))
+        if abs(self.semitones) > self.SEMITONES_LIMIT:
+            raise ValueError(f"Expected at most {self.SEMITONES_LIMIT} semitones either way but got {self.semitones}")
+        self.params = dict(semitones=self.semitones)
+
+    @property
+    def identity(self) -> bool:
+        return self.semitones == 0
+
+    def apply_device(self, clip):
+        if self.identity:
+            return
+        r, n = clip.r, clip.n
+        rate = 2.0 ** (-self.semitones / 12.0)
+        m = max(1, int(round(n / rate)))
+        stretched = r.mem.empty(m)
+        self.stretch(clip, rate, m, stretched)
+        dst = clip.other(n)
+        r.lib.call("al_fx_resample_sinc", r.mem.ptr(stretched), m, r.mem.ptr(dst), n, r.mem.stream())
+        clip.swap(n)
+
+
 ALL_EVENT_AUGMENTATIONS = [Gain, Invert, Reverse, Fade, Clipping, Distortion, Bitcrush, Preemphasis, Deemphasis,
                            TimeWarpSilence, TimeWarpDuplicate, TimeWarpRemove, TimeWarpReverse,
                            LowpassFilter, HighpassFilter, LowShelfFilter, HighShelfFilter, MultibandEqualizer,
-                           Delay, Chorus, Phaser, Compressor, Limiter]
+                           Delay, Chorus, Phaser, Compressor, Limiter, SpeedUp, PitchShift]

@@ -1,7 +1,7 @@
 // C ABI of the MI355X synthesis path (gfx950 only): every extern "C" entry point of include/audiblelight_hip.h that launches
 // device code, each one argument validation plus launch.  No kernel and no launch planning lives here: kernels, their device
 // helpers and the host-side choice of instantiation and grid are in the per-domain headers included below (al_mac.h accumulate,
-// al_levels.h level scalars, al_mixdown.h, al_rows.h, al_clipfx.h / al_sos.h / al_delayfx.h / al_dynfx.h FX, al_ingest.h, al_bigfft.h, al_stft.h);
+// al_levels.h level scalars, al_mixdown.h, al_rows.h, al_clipfx.h / al_sos.h / al_delayfx.h / al_dynfx.h / al_stretchfx.h FX, al_ingest.h, al_bigfft.h, al_stft.h);
 // the FFT kernels of the pipeline are the other translation unit, al_transforms.hip.  See DESIGN.md for the data layout and
 // per-kernel rooflines.
 //
@@ -31,6 +31,7 @@
 #include "al_rows.h"
 #include "al_sos.h"
 #include "al_stft.h"
+#include "al_stretchfx.h"
 
 // ====================================================================== C ABI
 namespace {
@@ -555,6 +556,63 @@ int al_fx_limiter(const float *src, float *dst, int64_t n, double fs, double thr
   if (int rc = limiter_prepare(src, dst, n, fs, threshold_db, release_ms, &job)) return rc;
   hipLaunchKernelGGL(al::k_fx_dynamics, dim3(1), dim3(al::DYN_LANES), 0, (hipStream_t)stream, (const al::DynJob *)nullptr, job);
   return check_launch("k_fx_dynamics");
+}
+
+// ---- time-stretch FX (phase vocoder, Kaiser-windowed sinc resampler): DESIGN.md "Time-stretch FX"
+namespace {
+// 0, or the error of the first bad pointer or length; src of n samples, dst of n_out
+int stretch_check(const char *fn, const float *src, int64_t n, const float *dst, int64_t n_out, const char *n_name,
+                  const char *n_out_name, const void *workspace, bool needs_workspace) {
+  char msg[200];
+  if (!src || !dst || (needs_workspace && !workspace)) snprintf(msg, sizeof(msg), "%s: null pointer", fn);
+  else if (n < 1) snprintf(msg, sizeof(msg), "%s: %s must be >= 1", fn, n_name);
+  else if (n_out < 1) snprintf(msg, sizeof(msg), "%s: %s must be >= 1", fn, n_out_name);
+  else return AL_OK;
+  return fail(AL_E_BADARG, msg);
+}
+
+int stretch_overlap_check(const char *fn, const float *src, int64_t n, const float *dst, int64_t n_out) {
+  if (!fx_ranges_overlap(src, n, dst, n_out)) return AL_OK;
+  char msg[200];
+  snprintf(msg, sizeof(msg), "%s: dst overlaps src (out of place only)", fn);
+  return fail(AL_E_BADARG, msg);
+}
+
+// 0, or the error of a bad (n, rate, n_fft): the geometry both time-stretch entries derive
+int stretch_geometry_check(const char *fn, int64_t n, double rate, int32_t n_fft) {
+  char msg[200];
+  const char *why = nullptr;
+  if (!al::pv_fft_ok(n_fft)) why = "n_fft must be a power of two in [64, 4096]";
+  else if (!isfinite(rate) || rate < 0.25 || rate > 4.0) why = "rate must be finite and in [0.25, 4]";
+  else if (al::pv_frames_in(n, n_fft) > al::PV_MAX_FRAMES) why = "too many analysis frames (F = 1 + n / hop must be <= 2^30)";
+  else if (al::pv_frames_out(al::pv_frames_in(n, n_fft), rate) > al::PV_MAX_FRAMES) why = "too many output frames (T must be <= 2^30)";
+  if (!why) return AL_OK;
+  snprintf(msg, sizeof(msg), "%s: %s", fn, why);
+  return fail(AL_E_BADARG, msg);
+}
+}  // namespace
+
+int64_t al_fx_time_stretch_workspace_floats(int64_t n, double rate, int32_t n_fft) {
+  if (n < 1 || stretch_geometry_check("al_fx_time_stretch_workspace_floats", n, rate, n_fft)) return 0;
+  return al::pv_plan(n, rate, n_fft).floats;
+}
+
+int al_fx_time_stretch(const float *src, int64_t n, float *dst, int64_t n_out, double rate, int32_t n_fft, float *workspace,
+                       al_stream_t stream) {
+  if (int rc = stretch_check("al_fx_time_stretch", src, n, dst, n_out, "n", "n_out", workspace, true)) return rc;
+  if (int rc = stretch_geometry_check("al_fx_time_stretch", n, rate, n_fft)) return rc;   // before the ranges: it bounds n
+  if (int rc = stretch_overlap_check("al_fx_time_stretch", src, n, dst, n_out)) return rc;
+  if (((uintptr_t)workspace & 15) != 0) return fail(AL_E_BADARG, "al_fx_time_stretch: workspace must be 16-byte aligned");
+  al::launch_time_stretch(src, n, dst, n_out, rate, n_fft, workspace, (hipStream_t)stream);
+  return check_launch("al_fx_time_stretch");  // hipGetLastError keeps the first failure of the sequence until it is read
+}
+
+int al_fx_resample_sinc(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream) {
+  if (int rc = stretch_check("al_fx_resample_sinc", src, m, dst, n, "m", "n", nullptr, false)) return rc;
+  if (m > 0x7fffffff || n > 0x7fffffff) return fail(AL_E_BADARG, "al_fx_resample_sinc: m and n must be below 2^31");
+  if (int rc = stretch_overlap_check("al_fx_resample_sinc", src, m, dst, n)) return rc;
+  al::launch_resample_sinc(src, m, dst, n, (hipStream_t)stream);
+  return check_launch("k_resample_sinc");
 }
 
 // ---- batched FX launches: one workgroup per job, the jobs of one kind in one grid

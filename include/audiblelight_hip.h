@@ -341,6 +341,31 @@ int al_fx_phaser(const float *src, float *dst, int64_t n, double fs, double rate
 int al_fx_compressor(const float *src, float *dst, int64_t n, double fs, double threshold_db, double ratio, double attack_ms,
                      double release_ms, al_stream_t stream);
 int al_fx_limiter(const float *src, float *dst, int64_t n, double fs, double threshold_db, double release_ms, al_stream_t stream);
+/* Time-stretch FX (SpeedUp, PitchShift; augmentation.py:1232-1347).  The reference calls pedalboard.time_stretch (Rubber Band, not
+ * vendored): these are pinned by the definition in DESIGN.md "Time-stretch FX" -- librosa 0.11's effects.time_stretch /
+ * phase_vocoder restated, and a Kaiser-windowed sinc resampler -- unchecked against a running pedalboard or librosa.
+ *
+ * al_fx_time_stretch: dst[0 .. n_out) = stretch(src[0 .. n), rate, n_fft, n_out).  hop = n_fft / 4, w[t] = sin^2(pi t / n_fft).
+ *   Analysis: x zero-padded by n_fft / 2 on both sides, F = 1 + n / hop frames, D[f] = rfft(w xpad[f hop ..]), D[F] = D[F+1] = 0.
+ *   Steps: step_t = t rate (float64) for every t >= 0 with step_t < F (T of them), i_t = floor(step_t), a_t = step_t - i_t.
+ *   mag[t][k] = (1 - a_t) |D[i_t][k]| + a_t |D[i_t + 1][k]|;  phi_k = pi hop k / (n_fft / 2);
+ *   d = arg D[i_t + 1][k] - arg D[i_t][k] - phi_k, d <- d - 2 pi round(d / 2 pi), inc[t][k] = phi_k + d  (arg 0 = 0).
+ *   acc[0][k] = arg D[0][k], acc[t + 1][k] = acc[t][k] + inc[t][k] (float64, reduced mod 2 pi at tile boundaries);
+ *   S[t][k] = mag[t][k] e^{i acc[t][k]};  fr[t] = irfft(S[t], n_fft);  y[u] = sum_t w[u - t hop] fr[t][u - t hop],
+ *   divided by sum_t w^2[u - t hop] where that exceeds FLT_MIN;  dst[j] = y[n_fft / 2 + j], zero from u = n_fft + hop (T - 1) on.
+ *   The analysis transform runs in float64 (an error in arg D would add up over the frames), the synthesis in float32.
+ *   Runs on `stream` without a host synchronisation; workspace: al_fx_time_stretch_workspace_floats(n, rate, n_fft) floats,
+ *   16-byte aligned (0 for arguments the entry would refuse).
+ * al_fx_resample_sinc: dst[0 .. n) from src[0 .. m): c = 0.95 min(1, n / m), H = 16 / c, beta = 8.6, p = t m / n (exact integer
+ *   division, int64: i + rem / n), dst[t] = sum_{j in [0, m), |p - j| <= H} src[j] c sinc(c (p - j)) I0(beta sqrt(1 - ((p - j) / H)^2)) / I0(beta),
+ *   float64 per output sample.  m == n is a low-pass (c = 0.95), not a copy.
+ * AL_E_BADARG, with al_last_error() naming the entry and the reason, for a null pointer (the workspace included), n < 1,
+ * n_out < 1, m < 1, dst overlapping src, n_fft not a power of two in [64, 4096], rate not finite or outside [0.25, 4], F or T
+ * above 2^30, a workspace that is not 16-byte aligned, m or n of the resampler at or above 2^31. */
+int64_t al_fx_time_stretch_workspace_floats(int64_t n, double rate, int32_t n_fft);
+int al_fx_time_stretch(const float *src, int64_t n, float *dst, int64_t n_out, double rate, int32_t n_fft, float *workspace,
+                       al_stream_t stream);
+int al_fx_resample_sinc(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream);
 /* Batched FX launches: the one-workgroup scans (al_fx_sos, al_fx_chorus with feedback > 0, al_fx_phaser, the AL_FX_DEEMPH op
  * of al_fx_apply) and the one-wave walks (al_fx_compressor, al_fx_limiter) on MANY clips in ONE launch, workgroup b running job b exactly as the single-clip entry would (the same
  * kernel, which a single-clip call launches with a grid of 1: the samples are bit-identical).  Three steps:
