@@ -32,7 +32,7 @@ class SceneJob:
     """One microphone of one scene, described by arrays already in host memory."""
     specs: Sequence[planning.EventSpec]
     clips: Sequence                 # float32 arrays or engine.ClipSource (device-resident / folded-FX clips)
-    irs: np.ndarray                 # (C, N_total, L) float32 or float64 (WorldState.get_irs() layout)
+    irs: np.ndarray                 # (C, N_total, L) float32 or float64 (WorldState.get_irs() layout), or a shoebox.DeviceIRTensor
     starts: Sequence[float]
     ends: Sequence[float]
     duration: float
@@ -127,7 +127,7 @@ class BatchDriver:
         audio_host = self._pinned_buffer("audio", torch.float32, pl.audio_floats, slot)
         r.pack_audio(pl, job.clips, out=audio_host.numpy())
         st = dict(job=job, plan=pl, mix=mix_plan, audio_host=audio_host, slot=slot, t0=time.perf_counter(),
-                  h2d=job.irs.nbytes + pl.audio_floats * 4)
+                  h2d=(0 if hasattr(job.irs, "result") else job.irs.nbytes) + pl.audio_floats * 4)   # a device-resident tensor: no copy
         if job.irs.dtype == np.float64 and self.cast_threads > 0 and job.irs.size:
             # float64 IRs (the reference's get_irs() dtype): cast HERE, in the planner thread's time, by a pool of threads into
             # the slot's page-locked float32 buffer; the uploader then moves half the bytes, as one asynchronous DMA.  The cast
@@ -161,7 +161,11 @@ class BatchDriver:
             for off, src in device_clips:
                 audio_dev[off: off + len(src)] = src.device[: len(src)]
             release = [] if self.async_h2d else None
-            if "irs_host_f32" in st:                     # cast by the planner: one asynchronous DMA out of page-locked memory
+            if hasattr(job.irs, "result"):               # born in HBM (shoebox.DeviceIRTensor): behind the launch that made it
+                if getattr(job.irs, "ready", None) is not None:
+                    self.copy_stream.wait_event(job.irs.ready)
+                irs_dev, strides = job.irs.result()
+            elif "irs_host_f32" in st:                   # cast by the planner: one asynchronous DMA out of page-locked memory
                 c, n, l = job.irs.shape
                 lp = (l + 3) // 4 * 4
                 raw = st["irs_host_f32"].to(r.mem.device, non_blocking=True)
@@ -476,7 +480,7 @@ def scene_jobs(scene, name: str, renderer: Optional[engine.Renderer] = None) -> 
         if len(getattr(scene, "ambience", {})) > 0:
             r = renderer or synthesize.get_renderer()
             ambience = [synthesize._ambience_on_device(r, a, (mic_ir.shape[0], n_scene)) for a in scene.ambience.values()]
-        jobs.append(SceneJob(specs=specs, clips=clips, irs=np.asarray(mic_ir), starts=starts, ends=ends,
+        jobs.append(SceneJob(specs=specs, clips=clips, irs=mic_ir if hasattr(mic_ir, "result") else np.asarray(mic_ir), starts=starts, ends=ends,
                              duration=scene.duration, sample_rate=scene.sample_rate, name=f"{name}/{mic_alias}",
                              ambience=ambience))
     return jobs
@@ -604,7 +608,12 @@ def merge_jobs(jobs: Sequence[SceneJob]):
                                             gain=sp.gain, ref_db=sp.ref_db, stft_len=sp.stft_len))
             clips.append(clip)
         col += job.irs.shape[1]
-    irs = np.concatenate([np.asarray(j.irs, dtype=np.float32) for j in jobs], axis=1)
+    if any(hasattr(j.irs, "result") for j in jobs):      # device-resident tensors are joined where they lie
+        from . import shoebox
+
+        irs = shoebox.concatenate_sources([j.irs for j in jobs])
+    else:
+        irs = np.concatenate([np.asarray(j.irs, dtype=np.float32) for j in jobs], axis=1)
     return specs, clips, irs, ranges
 
 

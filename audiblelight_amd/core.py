@@ -294,6 +294,124 @@ class StaticIRState:
         return None
 
 
+class ShoeboxIRState:
+    """WorldState stand-in for a rectangular room whose IRs are generated on the device by the image-source method
+    (shoebox.py, DESIGN.md "Shoebox IRs"): the reference's ``WorldStateShoebox`` (worldstate.py:3105-3110) is declared and left
+    empty.  ``betas``: six wall reflection coefficients (x0, x1, y0, y1, z0, z1), or ``rt60`` for one uniform coefficient by
+    Sabine's law.  Microphones are sets of omnidirectional point capsules; emitters are IR columns in event order (a moving event
+    contributes one row per trajectory point).  ``simulate()`` enqueues one generation per microphone; the tensors stay in HBM."""
+
+    name = "SHOEBOX"
+
+    def __init__(self, room, betas=None, rt60: Optional[float] = None, ir_len: int = 4096, sample_rate: int = config.SAMPLE_RATE,
+                 c: float = 343.0, max_order: Optional[int] = None, renderer=None, metadata: Optional[dict] = None):
+        from . import shoebox
+
+        if (betas is None) == (rt60 is None):
+            raise ValueError("give either betas or rt60")
+        self.room = shoebox._room(room)
+        self.rt60 = None if rt60 is None else float(rt60)
+        self.betas = shoebox.betas_from_rt60(self.room, rt60, c) if betas is None else np.array(betas, dtype=np.float64)
+        self.ir_len, self.sample_rate, self.c = int(ir_len), int(sample_rate), float(c)
+        self.max_order = None if max_order is None else int(max_order)
+        self.renderer = renderer
+        self.metadata = dict(metadata or {})
+        self.microphones: "OrderedDict[str, MicArray]" = OrderedDict()
+        self.emitters: "OrderedDict[str, np.ndarray]" = OrderedDict()
+        self._capsules: "OrderedDict[str, np.ndarray]" = OrderedDict()
+        self._irs = None
+        # refuse bad room parameters here, not at the first simulate()
+        inside = 0.5 * self.room[None, :]
+        shoebox.check_arguments(self.room, self.betas, inside, inside + 0.25 * self.room[None, :], self.ir_len, self.sample_rate,
+                                self.c, self.max_order)
+
+    def add_microphone(self, alias: str, capsule_positions) -> MicArray:
+        from . import shoebox
+
+        if alias in self.microphones:
+            raise KeyError(f"Microphone with alias {alias} already exists")
+        capsules = shoebox._points(capsule_positions, self.room, f"capsules of {alias}")
+        self._capsules[alias] = capsules
+        self.microphones[alias] = MicArray(alias, len(capsules), dict(micarray_type="MicArray", coordinates_absolute=capsules.tolist()))
+        self._irs = None
+        return self.microphones[alias]
+
+    def add_emitters(self, positions, alias: Optional[str] = None) -> str:
+        """One IR column per row of ``positions`` (n, 3), appended in event order.  Returns the alias the rows are filed under."""
+        from . import shoebox
+
+        alias = alias if alias is not None else f"emitters{len(self.emitters):03d}"
+        if alias in self.emitters:
+            raise KeyError(f"Emitters with alias {alias} already exist")
+        self.emitters[alias] = shoebox._points(np.atleast_2d(np.asarray(positions, dtype=np.float64)), self.room, f"emitters {alias}")
+        self._irs = None
+        return alias
+
+    @property
+    def num_emitters(self) -> int:
+        return sum(len(v) for v in self.emitters.values())
+
+    @property
+    def emitter_positions(self) -> np.ndarray:
+        return np.concatenate(list(self.emitters.values()), axis=0) if self.emitters else np.zeros((0, 3))
+
+    def simulate(self) -> None:
+        from . import shoebox, synthesize
+
+        if not self.microphones:
+            raise ValueError("WorldState has no microphones!")
+        if not self.emitters:
+            raise ValueError("WorldState has no emitters!")
+        r = self.renderer or synthesize.get_renderer()
+        sources = self.emitter_positions
+        irs = OrderedDict()
+        for alias, capsules in self._capsules.items():
+            buf, strides, _ = shoebox.shoebox_irs_device(r, self.room, self.betas, sources, capsules, self.ir_len, self.sample_rate,
+                                                         self.c, self.max_order)
+            irs[alias] = shoebox.DeviceIRTensor(r, buf, strides, (len(capsules), len(sources), self.ir_len))
+        self._irs = irs
+
+    @property
+    def irs(self):
+        if self._irs is None:
+            raise AttributeError("IRs have not been generated yet: call simulate()")
+        return self._irs
+
+    def get_irs(self):
+        return self.irs
+
+    def to_dict(self) -> dict:   # worldstate.py:2330-2356 layout, with the room in place of the mesh
+        d = dict(backend=self.name, sample_rate=self.sample_rate,
+                 emitters={k: v.tolist() for k, v in self.emitters.items()},
+                 microphones={k: m.to_dict() for k, m in self.microphones.items()},
+                 shoebox=dict(room=self.room.tolist(), betas=self.betas.tolist(), rt60=self.rt60, ir_len=self.ir_len, c=self.c,
+                              max_order=self.max_order))
+        d.update({k: v for k, v in self.metadata.items() if k not in d})
+        return d
+
+    @staticmethod
+    def describes(state_d: dict) -> bool:
+        """Does this state dictionary carry everything ``from_dict`` needs?"""
+        box, mics = state_d.get("shoebox"), state_d.get("microphones") or {}
+        return (str(state_d.get("backend", "")).upper() == "SHOEBOX" and isinstance(box, dict)
+                and all(k in box for k in ("room", "betas", "ir_len")) and bool(state_d.get("emitters")) and bool(mics)
+                and all(isinstance(m, dict) and m.get("coordinates_absolute") is not None for m in mics.values()))
+
+    @classmethod
+    def from_dict(cls, state_d: dict, renderer=None) -> "ShoeboxIRState":
+        box = state_d["shoebox"]
+        keep = {k: v for k, v in state_d.items() if k not in ("backend", "sample_rate", "emitters", "microphones", "shoebox")}
+        state = cls(box["room"], betas=box["betas"], ir_len=box["ir_len"], sample_rate=state_d.get("sample_rate") or config.SAMPLE_RATE,
+                    c=box.get("c", 343.0), max_order=box.get("max_order"), renderer=renderer, metadata=keep)
+        state.rt60 = box.get("rt60")
+        for alias, md in state_d["microphones"].items():
+            mic = state.add_microphone(alias, md["coordinates_absolute"])
+            mic.metadata.update({k: v for k, v in md.items() if k not in ("n_capsules",)})
+        for alias, rows in state_d["emitters"].items():
+            state.add_emitters(rows, alias)
+        return state
+
+
 class Scene:
     """Container with the attributes the synthesis functions read (core.py:131-251) and ``generate``."""
 
@@ -337,14 +455,17 @@ class Scene:
             json.dump(self.to_dict(), fh, indent=4, ensure_ascii=False)
 
     @classmethod
-    def from_dict(cls, d: dict, clips: Dict[str, np.ndarray], irs: Dict[str, np.ndarray]) -> "Scene":
+    def from_dict(cls, d: dict, clips: Dict[str, np.ndarray], irs: Optional[Dict[str, np.ndarray]] = None) -> "Scene":
         """Rebuild a scene from the reference's ``Scene.to_dict()`` metadata (core.py:2106-2130; what
         ``Scene.generate`` writes as ``metadata_out.json``) plus the arrays it does not carry: ``clips[event alias]``
         (decoded mono audio, see ``Event.from_dict``) and ``irs[mic alias]`` ((C, N_total, L) tensors in event order:
         ``WorldState.get_irs()``, worldstate.py:2183-2255).  A dataset can so be re-rendered on the GPU from its
-        metadata without the placement / ray-tracing stages."""
+        metadata without the placement / ray-tracing stages.  A state written by ``ShoeboxIRState`` (backend "SHOEBOX" with its
+        room, emitter positions and capsule coordinates) is rebuilt from the metadata when ``irs`` lacks its microphones: those
+        IRs are generated again on the device."""
         from . import ambience as amb_mod
 
+        irs = {} if irs is None else irs
         for k in ("duration", "ref_db", "events", "sample_rate"):
             if k not in d:
                 raise KeyError(f"Missing key: '{k}'")
@@ -355,10 +476,14 @@ class Scene:
                 raise ValueError(f"Microphone {mic} has {md.get('n_capsules')} capsules in the metadata but its IR tensor "
                                  f"has {np.asarray(irs[mic]).shape[0]}")
         missing = [m for m in mic_meta if m not in irs]
-        if missing:
+        from_room = bool(missing) and ShoeboxIRState.describes(state_d)   # a shoebox scene carries its room: IRs are generated again
+        if missing and not from_room:
             raise KeyError(f"No IR tensor given for microphones {missing}")
-        state = StaticIRState(irs, {k: v for k, v in mic_meta.items() if isinstance(v, dict)},
-                              {k: v for k, v in state_d.items() if k != "microphones"})
+        if from_room:
+            state = ShoeboxIRState.from_dict(state_d)
+        else:
+            state = StaticIRState(irs, {k: v for k, v in mic_meta.items() if isinstance(v, dict)},
+                                  {k: v for k, v in state_d.items() if k != "microphones"})
         scene = cls(d["duration"], state, sample_rate=d["sample_rate"], ref_db=d["ref_db"])
         scene.metadata = {k: d[k] for k in ("max_overlap", "fg_path", "bg_path", "class_mapping") if k in d}
         total = 0
@@ -367,7 +492,9 @@ class Scene:
                 raise KeyError(f"No clip given for event '{alias}' ({ed.get('filepath')})")
             ev = scene.add_event(Event.from_dict(dict(ed, alias=ed.get("alias", alias)), clips[alias]))
             total += len(ev)
-        for mic, tensor in state.irs.items():
+        if from_room and state.num_emitters != total:
+            raise ValueError(f"The state has {state.num_emitters} emitter positions, the events need {total}")
+        for mic, tensor in ({} if from_room else state.irs).items():
             if tensor.shape[1] != total:
                 raise ValueError(f"IR tensor of {mic} has {tensor.shape[1]} emitter columns, the events need {total}")
         for alias, ad in (d.get("ambience") or {}).items():
@@ -375,7 +502,7 @@ class Scene:
         return scene
 
     @classmethod
-    def from_json(cls, path: str, clips: Dict[str, np.ndarray], irs: Dict[str, np.ndarray]) -> "Scene":
+    def from_json(cls, path: str, clips: Dict[str, np.ndarray], irs: Optional[Dict[str, np.ndarray]] = None) -> "Scene":
         import json
 
         with open(path) as fh:

@@ -1,0 +1,243 @@
+// Shoebox room impulse responses by the image-source method (Allen & Berkley 1979), generated in HBM in the (C, N, pitch) layout
+// Renderer.prepare reads.  The definition is in DESIGN.md "Shoebox IRs" and in include/audiblelight_hip.h (al_ism_shoebox).
+//
+// Per axis an image is numbered by one integer q = 2 m - p (p = q & 1): image q lies in mirror cell q, its coordinate grows with q,
+// and it has been reflected |q| times (k0 = |m - p| times by the wall at 0, k1 = |m| times by the wall at L).  The CANONICAL ORDER of
+// the images of a (capsule, source) pair is lexicographic in (qx, qy, qz); every output sample is the float64 sum of its taps in
+// that order, rounded to float32 once.  Nothing is scattered and nothing is atomic: the kernel GATHERS.
+//
+// k_ism_shoebox  one workgroup of ONE WAVE per (pair, tile of ISM_TILE samples), ISM_PER_LANE samples per lane (lane, lane + 64, ...),
+//   the accumulators float64 registers.  (One wave: the __syncthreads() below order LDS traffic only, hipcc emits no barrier
+//   instruction for them, and no wave can be out of step with another.)
+//   The images that can reach the tile lie in the shell d_lo < |R| < d_hi.  The wave walks the lattice COLUMNS (qx, qy) in
+//   order, ISM_THREADS at a time, lane k taking column base + k:
+//     1. the lane bounds the column's qz by the shell (at most two runs: below and above the inner sphere; a column wholly inside the
+//        inner sphere, outside the outer one or beyond max_order has none) and counts the images of those runs that touch the tile
+//        (the exact test, on the image's own rint(tau): the runs are only a superset);
+//     2. an exclusive prefix sum of the counts over the wave (suffix sums by __shfl_down, the total through LDS);
+//     3. the lane walks its runs again and writes its touching images to the LDS list at its offset: the list is in canonical order.
+//        A list longer than ISM_LIST goes in windows of ISM_LIST, in order;
+//     4. every lane then adds the taps of the list's images that reach ITS samples, in list order.
+//   The order of a sample's sum depends on the room and the pair alone, never on the grid, the other pairs or the list size.
+// A tap costs one LDS entry, two table reads and a division: sin(pi (t - tau)) = -(-1)^j sin(pi f) and the window's cosine by the
+// angle sum over a table of cos / sin(2 pi j / 81), with t0 = rint(tau), f = tau - t0 (exact) and j = t - t0.
+// All geometry, tau, the tap weight and the accumulator are float64.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "al_common.h"
+
+namespace al {
+
+constexpr int ISM_THREADS = 64;   // one wave
+constexpr int ISM_PER_LANE = 4;
+constexpr int ISM_TILE = ISM_THREADS * ISM_PER_LANE;   // samples per workgroup
+constexpr int ISM_HALF = 40;      // taps on either side of rint(tau): |t - tau| < 40.5
+constexpr int ISM_TAPS = 2 * ISM_HALF + 1;
+constexpr int ISM_LIST = 128;     // images per LDS list window (48 bytes each)
+constexpr double ISM_MAX_HALF_WIDTH = 1048576.0;   // mirror cells per axis and side al_ism_shoebox accepts
+
+struct IsmJob {
+  const double *sources, *capsules;   // (N, 3), (C, 3)
+  float *out;                         // (C, N, pitch)
+  int32_t n_sources, n_capsules, ir_len, pitch, max_order, n_tiles;
+  double L[3], ln_beta[6];            // ln_beta: 0 where beta == 0 (see beta_zero)
+  int32_t beta_zero[6];
+  double c, fs;
+};
+
+struct alignas(16) IsmEntry {
+  double f, g, a, c81, s81;   // tau - t0; -a sin(pi f) / (2 pi); amplitude; cos, sin(2 pi f / 81)
+  int32_t t0, reserved;
+};
+
+// image q of an axis: m and p of the definition
+__device__ __forceinline__ void ism_mp(int q, int &m, int &p) {
+  p = q & 1;
+  m = (q + p) / 2;   // q + p is even
+}
+__device__ __forceinline__ double ism_offset(int q, double s, double r, double L) {
+  int m, p;
+  ism_mp(q, m, p);
+  return (double)(1 - 2 * p) * s + 2.0 * (double)m * L - r;
+}
+// k0 ln(beta0) + k1 ln(beta1) of an axis; dead: a wall of beta == 0 has been hit
+__device__ __forceinline__ double ism_log_gain(int q, const double *ln_beta, const int32_t *zero, bool &dead) {
+  int m, p;
+  ism_mp(q, m, p);
+  const int k0 = abs(m - p), k1 = abs(m);
+  dead = dead || (k0 > 0 && zero[0]) || (k1 > 0 && zero[1]);
+  return (double)k0 * ln_beta[0] + (double)k1 * ln_beta[1];
+}
+
+// the qz of a column, as two runs [a1, b1] and [a2, b2] (empty when a > b)
+struct IsmColumn {
+  double rho2, ln_xy;
+  int a1, b1, a2, b2;
+};
+
+__device__ __forceinline__ int ism_clamp(double v, int lo, int hi) { return v < (double)lo ? lo : v > (double)hi ? hi : (int)v; }
+
+__global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
+  __shared__ IsmEntry list[ISM_LIST];
+  __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];   // cos, sin(2 pi j / 81), j = -40 .. 40
+  __shared__ int wave_total[2];
+  const int tid = threadIdx.x, lane = tid;
+  const int tile = (int)(blockIdx.x % (unsigned)job.n_tiles);
+  const int64_t pair = blockIdx.x / (unsigned)job.n_tiles;   // c * N + n
+  const int n = (int)(pair % job.n_sources), cap = (int)(pair / job.n_sources);
+  const int t_lo = tile * ISM_TILE, t = t_lo + tid;
+  const int t_hi = min(t_lo + ISM_TILE, job.ir_len) - 1;
+  float *row = job.out + pair * (int64_t)job.pitch;
+  if (t_lo >= job.ir_len) {   // a tile of pad samples only
+    for (int s = 0; s < ISM_PER_LANE; ++s)
+      if (t + s * ISM_THREADS < job.pitch) row[t + s * ISM_THREADS] = 0.f;
+    return;
+  }
+  for (int i = tid; i < ISM_TAPS; i += ISM_THREADS) sincospi(2.0 * (double)(i - ISM_HALF) / (double)ISM_TAPS, &win_s[i], &win_c[i]);
+
+  const double sx = job.sources[3 * n], sy = job.sources[3 * n + 1], sz = job.sources[3 * n + 2];
+  const double rx = job.capsules[3 * cap], ry = job.capsules[3 * cap + 1], rz = job.capsules[3 * cap + 2];
+  const double Lx = job.L[0], Ly = job.L[1], Lz = job.L[2];
+  // the shell of this tile, a sample wider than the taps reach on either side
+  const double d_hi = (double)(t_hi + ISM_HALF + 2) * job.c / job.fs, d_lo = (double)(t_lo - ISM_HALF - 2) * job.c / job.fs;
+  const double hi2 = d_hi * d_hi, lo2 = d_lo > 0.0 ? d_lo * d_lo : 0.0;
+  const int K = job.max_order;
+  int Qx = ism_clamp(floor(d_hi / Lx) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH), Qy = ism_clamp(floor(d_hi / Ly) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH),
+      Qz = ism_clamp(floor(d_hi / Lz) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH);
+  if (K >= 0) {
+    Qx = min(Qx, K);
+    Qy = min(Qy, K);
+    Qz = min(Qz, K);
+  }
+  const int64_t ny = 2 * (int64_t)Qy + 1, n_columns = (2 * (int64_t)Qx + 1) * ny;
+
+  // does image qz of column `col` touch the tile?  t0, tau and d of the image either way
+  auto touches = [&](const IsmColumn &col, int qz, double &d, double &tau, int &t0) {
+    const double Rz = ism_offset(qz, sz, rz, Lz);
+    d = sqrt(col.rho2 + Rz * Rz);
+    tau = d * job.fs / job.c;
+    if (!(tau < 2.0e9) || !(d > 0.0)) return false;
+    t0 = (int)rint(tau);
+    return t0 + ISM_HALF >= t_lo && t0 - ISM_HALF <= t_hi;
+  };
+
+  double acc[ISM_PER_LANE] = {};
+  int parity = 0;
+  for (int64_t base = 0; base < n_columns; base += ISM_THREADS, parity ^= 1) {
+    // 1. this lane's column
+    const int64_t ci = base + tid;
+    IsmColumn col;
+    col.a1 = col.a2 = 0;
+    col.b1 = col.b2 = -1;
+    bool dead = true;
+    if (ci < n_columns) {
+      const int qx = (int)(ci / ny) - Qx, qy = (int)(ci % ny) - Qy;
+      const int k_xy = abs(qx) + abs(qy);
+      const double Rx = ism_offset(qx, sx, rx, Lx), Ry = ism_offset(qy, sy, ry, Ly);
+      col.rho2 = Rx * Rx + Ry * Ry;
+      if ((K < 0 || k_xy <= K) && col.rho2 < hi2) {
+        dead = false;
+        col.ln_xy = ism_log_gain(qx, job.ln_beta, job.beta_zero, dead) + ism_log_gain(qy, job.ln_beta + 2, job.beta_zero + 2, dead);
+        const int Kz = K < 0 ? Qz : min(Qz, K - k_xy);
+        const double z_max = sqrt(hi2 - col.rho2);
+        // image qz lies in (qz Lz, (qz + 1) Lz): one cell of margin on either side
+        col.a1 = ism_clamp(floor((rz - z_max) / Lz) - 1.0, -Kz, Kz);
+        const int top = ism_clamp(floor((rz + z_max) / Lz) + 1.0, -Kz, Kz);
+        col.b1 = top;   // one run, unless the inner sphere cuts it in two
+        if (lo2 > col.rho2) {   // the cells wholly inside the inner sphere are left out
+          const double z_min = sqrt(lo2 - col.rho2);
+          const double ea = ceil((rz - z_min) / Lz) + 1.0, eb = floor((rz + z_min) / Lz) - 2.0;
+          if (ea <= eb) {
+            col.b1 = ism_clamp(ea - 1.0, -Kz - 1, Kz);
+            col.a2 = ism_clamp(eb + 1.0, -Kz, Kz + 1);
+            col.b2 = top;
+          }
+        }
+      }
+    }
+    int count = 0;
+    if (!dead) {
+      double d, tau;
+      int t0;
+      for (int run = 0; run < 2; ++run)
+        for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz) {
+          bool gone = false;
+          ism_log_gain(qz, job.ln_beta + 4, job.beta_zero + 4, gone);
+          if (!gone && touches(col, qz, d, tau, t0)) ++count;
+        }
+    }
+    // 2. exclusive prefix sum of the counts: suffix sums by shuffles, the total (lane 0's) through LDS
+    int suffix = count;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int other = __shfl_down(suffix, off, 64);
+      if (lane + off < 64) suffix += other;
+    }
+    if (lane == 0) wave_total[parity] = suffix;
+    __syncthreads();
+    const int total = wave_total[parity], offset = total - suffix;
+    // 3. + 4. the list, a window of ISM_LIST at a time
+    for (int w0 = 0; w0 < total; w0 += ISM_LIST) {
+      if (count > 0 && offset < w0 + ISM_LIST && offset + count > w0) {
+        int pos = offset;
+        for (int run = 0; run < 2; ++run)
+          for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz) {
+            bool gone = false;
+            const double ln_z = ism_log_gain(qz, job.ln_beta + 4, job.beta_zero + 4, gone);
+            double d, tau;
+            int t0;
+            if (gone || !touches(col, qz, d, tau, t0)) continue;
+            if (pos >= w0 && pos < w0 + ISM_LIST) {
+              IsmEntry e;
+              double sp, cp;
+              e.t0 = t0;
+              e.reserved = 0;
+              e.f = tau - (double)t0;
+              e.a = exp(col.ln_xy + ln_z) / (4.0 * M_PI * d);
+              sincospi(e.f, &sp, &cp);
+              e.g = -0.5 * e.a * sp / M_PI;
+              sincospi(2.0 * e.f / (double)ISM_TAPS, &e.s81, &e.c81);
+              list[pos - w0] = e;
+            }
+            ++pos;
+          }
+      }
+      __syncthreads();
+      const int n_list = min(ISM_LIST, total - w0);
+      for (int i = 0; i < n_list; ++i) {
+        const int j0 = t - list[i].t0;   // of the lane's first sample; the others are 64 apart, so at most two are in reach
+        if (j0 > ISM_HALF || j0 + (ISM_PER_LANE - 1) * ISM_THREADS < -ISM_HALF) continue;
+        const IsmEntry e = list[i];
+#pragma unroll
+        for (int s = 0; s < ISM_PER_LANE; ++s) {
+          const int j = j0 + s * ISM_THREADS;
+          if (j < -ISM_HALF || j > ISM_HALF || t + s * ISM_THREADS >= job.ir_len) continue;
+          const double u = (double)j - e.f;
+          if (!(fabs(u) < 0.5 * (double)ISM_TAPS)) continue;
+          if (u == 0.0) {
+            acc[s] += e.a;
+          } else {
+            const double window = 1.0 + (win_c[j + ISM_HALF] * e.c81 + win_s[j + ISM_HALF] * e.s81);
+            acc[s] += ((j & 1) ? -e.g : e.g) * window / u;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < ISM_PER_LANE; ++s) {
+    const int ts = t + s * ISM_THREADS;
+    if (ts < job.pitch) row[ts] = ts < job.ir_len ? (float)acc[s] : 0.f;
+  }
+}
+
+inline void launch_ism_shoebox(const IsmJob &job, hipStream_t stream) {
+  const int64_t groups = (int64_t)job.n_tiles * job.n_sources * job.n_capsules;
+  hipLaunchKernelGGL(k_ism_shoebox, dim3((unsigned)groups), dim3(ISM_THREADS), 0, stream, job);
+}
+
+}  // namespace al

@@ -1,7 +1,7 @@
 // C ABI of the MI355X synthesis path (gfx950 only): every extern "C" entry point of include/audiblelight_hip.h that launches
 // device code, each one argument validation plus launch.  No kernel and no launch planning lives here: kernels, their device
 // helpers and the host-side choice of instantiation and grid are in the per-domain headers included below (al_mac.h accumulate,
-// al_levels.h level scalars, al_mixdown.h, al_rows.h, al_clipfx.h / al_sos.h / al_delayfx.h / al_dynfx.h / al_stretchfx.h FX, al_ingest.h, al_bigfft.h, al_stft.h);
+// al_levels.h level scalars, al_mixdown.h, al_rows.h, al_clipfx.h / al_sos.h / al_delayfx.h / al_dynfx.h / al_stretchfx.h FX, al_ingest.h, al_ism.h, al_bigfft.h, al_stft.h);
 // the FFT kernels of the pipeline are the other translation unit, al_transforms.hip.  See DESIGN.md for the data layout and
 // per-kernel rooflines.
 //
@@ -25,6 +25,7 @@
 #include "al_dynfx.h"
 #include "al_fft.h"
 #include "al_ingest.h"
+#include "al_ism.h"
 #include "al_levels.h"
 #include "al_mac.h"
 #include "al_mixdown.h"
@@ -879,6 +880,45 @@ int al_pack_ragged_irs(const void *src, int32_t src_is_f64, const int64_t *offse
     hipLaunchKernelGGL(al::k_pack_ragged<float>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const float *>(src), offsets, lens, dst, dst_pitch);
   return check_launch("k_pack_ragged");
+}
+
+// ---- shoebox room IRs (image-source method): DESIGN.md "Shoebox IRs"
+int al_ism_shoebox(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
+                   const double *beta, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, float *out,
+                   al_stream_t stream) {
+  if (!sources || !capsules || !L || !beta || !out) return fail(AL_E_BADARG, "al_ism_shoebox: null pointer");
+  if (n_sources < 1 || n_capsules < 1) return fail(AL_E_BADARG, "al_ism_shoebox: n_sources and n_capsules must be >= 1");
+  if (ir_len < 1) return fail(AL_E_BADARG, "al_ism_shoebox: ir_len must be >= 1");
+  if (pitch < ir_len || (pitch & 3)) return fail(AL_E_BADARG, "al_ism_shoebox: pitch must be >= ir_len and a multiple of 4");
+  if (max_order < -1) return fail(AL_E_BADARG, "al_ism_shoebox: max_order must be >= 0, or -1 for none");
+  if (!isfinite(c) || !(c > 0.0) || !isfinite(fs) || !(fs > 0.0)) return fail(AL_E_BADARG, "al_ism_shoebox: c and fs must be finite and positive");
+  al::IsmJob job;
+  for (int i = 0; i < 3; ++i) {
+    if (!isfinite(L[i]) || !(L[i] > 0.0)) return fail(AL_E_BADARG, "al_ism_shoebox: room dimensions must be finite and positive");
+    if (!(c * ((double)ir_len + 42.0) / fs / L[i] + 2.0 <= al::ISM_MAX_HALF_WIDTH))
+      return fail(AL_E_BADARG, "al_ism_shoebox: c (ir_len + 42) / fs spans more than 2^20 mirror cells of the room");
+    job.L[i] = L[i];
+  }
+  for (int i = 0; i < 6; ++i) {
+    if (!(beta[i] >= 0.0 && beta[i] <= 1.0)) return fail(AL_E_BADARG, "al_ism_shoebox: reflection coefficients must be in [0, 1]");
+    job.beta_zero[i] = beta[i] == 0.0;
+    job.ln_beta[i] = beta[i] == 0.0 ? 0.0 : log(beta[i]);
+  }
+  job.n_tiles = (pitch + al::ISM_TILE - 1) / al::ISM_TILE;
+  if ((int64_t)job.n_tiles * n_sources * n_capsules > 0x7fffffff)
+    return fail(AL_E_BADARG, "al_ism_shoebox: more than 2^31 - 1 workgroups (tiles of 256 samples x pairs): split the call");
+  job.sources = sources;
+  job.capsules = capsules;
+  job.out = out;
+  job.n_sources = n_sources;
+  job.n_capsules = n_capsules;
+  job.ir_len = ir_len;
+  job.pitch = pitch;
+  job.max_order = max_order;
+  job.c = c;
+  job.fs = fs;
+  al::launch_ism_shoebox(job, (hipStream_t)stream);
+  return check_launch("k_ism_shoebox");
 }
 
 int al_resample_poly(const float *x, int32_t rows, int64_t n_in, const float *taps, int32_t half_len, int32_t up, int32_t down,

@@ -566,7 +566,9 @@ def render_audio_for_all_scene_events(scene, ignore_cache: Optional[bool] = Fals
         res = r.render(pl, clips, ir_on_device.pop(mic_alias, mic_ir))
         for i, (event, em0, clip_dtype) in enumerate(todo):
             _publish(event, mic_alias, res, i, _reference_dtype(clip_dtype, len(event), mic_ir))
-        _dry_batch(r, [(event, mic_ir[:, em0: em0 + len(event), :], i, em0) for i, (event, em0, _) in enumerate(todo)],
+        # (only events that ask for a dry render slice the tensor: slicing a device-resident one brings it to the host)
+        _dry_batch(r, [(event, mic_ir[:, em0: em0 + len(event), :], i, em0) for i, (event, em0, _) in enumerate(todo)
+                       if getattr(event, "ref_ir_channel", None) is not None or getattr(event, "direct_path_time_ms", None) is not None],
                    mic_alias, res)
     logger.info(f"Rendered scene audio in {(time() - start):.2f} seconds!")
 

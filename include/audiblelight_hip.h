@@ -594,6 +594,24 @@ int al_plan_mixdown(const double *starts, const double *ends, const int32_t *len
 void al_mix_plan_destroy(al_mix_plan *plan);
 int al_mix_plan_get(const al_mix_plan *plan, al_mix_tables *tables);
 
+/* Shoebox room impulse responses by the image-source method (DESIGN.md "Shoebox IRs"; kernel: csrc/al_ism.h), written straight into
+ * the (C, N, pitch) float32 layout al_batch.ir reads (ir_stride_c = N * pitch, ir_stride_n = pitch).  For p in {0,1}^3 and m in Z^3,
+ * per axis (x shown): R_x = (1 - 2 p_x) s_x + 2 m_x L_x - r_x, k_x0 = |m_x - p_x|, k_x1 = |m_x|; d = |R|, tau = d fs / c samples,
+ * order = sum of the six k, a = prod beta^k / (4 pi d) with 0^0 = 1.  An image of order <= max_order (max_order == -1: no limit)
+ * adds  a * 0.5 (1 + cos(2 pi (t - tau) / 81)) * sinc(t - tau)  to every integer t in [0, ir_len) with |t - tau| < 40.5.  Each sample
+ * is the float64 sum of its taps in one fixed image order, rounded to float32 once: bit-reproducible, a row's bits do not depend on
+ * the other rows of the call.  out[(c * n_sources + n) * pitch + t]; the pad samples [ir_len, pitch) are written as zeros.
+ *   sources (n_sources, 3), capsules (n_capsules, 3): float64 DEVICE tables of points strictly inside the room, every source at a
+ *   distance > 0 from every capsule (not checked: the tables are never read on the host);
+ *   L[3] (metres), beta[6] = (x0, x1, y0, y1, z0, z1) in [0, 1]: HOST arrays, read while the launch is built.
+ * One launch on `stream`; no allocation, no synchronisation.  Cost without max_order grows as ir_len^3 / (L_x L_y L_z) per pair.
+ * AL_E_BADARG: a null pointer, a non-positive or non-finite L, c or fs, a beta outside [0, 1], n_sources < 1, n_capsules < 1,
+ * ir_len < 1, pitch < ir_len, pitch % 4 != 0, max_order < -1, more than 2^31 - 1 workgroups ((pitch / 256 rounded up) * pairs), or a
+ * room so small that c (ir_len + 42) / fs spans more than 2^20 mirror cells of an axis. */
+int al_ism_shoebox(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
+                   const double *beta, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, float *out,
+                   al_stream_t stream);
+
 /* dst[t] = src[t mod m] for t < n: np.pad(..., mode="wrap") of Augmentation.process. */
 int al_wrap_copy(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream);
 
