@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "al_common.h"
+#include "al_status.h"
 
 namespace al {
 
@@ -112,6 +113,22 @@ __global__ __launch_bounds__(1024) void k_fx_deemph(const DeemphJob *__restrict_
     pw *= c;
     cn *= c;
   }
+}
+
+// ---- host side: al_fx_apply's checks of its clip arguments, and the de-emphasis job of a clip that passes them
+inline int fx_apply_check(int op, const float *src, const float *dst, int64_t n) {
+  if (!src || !dst || n <= 0) return fail(AL_E_BADARG, "bad fx arguments");
+  if (op < AL_FX_GAIN || op > AL_FX_DEEMPH) return fail(AL_E_UNSUPPORTED, "unknown fx op");
+  const bool out_of_place = (op == AL_FX_REVERSE || op == AL_FX_PREEMPH || op == AL_FX_DEEMPH);
+  if (out_of_place && src == dst) return fail(AL_E_BADARG, "this fx op needs dst != src");
+  if ((op == AL_FX_PREEMPH || op == AL_FX_DEEMPH) && n < 2) return fail(AL_E_BADARG, "emphasis filters need n >= 2");
+  return AL_OK;
+}
+
+inline int deemph_prepare(const al_fx_deemph_job &in, DeemphJob *job) {
+  if (int rc = fx_apply_check(AL_FX_DEEMPH, in.src, in.dst, in.n)) return rc;
+  *job = DeemphJob{in.src, in.dst, in.n, in.coef};
+  return AL_OK;
 }
 
 __global__ __launch_bounds__(256) void k_frame_shuffle(const float *src, float *dst, int64_t n, int frame_len,

@@ -195,6 +195,12 @@ __device__ __forceinline__ void block_reduce3(float &a_sum, float &b_max, float 
   }
 }
 
+// workgroups of 256 threads for a grid-stride loop over n elements: one thread per element, at most `cap` workgroups
+inline unsigned grid_1d(int64_t n, int64_t cap) {
+  const int64_t blocks = (n + 255) / 256;
+  return (unsigned)(blocks < cap ? blocks : cap);
+}
+
 // launchers of the transform kernels (defined in al_transforms.hip); return hipGetLastError() of the launch
 hipError_t launch_ir_spectra(const al_batch *b, hipStream_t stream);
 hipError_t launch_signal_spectra(const al_batch *b, hipStream_t stream);

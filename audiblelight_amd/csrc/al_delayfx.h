@@ -17,12 +17,33 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <string.h>
 
 #include "al_common.h"
+#include "al_status.h"
 
 namespace al {
 
 constexpr double DFX_PI = 3.14159265358979323846;
+
+// What the entries of these FX (and of the dynamics FX) ask of a clip and of its scalars: out of place, n >= 1, every named value
+// finite and >= 0, "feedback" below 1.  0, or the error of the first bad argument under the entry's name `fn`.
+inline int fx_check(const char *fn, const float *src, const float *dst, int64_t n, const char *const *names, const double *vals,
+                    int count) {
+  if (!src || !dst) return fail_arg(fn, "null pointer");
+  if (n < 1) return fail_arg(fn, "n must be >= 1");
+  if (fx_ranges_overlap(src, n, dst, n)) return fail_arg(fn, "dst overlaps src (out of place only)");
+  for (int i = 0; i < count; ++i) {
+    if (!isfinite(vals[i]) || vals[i] < 0.0) {
+      char why[160];
+      snprintf(why, sizeof(why), "%s must be finite and >= 0", names[i]);
+      return fail_arg(fn, why);
+    }
+    if (!strcmp(names[i], "feedback") && vals[i] >= 1.0) return fail_arg(fn, "feedback must be < 1 (unstable loop)");
+  }
+  return AL_OK;
+}
 
 // ------------------------------------------------------------------ Delay
 constexpr int DLY_THREADS = 1024;
@@ -59,6 +80,14 @@ inline DelayPlan delay_plan(int64_t n, int64_t D, double fb) {
   p.R = p.K > 0 ? (p.K + p.P - 1) / p.P : 0;
   p.phi = pow(fb, (double)p.R);
   return p;
+}
+
+inline int delay_check(const float *src, const float *dst, int64_t n, int64_t delay_samples, float feedback, float mix) {
+  static const char *const names[] = {"feedback", "mix"};
+  const double vals[] = {feedback, mix};
+  if (int e = fx_check("al_fx_delay", src, dst, n, names, vals, 2)) return e;
+  if (delay_samples < 0) return fail(AL_E_BADARG, "al_fx_delay: delay_samples must be >= 0");
+  return AL_OK;
 }
 
 // y[t] = dry x[t] + wet d[t].  Thread (g, p): residue r = blockIdx.x * G + g, chain steps k in [p R + 1, (p + 1) R] (t = r + k D).
@@ -178,6 +207,38 @@ __global__ __launch_bounds__(1024) void k_fx_chorus_fb(const ChorusJob *__restri
     }
     __syncthreads();
   }
+}
+
+// 0 with *job filled, or the error of the first bad argument.  The same job feeds k_fx_chorus_ff (feedback == 0: job->a alone).
+inline int chorus_prepare(const al_fx_mod_job &in, ChorusJob *job) {
+  static const char *const names[] = {"fs", "rate_hz", "depth", "centre_delay_ms", "feedback", "mix"};
+  const double vals[] = {in.fs, in.rate_hz, in.depth, in.centre, in.feedback, in.mix};
+  if (int e = fx_check("al_fx_chorus", in.src, in.dst, in.n, names, vals, 6)) return e;
+  const double tau_max = ceil(110.0 * in.fs / 1000.0);
+  const double b_min = floor(in.fs / 1000.0);   // tau >= fs / 1000: the 1 ms floor of the delay
+  if (!(b_min >= 1.0) || tau_max + b_min + 2.0 > (double)CHO_RING)
+    return fail(AL_E_BADARG, "al_fx_chorus: fs out of range (1000 <= fs and ceil(0.11 fs) + floor(fs / 1000) + 2 <= 16384)");
+  job->src = in.src;
+  job->dst = in.dst;
+  job->n = in.n;
+  ChorusArgs &a = job->a;
+  a.fs = in.fs;
+  a.rate = in.rate_hz;
+  a.depth10 = 10.0 * in.depth;
+  a.centre_ms = in.centre;
+  a.tau_max = tau_max;
+  a.fb = in.feedback;
+  const double m = in.mix < 1.0 ? in.mix : 1.0;   // JUCE's DryWetMixer clamps the proportion
+  a.dry = 1.0 - m;
+  a.wet = m;
+  // B = floor of a lower bound of every tau_t, one sample short of it against rounding, never below the 1 ms floor
+  const double lowest = fmin(fmax(1.0, in.centre - 10.0 * in.depth) * in.fs / 1000.0, tau_max);
+  double b = floor(lowest) - 1.0;
+  b = b > b_min ? b : b_min;
+  b = b < (double)CHO_MAX_BLOCK ? b : (double)CHO_MAX_BLOCK;
+  b = b < (double)CHO_RING - tau_max - 2.0 ? b : (double)CHO_RING - tau_max - 2.0;
+  a.block = (int64_t)b;
+  return AL_OK;
 }
 
 // ------------------------------------------------------------------ Phaser
@@ -306,6 +367,30 @@ __global__ __launch_bounds__(PH_THREADS) void k_fx_phaser(const PhaserJob *__res
       y[t4 + q] = (float)fma(a.wet, wet, a.dry * xin);
     }
   }
+}
+
+// 0 with *job filled, or the error of the first bad argument
+inline int phaser_prepare(const al_fx_mod_job &in, PhaserJob *job) {
+  static const char *const names[] = {"fs", "rate_hz", "depth", "centre_frequency_hz", "feedback", "mix"};
+  const double vals[] = {in.fs, in.rate_hz, in.depth, in.centre, in.feedback, in.mix};
+  if (int e = fx_check("al_fx_phaser", in.src, in.dst, in.n, names, vals, 6)) return e;
+  if (!(0.49 * in.fs > 20.0)) return fail(AL_E_BADARG, "al_fx_phaser: fs out of range (0.49 fs must exceed 20 Hz)");
+  const double fmax_hz = fmin(20000.0, 0.49 * in.fs);
+  job->src = in.src;
+  job->dst = in.dst;
+  job->n = in.n;
+  job->run = phaser_run_length(in.n);
+  PhaserArgs &a = job->a;
+  a.fs = in.fs;
+  a.rate = in.rate_hz;
+  a.half_depth = 0.5 * in.depth;
+  a.c = log10(in.centre / 20.0) / log10(fmax_hz / 20.0);   // -inf at fc = 0: the LFO clamps it to 0
+  a.log_ratio = log(fmax_hz / 20.0);
+  a.fb = in.feedback;
+  const double m = in.mix < 1.0 ? in.mix : 1.0;
+  a.dry = 1.0 - m;
+  a.wet = m;
+  return AL_OK;
 }
 
 }  // namespace al

@@ -19,8 +19,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "al_common.h"
+#include "al_delayfx.h"   // fx_check
+#include "al_status.h"
 
 namespace al {
 
@@ -193,6 +196,57 @@ __global__ __launch_bounds__(64) void k_fx_dynamics(const DynJob *__restrict__ t
     }
     __syncthreads();
   }
+}
+
+// ---- host side: the checks both entries share, then the stages of each
+constexpr double DYN_TWO_PI = 6.283185307179586476925286766559;
+
+// cte(ms): the one-pole coefficient of a time constant, 0 below a microsecond (JUCE's BallisticsFilter)
+inline double dyn_cte(double ms, double fs) { return ms < 1e-3 ? 0.0 : exp(-DYN_TWO_PI * 1000.0 / (ms * fs)); }
+
+inline DynStage dyn_stage(double threshold_db, double ratio, double cA, double cR) {
+  const double T = pow(10.0, threshold_db / 20.0);
+  return DynStage{T, 1.0 / T, 1.0 / ratio - 1.0, cA, cR};
+}
+
+// 0 with the clip of `in` in a zeroed *job, or the error of the first bad argument
+template <class Job>
+inline int dyn_check(const char *fn, const Job &in, bool limiter, double ratio, double attack_ms, DynJob *job) {
+  if (int e = fx_check(fn, in.src, in.dst, in.n, nullptr, nullptr, 0)) return e;
+  const char *why = nullptr;
+  if (!isfinite(in.fs) || !(in.fs > 0.0)) why = "fs must be finite and > 0";
+  else if (!isfinite(in.threshold_db) || !(in.threshold_db > -200.0)) why = "threshold_db must be finite and > -200";
+  else if (limiter && !(in.threshold_db < 100.0)) why = "threshold_db must be < 100";
+  else if (!isfinite(ratio) || !(ratio >= 1.0)) why = "ratio must be finite and >= 1";
+  else if (!isfinite(attack_ms) || attack_ms < 0.0) why = "attack_ms must be finite and >= 0";
+  else if (!isfinite(in.release_ms) || in.release_ms < 0.0) why = "release_ms must be finite and >= 0";
+  if (why) return fail_arg(fn, why);
+  memset(job, 0, sizeof(*job));
+  job->src = in.src;
+  job->dst = in.dst;
+  job->n = in.n;
+  return AL_OK;
+}
+
+inline int compressor_prepare(const al_fx_compressor_job &in, DynJob *job) {
+  if (int e = dyn_check("al_fx_compressor", in, false, in.ratio, in.attack_ms, job)) return e;
+  job->n_stages = 1;
+  job->st[0] = dyn_stage(in.threshold_db, in.ratio, dyn_cte(in.attack_ms, in.fs), dyn_cte(in.release_ms, in.fs));
+  job->st[1] = job->st[0];   // not walked
+  job->out_gain = 1.0;
+  job->ceiling = INFINITY;
+  return AL_OK;
+}
+
+// JUCE's dsp::Limiter: a fixed first compressor, the caller's second one (attack 0.001 ms: cA = 0), the make-up gain, the clamp
+inline int limiter_prepare(const al_fx_limiter_job &in, DynJob *job) {
+  if (int e = dyn_check("al_fx_limiter", in, true, 1000.0, 0.0, job)) return e;
+  job->n_stages = 2;
+  job->st[0] = dyn_stage(-10.0, 4.0, dyn_cte(2.0, in.fs), dyn_cte(200.0, in.fs));
+  job->st[1] = dyn_stage(in.threshold_db, 1000.0, 0.0, dyn_cte(in.release_ms, in.fs));
+  job->out_gain = pow(10.0, 10.0 * (1.0 - 1.0 / 4.0) / 40.0) * pow(10.0, -in.threshold_db / 20.0);
+  job->ceiling = 1.0;
+  return AL_OK;
 }
 
 }  // namespace al

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "al_common.h"
+#include "al_status.h"
 
 namespace al {
 
@@ -233,6 +234,43 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
     const int ts = t + s * ISM_THREADS;
     if (ts < job.pitch) row[ts] = ts < job.ir_len ? (float)acc[s] : 0.f;
   }
+}
+
+// al_ism_shoebox's arguments as the kernel's job: 0 with *job filled, or the error of the first bad argument
+inline int ism_prepare(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
+                       const double *beta, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, float *out,
+                       IsmJob *job) {
+  if (!sources || !capsules || !L || !beta || !out) return fail(AL_E_BADARG, "al_ism_shoebox: null pointer");
+  if (n_sources < 1 || n_capsules < 1) return fail(AL_E_BADARG, "al_ism_shoebox: n_sources and n_capsules must be >= 1");
+  if (ir_len < 1) return fail(AL_E_BADARG, "al_ism_shoebox: ir_len must be >= 1");
+  if (pitch < ir_len || (pitch & 3)) return fail(AL_E_BADARG, "al_ism_shoebox: pitch must be >= ir_len and a multiple of 4");
+  if (max_order < -1) return fail(AL_E_BADARG, "al_ism_shoebox: max_order must be >= 0, or -1 for none");
+  if (!isfinite(c) || !(c > 0.0) || !isfinite(fs) || !(fs > 0.0)) return fail(AL_E_BADARG, "al_ism_shoebox: c and fs must be finite and positive");
+  for (int i = 0; i < 3; ++i) {
+    if (!isfinite(L[i]) || !(L[i] > 0.0)) return fail(AL_E_BADARG, "al_ism_shoebox: room dimensions must be finite and positive");
+    if (!(c * ((double)ir_len + 42.0) / fs / L[i] + 2.0 <= ISM_MAX_HALF_WIDTH))
+      return fail(AL_E_BADARG, "al_ism_shoebox: c (ir_len + 42) / fs spans more than 2^20 mirror cells of the room");
+    job->L[i] = L[i];
+  }
+  for (int i = 0; i < 6; ++i) {
+    if (!(beta[i] >= 0.0 && beta[i] <= 1.0)) return fail(AL_E_BADARG, "al_ism_shoebox: reflection coefficients must be in [0, 1]");
+    job->beta_zero[i] = beta[i] == 0.0;
+    job->ln_beta[i] = beta[i] == 0.0 ? 0.0 : log(beta[i]);
+  }
+  job->n_tiles = (pitch + ISM_TILE - 1) / ISM_TILE;
+  if ((int64_t)job->n_tiles * n_sources * n_capsules > 0x7fffffff)
+    return fail(AL_E_BADARG, "al_ism_shoebox: more than 2^31 - 1 workgroups (tiles of 256 samples x pairs): split the call");
+  job->sources = sources;
+  job->capsules = capsules;
+  job->out = out;
+  job->n_sources = n_sources;
+  job->n_capsules = n_capsules;
+  job->ir_len = ir_len;
+  job->pitch = pitch;
+  job->max_order = max_order;
+  job->c = c;
+  job->fs = fs;
+  return AL_OK;
 }
 
 inline void launch_ism_shoebox(const IsmJob &job, hipStream_t stream) {

@@ -1,8 +1,12 @@
 // C ABI of the MI355X synthesis path (gfx950 only): every extern "C" entry point of include/audiblelight_hip.h that launches
-// device code, each one argument validation plus launch.  No kernel and no launch planning lives here: kernels, their device
-// helpers and the host-side choice of instantiation and grid are in the per-domain headers included below (al_mac.h accumulate,
-// al_levels.h level scalars, al_mixdown.h, al_rows.h, al_clipfx.h / al_sos.h / al_delayfx.h / al_dynfx.h / al_stretchfx.h FX, al_ingest.h, al_ism.h, al_bigfft.h, al_stft.h);
-// the FFT kernels of the pipeline are the other translation unit, al_transforms.hip.  See DESIGN.md for the data layout and
+// device code.  No kernel, no launch planning and no definition of an effect lives here.  Each per-domain header included below
+// owns its kernels, their device helpers and its host side: the choice of instantiation and grid (al_mac.h plan_mac, al_delayfx.h
+// delay_plan, al_stretchfx.h pv_plan) and, for the FX, time-stretch and image-source entries, the checks and derivations that turn
+// the caller's arguments into the kernel's job (the *_prepare and *_check functions of al_clipfx.h, al_sos.h, al_delayfx.h,
+// al_dynfx.h, al_stretchfx.h, al_ism.h), refusing through al_status.h.  What is left to an entry is: prepare, launch, check_launch;
+// the entries without a prepare check their few arguments in place.  The FX that a batched launch can run are ONE TABLE (FX_KINDS
+// below): a row per batched kind, read by al_fx_batch_desc_bytes / _pack / _launch and by the single-clip entries alike.
+// The FFT kernels of the pipeline are the other translation unit, al_transforms.hip.  See DESIGN.md for the data layout and
 // per-kernel rooflines.
 //
 // Pipeline per batch of events (uniformly partitioned overlap-save, block B = M = 2^LOG2M):
@@ -31,27 +35,16 @@
 #include "al_mixdown.h"
 #include "al_rows.h"
 #include "al_sos.h"
+#include "al_status.h"
 #include "al_stft.h"
 #include "al_stretchfx.h"
 
 // ====================================================================== C ABI
 namespace {
-thread_local char g_err[256] = "";
-
-int fail(int code, const char *msg) {
-  snprintf(g_err, sizeof(g_err), "%s", msg);
-  return code;
-}
-
-int check_error(hipError_t e, const char *what) {
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return AL_E_HIP;
-  }
-  return AL_OK;
-}
-
-int check_launch(const char *what) { return check_error(hipGetLastError(), what); }
+using al::check_error;
+using al::check_launch;
+using al::fail;
+using al::grid_1d;
 
 int check_batch(const al_batch *b) {
   if (!b) return fail(AL_E_BADARG, "null batch");
@@ -68,11 +61,70 @@ int check_batch(const al_batch *b) {
   return AL_OK;
 }
 
+// ---- the FX a batched launch can run: one row per kind.  Job: the public job struct of audiblelight_hip.h; Desc: what
+// Prepare derives from it, the packed descriptor that Kernel reads -- workgroup b from table[b], or `one` by value when the table
+// is null (a single clip, grid of 1).  A new scan FX is one header with kernel, descriptor and prepare, one public job struct, and
+// one row here.
+struct FxKind {
+  int32_t kind;
+  size_t job_bytes, desc_bytes;
+  int (*prepare)(const void *job, void *desc);   // 0, or the error of the job's first bad argument
+  void (*launch)(const void *table, const void *one, unsigned count, hipStream_t stream);
+  const char *kernel;                            // its name, for check_launch
+  const float *(*src)(const void *job);
+  const float *(*dst)(const void *job);
+  int64_t (*n)(const void *job);
+};
+
+template <int32_t Kind, class JobT, class DescT, int (*Prepare)(const JobT &, DescT *), void (*Kernel)(const DescT *, DescT), int Threads>
+struct FxRow {
+  using Job = JobT;
+  using Desc = DescT;
+  static constexpr int32_t KIND = Kind;
+  static int prepare(const void *job, void *desc) { return Prepare(*static_cast<const Job *>(job), static_cast<Desc *>(desc)); }
+  static void launch(const void *table, const void *one, unsigned count, hipStream_t stream) {
+    hipLaunchKernelGGL(Kernel, dim3(count), dim3(Threads), 0, stream, static_cast<const Desc *>(table),
+                       one ? *static_cast<const Desc *>(one) : Desc{});
+  }
+  // by name: a job struct without src, dst and n does not compile
+  static const float *src(const void *job) { return static_cast<const Job *>(job)->src; }
+  static const float *dst(const void *job) { return static_cast<const Job *>(job)->dst; }
+  static int64_t n(const void *job) { return static_cast<const Job *>(job)->n; }
+  static constexpr FxKind row(const char *kernel) { return {Kind, sizeof(Job), sizeof(Desc), prepare, launch, kernel, src, dst, n}; }
+};
+
+using SosRow = FxRow<AL_FXB_SOS, al_fx_sos_job, al::SosJob, al::sos_prepare, al::k_fx_sos, al::SOS_THREADS>;
+using ChorusRow = FxRow<AL_FXB_CHORUS, al_fx_mod_job, al::ChorusJob, al::chorus_prepare, al::k_fx_chorus_fb, al::CHO_THREADS>;
+using PhaserRow = FxRow<AL_FXB_PHASER, al_fx_mod_job, al::PhaserJob, al::phaser_prepare, al::k_fx_phaser, al::PH_THREADS>;
+using DeemphRow = FxRow<AL_FXB_DEEMPH, al_fx_deemph_job, al::DeemphJob, al::deemph_prepare, al::k_fx_deemph, 1024>;
+using CompressorRow = FxRow<AL_FXB_COMPRESSOR, al_fx_compressor_job, al::DynJob, al::compressor_prepare, al::k_fx_dynamics, al::DYN_LANES>;
+using LimiterRow = FxRow<AL_FXB_LIMITER, al_fx_limiter_job, al::DynJob, al::limiter_prepare, al::k_fx_dynamics, al::DYN_LANES>;
+
+const FxKind FX_KINDS[] = {SosRow::row("k_fx_sos"),       ChorusRow::row("k_fx_chorus_fb"),    PhaserRow::row("k_fx_phaser"),
+                           DeemphRow::row("k_fx_deemph"), CompressorRow::row("k_fx_dynamics"), LimiterRow::row("k_fx_dynamics")};
+
+const FxKind *fx_kind(int32_t kind) {
+  for (const FxKind &row : FX_KINDS)
+    if (row.kind == kind) return &row;
+  return nullptr;
+}
+
+// one clip through its row, exactly as a batch of one job: the same prepare, the same kernel, the descriptor by value
+template <class Row>
+int fx_single(const typename Row::Job &in, al_stream_t stream) {
+  const FxKind *row = fx_kind(Row::KIND);
+  if (!row) return fail(AL_E_UNSUPPORTED, "fx_single: this kind has no row in FX_KINDS");
+  typename Row::Desc desc;
+  if (int rc = row->prepare(&in, &desc)) return rc;
+  row->launch(nullptr, &desc, 1, (hipStream_t)stream);
+  return check_launch(row->kernel);
+}
+
 }  // namespace
 
 extern "C" {
 
-const char *al_last_error(void) { return g_err; }
+const char *al_last_error(void) { return al::g_err; }
 int al_abi_version(void) { return AL_ABI_VERSION; }
 
 int64_t al_twiddle_bytes(int log2_block) {
@@ -211,16 +263,14 @@ int al_mixdown(const al_mix *m, al_stream_t stream) {
 int al_scale_rows(float *x, int64_t n, const float *scale, al_stream_t stream) {
   if (!x || !scale || n < 0) return fail(AL_E_BADARG, "bad scale arguments");
   if (n == 0) return AL_OK;
-  const int64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(al::k_scale, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, (hipStream_t)stream, x, n, scale);
+  hipLaunchKernelGGL(al::k_scale, dim3(grid_1d(n, 8192)), dim3(256), 0, (hipStream_t)stream, x, n, scale);
   return check_launch("k_scale");
 }
 
 int al_scale_rows_f64(float *x, int64_t n, const double *scale, al_stream_t stream) {
   if (!x || !scale || n < 0) return fail(AL_E_BADARG, "bad scale arguments");
   if (n == 0) return AL_OK;
-  const int64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(al::k_scale_d, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, (hipStream_t)stream, x, n, scale);
+  hipLaunchKernelGGL(al::k_scale_d, dim3(grid_1d(n, 8192)), dim3(256), 0, (hipStream_t)stream, x, n, scale);
   return check_launch("k_scale_d");
 }
 
@@ -242,8 +292,7 @@ int al_peak_scale(const float *x, int64_t n, float prescale, float *scale_out, a
 int al_axpy(float *y, const float *x, const float *a_dev, int64_t n, al_stream_t stream) {
   if (!x || !y || !a_dev || n < 0) return fail(AL_E_BADARG, "bad axpy arguments");
   if (n == 0) return AL_OK;
-  const int64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(al::k_axpy, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, (hipStream_t)stream, y, x, a_dev, n);
+  hipLaunchKernelGGL(al::k_axpy, dim3(grid_1d(n, 8192)), dim3(256), 0, (hipStream_t)stream, y, x, a_dev, n);
   return check_launch("k_axpy");
 }
 
@@ -262,233 +311,18 @@ int al_row_stats(const float *x, int32_t rows, int64_t cols, float *partials, do
   return check_launch("k_row_stats_final");
 }
 
-// ---- FX: the checks and derivations of every entry whose kernel a batched launch can run, shared by the single-clip entries and
-// al_fx_batch_pack.  Each returns 0 with *job filled, or the error of the first bad argument.
-namespace {
-bool fx_ranges_overlap(const float *a, int64_t na, const float *b, int64_t nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + (uintptr_t)nb * sizeof(float) && pb < pa + (uintptr_t)na * sizeof(float);
-}
-
-bool fx_overlap(const float *a, const float *b, int64_t n) { return fx_ranges_overlap(a, n, b, n); }
-
-// 0, or the error for the first bad argument
-int fx_check(const char *fn, const float *src, const float *dst, int64_t n, const char *const *names, const double *vals,
-             int count) {
-  char msg[200];
-  if (!src || !dst) {
-    snprintf(msg, sizeof(msg), "%s: null pointer", fn);
-    return fail(AL_E_BADARG, msg);
-  }
-  if (n < 1) {
-    snprintf(msg, sizeof(msg), "%s: n must be >= 1", fn);
-    return fail(AL_E_BADARG, msg);
-  }
-  if (fx_overlap(src, dst, n)) {
-    snprintf(msg, sizeof(msg), "%s: dst overlaps src (out of place only)", fn);
-    return fail(AL_E_BADARG, msg);
-  }
-  for (int i = 0; i < count; ++i) {
-    if (!isfinite(vals[i]) || vals[i] < 0.0) {
-      snprintf(msg, sizeof(msg), "%s: %s must be finite and >= 0", fn, names[i]);
-      return fail(AL_E_BADARG, msg);
-    }
-    if (!strcmp(names[i], "feedback") && vals[i] >= 1.0) {
-      snprintf(msg, sizeof(msg), "%s: feedback must be < 1 (unstable loop)", fn);
-      return fail(AL_E_BADARG, msg);
-    }
-  }
-  return AL_OK;
-}
-
-// al_fx_apply's checks of its clip arguments
-int fx_apply_check(int op, const float *src, const float *dst, int64_t n) {
-  if (!src || !dst || n <= 0) return fail(AL_E_BADARG, "bad fx arguments");
-  if (op < AL_FX_GAIN || op > AL_FX_DEEMPH) return fail(AL_E_UNSUPPORTED, "unknown fx op");
-  const bool out_of_place = (op == AL_FX_REVERSE || op == AL_FX_PREEMPH || op == AL_FX_DEEMPH);
-  if (out_of_place && src == dst) return fail(AL_E_BADARG, "this fx op needs dst != src");
-  if ((op == AL_FX_PREEMPH || op == AL_FX_DEEMPH) && n < 2) return fail(AL_E_BADARG, "emphasis filters need n >= 2");
-  return AL_OK;
-}
-
-int deemph_prepare(const float *src, float *dst, int64_t n, float c, al::DeemphJob *job) {
-  if (int rc = fx_apply_check(AL_FX_DEEMPH, src, dst, n)) return rc;
-  *job = al::DeemphJob{src, dst, n, c};
-  return AL_OK;
-}
-
-int sos_prepare(const float *src, float *dst, int64_t n, const double *sos, int32_t n_sections, al::SosJob *job) {
-  if (!src || !dst || !sos) return fail(AL_E_BADARG, "al_fx_sos: null pointer");
-  if (n < 1) return fail(AL_E_BADARG, "al_fx_sos: n must be >= 1");
-  if (n_sections < 1 || n_sections > AL_SOS_MAX_SECTIONS)
-    return fail(AL_E_BADARG, "al_fx_sos: n_sections must be in 1..AL_SOS_MAX_SECTIONS (16); split longer cascades");
-  const int64_t run = al::sos_run_length(n);
-  memset(job, 0, sizeof(*job));
-  job->src = src;
-  job->dst = dst;
-  job->n = n;
-  job->run = run;
-  al::SosArgs &a = job->a;
-  a.n_sections = n_sections;
-  char msg[160];
-  for (int k = 0; k < n_sections; ++k) {
-    const double *row = sos + 6 * k;
-    for (int i = 0; i < 6; ++i)
-      if (!isfinite(row[i])) {
-        snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a non-finite coefficient", k);
-        return fail(AL_E_BADARG, msg);
-      }
-    if (row[3] == 0.0) {
-      snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a0 == 0", k);
-      return fail(AL_E_BADARG, msg);
-    }
-    const double c[5] = {row[0] / row[3], row[1] / row[3], row[2] / row[3], row[4] / row[3], row[5] / row[3]};
-    for (int i = 0; i < 5; ++i)
-      if (!isfinite(c[i])) {
-        snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a non-finite coefficient after division by a0", k);
-        return fail(AL_E_BADARG, msg);
-      }
-    // both roots of z^2 + a1 z + a2 inside the unit circle (Jury): |a2| < 1 and |a1| < 1 + a2
-    if (!(fabs(c[4]) < 1.0 && fabs(c[3]) < 1.0 + c[4])) {
-      snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a pole of magnitude >= 1 (unstable filter)", k);
-      return fail(AL_E_BADARG, msg);
-    }
-    for (int i = 0; i < 5; ++i) a.c[k][i] = c[i];
-    al::sos_transition_power(c[3], c[4], run, a.phi[k]);
-  }
-  return AL_OK;
-}
-
-// delay and modulation FX: out of place, every parameter finite and >= 0, feedback < 1
-int chorus_prepare(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_delay_ms,
-                   double feedback, double mix, al::ChorusJob *job) {
-  static const char *const names[] = {"fs", "rate_hz", "depth", "centre_delay_ms", "feedback", "mix"};
-  const double vals[] = {fs, rate_hz, depth, centre_delay_ms, feedback, mix};
-  if (int e = fx_check("al_fx_chorus", src, dst, n, names, vals, 6)) return e;
-  const double tau_max = ceil(110.0 * fs / 1000.0);
-  const double b_min = floor(fs / 1000.0);   // tau >= fs / 1000: the 1 ms floor of the delay
-  if (!(b_min >= 1.0) || tau_max + b_min + 2.0 > (double)al::CHO_RING)
-    return fail(AL_E_BADARG, "al_fx_chorus: fs out of range (1000 <= fs and ceil(0.11 fs) + floor(fs / 1000) + 2 <= 16384)");
-  job->src = src;
-  job->dst = dst;
-  job->n = n;
-  al::ChorusArgs &a = job->a;
-  a.fs = fs;
-  a.rate = rate_hz;
-  a.depth10 = 10.0 * depth;
-  a.centre_ms = centre_delay_ms;
-  a.tau_max = tau_max;
-  a.fb = feedback;
-  const double m = mix < 1.0 ? mix : 1.0;   // JUCE's DryWetMixer clamps the proportion
-  a.dry = 1.0 - m;
-  a.wet = m;
-  // B = floor of a lower bound of every tau_t, one sample short of it against rounding, never below the 1 ms floor
-  const double lowest = fmin(fmax(1.0, centre_delay_ms - 10.0 * depth) * fs / 1000.0, tau_max);
-  double b = floor(lowest) - 1.0;
-  b = b > b_min ? b : b_min;
-  b = b < (double)al::CHO_MAX_BLOCK ? b : (double)al::CHO_MAX_BLOCK;
-  b = b < (double)al::CHO_RING - tau_max - 2.0 ? b : (double)al::CHO_RING - tau_max - 2.0;
-  a.block = (int64_t)b;
-  return AL_OK;
-}
-
-int phaser_prepare(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_frequency_hz,
-                   double feedback, double mix, al::PhaserJob *job) {
-  static const char *const names[] = {"fs", "rate_hz", "depth", "centre_frequency_hz", "feedback", "mix"};
-  const double vals[] = {fs, rate_hz, depth, centre_frequency_hz, feedback, mix};
-  if (int e = fx_check("al_fx_phaser", src, dst, n, names, vals, 6)) return e;
-  if (!(0.49 * fs > 20.0)) return fail(AL_E_BADARG, "al_fx_phaser: fs out of range (0.49 fs must exceed 20 Hz)");
-  const double fmax_hz = fmin(20000.0, 0.49 * fs);
-  job->src = src;
-  job->dst = dst;
-  job->n = n;
-  job->run = al::phaser_run_length(n);
-  al::PhaserArgs &a = job->a;
-  a.fs = fs;
-  a.rate = rate_hz;
-  a.half_depth = 0.5 * depth;
-  a.c = log10(centre_frequency_hz / 20.0) / log10(fmax_hz / 20.0);   // -inf at fc = 0: the LFO clamps it to 0
-  a.log_ratio = log(fmax_hz / 20.0);
-  a.fb = feedback;
-  const double m = mix < 1.0 ? mix : 1.0;
-  a.dry = 1.0 - m;
-  a.wet = m;
-  return AL_OK;
-}
-// dynamics FX: out of place; the checks both entries share, then the stages
-constexpr double DYN_TWO_PI = 6.283185307179586476925286766559;
-
-// cte(ms): the one-pole coefficient of a time constant, 0 below a microsecond (JUCE's BallisticsFilter)
-double dyn_cte(double ms, double fs) { return ms < 1e-3 ? 0.0 : exp(-DYN_TWO_PI * 1000.0 / (ms * fs)); }
-
-al::DynStage dyn_stage(double threshold_db, double ratio, double cA, double cR) {
-  const double T = pow(10.0, threshold_db / 20.0);
-  return al::DynStage{T, 1.0 / T, 1.0 / ratio - 1.0, cA, cR};
-}
-
-int dyn_check(const char *fn, const float *src, const float *dst, int64_t n, double fs, double threshold_db, bool limiter,
-              double ratio, double attack_ms, double release_ms) {
-  if (int e = fx_check(fn, src, dst, n, nullptr, nullptr, 0)) return e;
-  char msg[200];
-  const char *why = nullptr;
-  if (!isfinite(fs) || !(fs > 0.0)) why = "fs must be finite and > 0";
-  else if (!isfinite(threshold_db) || !(threshold_db > -200.0)) why = "threshold_db must be finite and > -200";
-  else if (limiter && !(threshold_db < 100.0)) why = "threshold_db must be < 100";
-  else if (!isfinite(ratio) || !(ratio >= 1.0)) why = "ratio must be finite and >= 1";
-  else if (!isfinite(attack_ms) || attack_ms < 0.0) why = "attack_ms must be finite and >= 0";
-  else if (!isfinite(release_ms) || release_ms < 0.0) why = "release_ms must be finite and >= 0";
-  if (!why) return AL_OK;
-  snprintf(msg, sizeof(msg), "%s: %s", fn, why);
-  return fail(AL_E_BADARG, msg);
-}
-
-int compressor_prepare(const float *src, float *dst, int64_t n, double fs, double threshold_db, double ratio, double attack_ms,
-                       double release_ms, al::DynJob *job) {
-  if (int e = dyn_check("al_fx_compressor", src, dst, n, fs, threshold_db, false, ratio, attack_ms, release_ms)) return e;
-  memset(job, 0, sizeof(*job));
-  job->src = src;
-  job->dst = dst;
-  job->n = n;
-  job->n_stages = 1;
-  job->st[0] = dyn_stage(threshold_db, ratio, dyn_cte(attack_ms, fs), dyn_cte(release_ms, fs));
-  job->st[1] = job->st[0];   // not walked
-  job->out_gain = 1.0;
-  job->ceiling = INFINITY;
-  return AL_OK;
-}
-
-// JUCE's dsp::Limiter: a fixed first compressor, the caller's second one (attack 0.001 ms: cA = 0), the make-up gain, the clamp
-int limiter_prepare(const float *src, float *dst, int64_t n, double fs, double threshold_db, double release_ms, al::DynJob *job) {
-  if (int e = dyn_check("al_fx_limiter", src, dst, n, fs, threshold_db, true, 1000.0, 0.0, release_ms)) return e;
-  memset(job, 0, sizeof(*job));
-  job->src = src;
-  job->dst = dst;
-  job->n = n;
-  job->n_stages = 2;
-  job->st[0] = dyn_stage(-10.0, 4.0, dyn_cte(2.0, fs), dyn_cte(200.0, fs));
-  job->st[1] = dyn_stage(threshold_db, 1000.0, 0.0, dyn_cte(release_ms, fs));
-  job->out_gain = pow(10.0, 10.0 * (1.0 - 1.0 / 4.0) / 40.0) * pow(10.0, -threshold_db / 20.0);
-  job->ceiling = 1.0;
-  return AL_OK;
-}
-}  // namespace
-
+// ---- FX.  The scans and walks run through their row of FX_KINDS; the pointwise ops, the frame shuffle, the delay and the
+// feed-forward chorus are grid-wide launches of their own.
 int al_fx_apply(int op, const float *src, float *dst, int64_t n, const float *params, const int32_t *iparams,
                 al_stream_t stream) {
-  if (int rc = fx_apply_check(op, src, dst, n)) return rc;
+  if (int rc = al::fx_apply_check(op, src, dst, n)) return rc;
   al::FxArgs a{op, params ? params[0] : 0.f, 0, 0, AL_FADE_NONE, AL_FADE_NONE};
   if (op == AL_FX_FADE) {
     if (!iparams) return fail(AL_E_BADARG, "fade needs iparams");
     a.n_in = iparams[0]; a.n_out = iparams[1]; a.shape_in = iparams[2]; a.shape_out = iparams[3];
   }
-  if (op == AL_FX_DEEMPH) {
-    al::DeemphJob job;
-    if (int rc = deemph_prepare(src, dst, n, a.p0, &job)) return rc;
-    hipLaunchKernelGGL(al::k_fx_deemph, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const al::DeemphJob *)nullptr, job);
-    return check_launch("k_fx_deemph");
-  }
-  const int64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(al::k_fx_pointwise, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
+  if (op == AL_FX_DEEMPH) return fx_single<DeemphRow>(al_fx_deemph_job{src, dst, n, a.p0, 0}, stream);
+  hipLaunchKernelGGL(al::k_fx_pointwise, dim3(grid_1d(n, 4096)), dim3(256), 0,
                      (hipStream_t)stream, src, dst, n, a);
   return check_launch("k_fx_pointwise");
 }
@@ -497,24 +331,17 @@ int al_fx_frame_shuffle(const float *src, float *dst, int64_t n, int32_t frame_l
                         const int32_t *rows, int32_t n_rows, al_stream_t stream) {
   if (!src || !dst || !rows || n <= 0 || frame_len <= 0 || row_len <= 0 || n_rows <= 0 || src == dst)
     return fail(AL_E_BADARG, "bad frame_shuffle arguments");
-  const int64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(al::k_frame_shuffle, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
+  hipLaunchKernelGGL(al::k_frame_shuffle, dim3(grid_1d(n, 4096)), dim3(256), 0,
                      (hipStream_t)stream, src, dst, n, frame_len, row_len, rows, n_rows);
   return check_launch("k_frame_shuffle");
 }
 
 int al_fx_sos(const float *src, float *dst, int64_t n, const double *sos, int32_t n_sections, al_stream_t stream) {
-  al::SosJob job;
-  if (int rc = sos_prepare(src, dst, n, sos, n_sections, &job)) return rc;
-  hipLaunchKernelGGL(al::k_fx_sos, dim3(1), dim3(al::SOS_THREADS), 0, (hipStream_t)stream, (const al::SosJob *)nullptr, job);
-  return check_launch("k_fx_sos");
+  return fx_single<SosRow>(al_fx_sos_job{src, dst, n, sos, n_sections, 0}, stream);
 }
 
 int al_fx_delay(const float *src, float *dst, int64_t n, int64_t delay_samples, float feedback, float mix, al_stream_t stream) {
-  static const char *const names[] = {"feedback", "mix"};
-  const double vals[] = {feedback, mix};
-  if (int e = fx_check("al_fx_delay", src, dst, n, names, vals, 2)) return e;
-  if (delay_samples < 0) return fail(AL_E_BADARG, "al_fx_delay: delay_samples must be >= 0");
+  if (int rc = al::delay_check(src, dst, n, delay_samples, feedback, mix)) return rc;
   const al::DelayPlan pl = al::delay_plan(n, delay_samples, (double)feedback);
   const int64_t grid = (pl.residues + pl.G - 1) / pl.G;
   hipLaunchKernelGGL(al::k_fx_delay, dim3((unsigned)grid), dim3(pl.G * pl.P), 0, (hipStream_t)stream, src, dst, n, pl,
@@ -524,171 +351,80 @@ int al_fx_delay(const float *src, float *dst, int64_t n, int64_t delay_samples, 
 
 int al_fx_chorus(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_delay_ms,
                  double feedback, double mix, al_stream_t stream) {
-  al::ChorusJob job;
-  if (int rc = chorus_prepare(src, dst, n, fs, rate_hz, depth, centre_delay_ms, feedback, mix, &job)) return rc;
-  if (feedback == 0.0) {
-    const int64_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(al::k_fx_chorus_ff, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0,
-                       (hipStream_t)stream, src, dst, n, job.a);
-    return check_launch("k_fx_chorus_ff");
-  }
-  hipLaunchKernelGGL(al::k_fx_chorus_fb, dim3(1), dim3(al::CHO_THREADS), 0, (hipStream_t)stream, (const al::ChorusJob *)nullptr, job);
-  return check_launch("k_fx_chorus_fb");
+  const al_fx_mod_job in{src, dst, n, fs, rate_hz, depth, centre_delay_ms, feedback, mix};
+  if (feedback != 0.0) return fx_single<ChorusRow>(in, stream);
+  al::ChorusJob job;   // no feedback: the same prepare, then the gather runs grid-wide
+  if (int rc = al::chorus_prepare(in, &job)) return rc;
+  hipLaunchKernelGGL(al::k_fx_chorus_ff, dim3(grid_1d(n, 8192)), dim3(256), 0, (hipStream_t)stream, src, dst, n, job.a);
+  return check_launch("k_fx_chorus_ff");
 }
 
 int al_fx_phaser(const float *src, float *dst, int64_t n, double fs, double rate_hz, double depth, double centre_frequency_hz,
                  double feedback, double mix, al_stream_t stream) {
-  al::PhaserJob job;
-  if (int rc = phaser_prepare(src, dst, n, fs, rate_hz, depth, centre_frequency_hz, feedback, mix, &job)) return rc;
-  hipLaunchKernelGGL(al::k_fx_phaser, dim3(1), dim3(al::PH_THREADS), 0, (hipStream_t)stream, (const al::PhaserJob *)nullptr, job);
-  return check_launch("k_fx_phaser");
+  return fx_single<PhaserRow>(al_fx_mod_job{src, dst, n, fs, rate_hz, depth, centre_frequency_hz, feedback, mix}, stream);
 }
 
 int al_fx_compressor(const float *src, float *dst, int64_t n, double fs, double threshold_db, double ratio, double attack_ms,
                      double release_ms, al_stream_t stream) {
-  al::DynJob job;
-  if (int rc = compressor_prepare(src, dst, n, fs, threshold_db, ratio, attack_ms, release_ms, &job)) return rc;
-  hipLaunchKernelGGL(al::k_fx_dynamics, dim3(1), dim3(al::DYN_LANES), 0, (hipStream_t)stream, (const al::DynJob *)nullptr, job);
-  return check_launch("k_fx_dynamics");
+  return fx_single<CompressorRow>(al_fx_compressor_job{src, dst, n, fs, threshold_db, ratio, attack_ms, release_ms}, stream);
 }
 
 int al_fx_limiter(const float *src, float *dst, int64_t n, double fs, double threshold_db, double release_ms, al_stream_t stream) {
-  al::DynJob job;
-  if (int rc = limiter_prepare(src, dst, n, fs, threshold_db, release_ms, &job)) return rc;
-  hipLaunchKernelGGL(al::k_fx_dynamics, dim3(1), dim3(al::DYN_LANES), 0, (hipStream_t)stream, (const al::DynJob *)nullptr, job);
-  return check_launch("k_fx_dynamics");
+  return fx_single<LimiterRow>(al_fx_limiter_job{src, dst, n, fs, threshold_db, release_ms}, stream);
 }
 
 // ---- time-stretch FX (phase vocoder, Kaiser-windowed sinc resampler): DESIGN.md "Time-stretch FX"
-namespace {
-// 0, or the error of the first bad pointer or length; src of n samples, dst of n_out
-int stretch_check(const char *fn, const float *src, int64_t n, const float *dst, int64_t n_out, const char *n_name,
-                  const char *n_out_name, const void *workspace, bool needs_workspace) {
-  char msg[200];
-  if (!src || !dst || (needs_workspace && !workspace)) snprintf(msg, sizeof(msg), "%s: null pointer", fn);
-  else if (n < 1) snprintf(msg, sizeof(msg), "%s: %s must be >= 1", fn, n_name);
-  else if (n_out < 1) snprintf(msg, sizeof(msg), "%s: %s must be >= 1", fn, n_out_name);
-  else return AL_OK;
-  return fail(AL_E_BADARG, msg);
-}
-
-int stretch_overlap_check(const char *fn, const float *src, int64_t n, const float *dst, int64_t n_out) {
-  if (!fx_ranges_overlap(src, n, dst, n_out)) return AL_OK;
-  char msg[200];
-  snprintf(msg, sizeof(msg), "%s: dst overlaps src (out of place only)", fn);
-  return fail(AL_E_BADARG, msg);
-}
-
-// 0, or the error of a bad (n, rate, n_fft): the geometry both time-stretch entries derive
-int stretch_geometry_check(const char *fn, int64_t n, double rate, int32_t n_fft) {
-  char msg[200];
-  const char *why = nullptr;
-  if (!al::pv_fft_ok(n_fft)) why = "n_fft must be a power of two in [64, 4096]";
-  else if (!isfinite(rate) || rate < 0.25 || rate > 4.0) why = "rate must be finite and in [0.25, 4]";
-  else if (al::pv_frames_in(n, n_fft) > al::PV_MAX_FRAMES) why = "too many analysis frames (F = 1 + n / hop must be <= 2^30)";
-  else if (al::pv_frames_out(al::pv_frames_in(n, n_fft), rate) > al::PV_MAX_FRAMES) why = "too many output frames (T must be <= 2^30)";
-  if (!why) return AL_OK;
-  snprintf(msg, sizeof(msg), "%s: %s", fn, why);
-  return fail(AL_E_BADARG, msg);
-}
-}  // namespace
-
 int64_t al_fx_time_stretch_workspace_floats(int64_t n, double rate, int32_t n_fft) {
-  if (n < 1 || stretch_geometry_check("al_fx_time_stretch_workspace_floats", n, rate, n_fft)) return 0;
+  if (n < 1 || al::stretch_geometry_check("al_fx_time_stretch_workspace_floats", n, rate, n_fft)) return 0;
   return al::pv_plan(n, rate, n_fft).floats;
 }
 
 int al_fx_time_stretch(const float *src, int64_t n, float *dst, int64_t n_out, double rate, int32_t n_fft, float *workspace,
                        al_stream_t stream) {
-  if (int rc = stretch_check("al_fx_time_stretch", src, n, dst, n_out, "n", "n_out", workspace, true)) return rc;
-  if (int rc = stretch_geometry_check("al_fx_time_stretch", n, rate, n_fft)) return rc;   // before the ranges: it bounds n
-  if (int rc = stretch_overlap_check("al_fx_time_stretch", src, n, dst, n_out)) return rc;
+  if (int rc = al::stretch_check("al_fx_time_stretch", src, n, dst, n_out, "n", "n_out", workspace, true)) return rc;
+  if (int rc = al::stretch_geometry_check("al_fx_time_stretch", n, rate, n_fft)) return rc;   // before the ranges: it bounds n
+  if (int rc = al::stretch_overlap_check("al_fx_time_stretch", src, n, dst, n_out)) return rc;
   if (((uintptr_t)workspace & 15) != 0) return fail(AL_E_BADARG, "al_fx_time_stretch: workspace must be 16-byte aligned");
   al::launch_time_stretch(src, n, dst, n_out, rate, n_fft, workspace, (hipStream_t)stream);
   return check_launch("al_fx_time_stretch");  // hipGetLastError keeps the first failure of the sequence until it is read
 }
 
 int al_fx_resample_sinc(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream) {
-  if (int rc = stretch_check("al_fx_resample_sinc", src, m, dst, n, "m", "n", nullptr, false)) return rc;
+  if (int rc = al::stretch_check("al_fx_resample_sinc", src, m, dst, n, "m", "n", nullptr, false)) return rc;
   if (m > 0x7fffffff || n > 0x7fffffff) return fail(AL_E_BADARG, "al_fx_resample_sinc: m and n must be below 2^31");
-  if (int rc = stretch_overlap_check("al_fx_resample_sinc", src, m, dst, n)) return rc;
+  if (int rc = al::stretch_overlap_check("al_fx_resample_sinc", src, m, dst, n)) return rc;
   al::launch_resample_sinc(src, m, dst, n, (hipStream_t)stream);
   return check_launch("k_resample_sinc");
 }
 
 // ---- batched FX launches: one workgroup per job, the jobs of one kind in one grid
-namespace {
-int64_t fxb_desc_bytes(int32_t kind) {
-  switch (kind) {
-    case AL_FXB_SOS: return (int64_t)sizeof(al::SosJob);
-    case AL_FXB_CHORUS: return (int64_t)sizeof(al::ChorusJob);
-    case AL_FXB_PHASER: return (int64_t)sizeof(al::PhaserJob);
-    case AL_FXB_DEEMPH: return (int64_t)sizeof(al::DeemphJob);
-    case AL_FXB_COMPRESSOR:
-    case AL_FXB_LIMITER: return (int64_t)sizeof(al::DynJob);
-    default: return -1;
-  }
+int64_t al_fx_batch_desc_bytes(int32_t kind) {
+  const FxKind *row = fx_kind(kind);
+  return row ? (int64_t)row->desc_bytes : -1;
 }
-
-// the last error, with the job it belongs to in front
-int fail_job(int rc, int32_t job) {
-  char msg[sizeof(g_err)];
-  snprintf(msg, sizeof(msg), "al_fx_batch_pack: job %d: %.200s", job, g_err);
-  return fail(rc, msg);
-}
-
-struct FxRange {
-  const float *src, *dst;
-  int64_t n;
-};
-}  // namespace
-
-int64_t al_fx_batch_desc_bytes(int32_t kind) { return fxb_desc_bytes(kind); }
 
 int al_fx_batch_pack(int32_t kind, const void *jobs, int32_t count, void *host_table) {
-  if (fxb_desc_bytes(kind) < 0) return fail(AL_E_BADARG, "al_fx_batch_pack: unknown kind");
+  const FxKind *row = fx_kind(kind);
+  if (!row) return fail(AL_E_BADARG, "al_fx_batch_pack: unknown kind");
   if (!jobs || !host_table) return fail(AL_E_BADARG, "al_fx_batch_pack: null pointer");
   if (count < 1) return fail(AL_E_BADARG, "al_fx_batch_pack: count must be >= 1");
+  auto job = [&](int32_t i) -> const void * { return static_cast<const char *>(jobs) + row->job_bytes * i; };
   for (int32_t i = 0; i < count; ++i) {
-    int rc = AL_OK;
-    if (kind == AL_FXB_SOS) {
-      const al_fx_sos_job &j = static_cast<const al_fx_sos_job *>(jobs)[i];
-      rc = sos_prepare(j.src, j.dst, j.n, j.sos, j.n_sections, static_cast<al::SosJob *>(host_table) + i);
-    } else if (kind == AL_FXB_DEEMPH) {
-      const al_fx_deemph_job &j = static_cast<const al_fx_deemph_job *>(jobs)[i];
-      rc = deemph_prepare(j.src, j.dst, j.n, j.coef, static_cast<al::DeemphJob *>(host_table) + i);
-    } else if (kind == AL_FXB_COMPRESSOR) {
-      const al_fx_compressor_job &j = static_cast<const al_fx_compressor_job *>(jobs)[i];
-      rc = compressor_prepare(j.src, j.dst, j.n, j.fs, j.threshold_db, j.ratio, j.attack_ms, j.release_ms,
-                              static_cast<al::DynJob *>(host_table) + i);
-    } else if (kind == AL_FXB_LIMITER) {
-      const al_fx_limiter_job &j = static_cast<const al_fx_limiter_job *>(jobs)[i];
-      rc = limiter_prepare(j.src, j.dst, j.n, j.fs, j.threshold_db, j.release_ms, static_cast<al::DynJob *>(host_table) + i);
-    } else {
-      const al_fx_mod_job &j = static_cast<const al_fx_mod_job *>(jobs)[i];
-      if (kind == AL_FXB_CHORUS) {
-        rc = chorus_prepare(j.src, j.dst, j.n, j.fs, j.rate_hz, j.depth, j.centre, j.feedback, j.mix,
-                            static_cast<al::ChorusJob *>(host_table) + i);
-        if (!rc && j.feedback == 0.0)
-          rc = fail(AL_E_BADARG, "al_fx_chorus: feedback == 0 runs grid-wide (k_fx_chorus_ff): not a batch job");
-      } else {
-        rc = phaser_prepare(j.src, j.dst, j.n, j.fs, j.rate_hz, j.depth, j.centre, j.feedback, j.mix,
-                            static_cast<al::PhaserJob *>(host_table) + i);
-      }
+    int rc = row->prepare(job(i), static_cast<char *>(host_table) + row->desc_bytes * i);
+    if (!rc && row->kind == ChorusRow::KIND && static_cast<const al_fx_mod_job *>(job(i))->feedback == 0.0)
+      rc = fail(AL_E_BADARG, "al_fx_chorus: feedback == 0 runs grid-wide (k_fx_chorus_ff): not a batch job");
+    if (rc) {   // the refusal, with the job it belongs to in front
+      char msg[sizeof(al::g_err)];
+      snprintf(msg, sizeof(msg), "al_fx_batch_pack: job %d: %.200s", i, al::g_err);
+      return fail(rc, msg);
     }
-    if (rc) return fail_job(rc, i);
   }
-  // the workgroups run concurrently: no job may write where another reads or writes (src, dst, n lead every job struct)
-  const size_t stride = kind == AL_FXB_SOS          ? sizeof(al_fx_sos_job)
-                        : kind == AL_FXB_DEEMPH     ? sizeof(al_fx_deemph_job)
-                        : kind == AL_FXB_COMPRESSOR ? sizeof(al_fx_compressor_job)
-                        : kind == AL_FXB_LIMITER    ? sizeof(al_fx_limiter_job)
-                                                    : sizeof(al_fx_mod_job);
-  auto range = [&](int32_t i) { return reinterpret_cast<const FxRange *>(static_cast<const char *>(jobs) + stride * i); };
+  // the workgroups run concurrently: no job may write where another reads or writes
   for (int32_t i = 0; i < count; ++i)
     for (int32_t k = 0; k < count; ++k) {
-      const FxRange *a = range(i), *b = range(k);
-      if (k == i || !(fx_ranges_overlap(a->dst, a->n, b->src, b->n) || fx_ranges_overlap(a->dst, a->n, b->dst, b->n))) continue;
+      const void *a = job(i), *b = job(k);
+      if (k == i || !(al::fx_ranges_overlap(row->dst(a), row->n(a), row->src(b), row->n(b)) ||
+                      al::fx_ranges_overlap(row->dst(a), row->n(a), row->dst(b), row->n(b)))) continue;
       char msg[160];
       snprintf(msg, sizeof(msg), "al_fx_batch_pack: job %d: dst overlaps src or dst of job %d (the jobs run concurrently)", i, k);
       return fail(AL_E_BADARG, msg);
@@ -697,26 +433,11 @@ int al_fx_batch_pack(int32_t kind, const void *jobs, int32_t count, void *host_t
 }
 
 int al_fx_batch_launch(int32_t kind, const void *device_table, int32_t count, al_stream_t stream) {
-  if (fxb_desc_bytes(kind) < 0) return fail(AL_E_BADARG, "al_fx_batch_launch: unknown kind");
+  const FxKind *row = fx_kind(kind);
+  if (!row) return fail(AL_E_BADARG, "al_fx_batch_launch: unknown kind");
   if (!device_table || count < 1) return fail(AL_E_BADARG, "al_fx_batch_launch: needs a table and count >= 1");
-  switch (kind) {
-    case AL_FXB_SOS:
-      hipLaunchKernelGGL(al::k_fx_sos, dim3((unsigned)count), dim3(al::SOS_THREADS), 0, (hipStream_t)stream, static_cast<const al::SosJob *>(device_table), al::SosJob{});
-      return check_launch("k_fx_sos");
-    case AL_FXB_CHORUS:
-      hipLaunchKernelGGL(al::k_fx_chorus_fb, dim3((unsigned)count), dim3(al::CHO_THREADS), 0, (hipStream_t)stream, static_cast<const al::ChorusJob *>(device_table), al::ChorusJob{});
-      return check_launch("k_fx_chorus_fb");
-    case AL_FXB_PHASER:
-      hipLaunchKernelGGL(al::k_fx_phaser, dim3((unsigned)count), dim3(al::PH_THREADS), 0, (hipStream_t)stream, static_cast<const al::PhaserJob *>(device_table), al::PhaserJob{});
-      return check_launch("k_fx_phaser");
-    case AL_FXB_COMPRESSOR:
-    case AL_FXB_LIMITER:
-      hipLaunchKernelGGL(al::k_fx_dynamics, dim3((unsigned)count), dim3(al::DYN_LANES), 0, (hipStream_t)stream, static_cast<const al::DynJob *>(device_table), al::DynJob{});
-      return check_launch("k_fx_dynamics");
-    default:
-      hipLaunchKernelGGL(al::k_fx_deemph, dim3((unsigned)count), dim3(1024), 0, (hipStream_t)stream, static_cast<const al::DeemphJob *>(device_table), al::DeemphJob{});
-      return check_launch("k_fx_deemph");
-  }
+  row->launch(device_table, nullptr, (unsigned)count, (hipStream_t)stream);
+  return check_launch(row->kernel);
 }
 
 // ---- arbitrary-length inverse real FFT (ambience)
@@ -766,8 +487,7 @@ int al_ambience_scales(const double *row_stats, int32_t rows, int64_t cols, floa
 
 int al_axpy_rows(float *y, const float *x, const float *a_dev, int32_t rows, int64_t cols, al_stream_t stream) {
   if (!x || !y || !a_dev || rows <= 0 || rows > 65535 || cols <= 0) return fail(AL_E_BADARG, "bad axpy_rows arguments");
-  const int64_t blocks = (cols + 255) / 256;
-  hipLaunchKernelGGL(al::k_axpy_rows, dim3((unsigned)(blocks < 2048 ? blocks : 2048), rows), dim3(256), 0, (hipStream_t)stream, y, x,
+  hipLaunchKernelGGL(al::k_axpy_rows, dim3(grid_1d(cols, 2048), rows), dim3(256), 0, (hipStream_t)stream, y, x,
                      a_dev, cols);
   return check_launch("k_axpy_rows");
 }
@@ -849,8 +569,7 @@ int al_istft_ola(const float *spatial_stft, int32_t n_frames, int32_t n_freq, in
 
 int al_scale_matrix_rows(float *x, int32_t rows, int64_t cols, const float *scale, al_stream_t stream) {
   if (!x || !scale || rows <= 0 || rows > 65535 || cols <= 0) return fail(AL_E_BADARG, "bad scale_matrix_rows arguments");
-  const int64_t blocks = (cols + 255) / 256;
-  hipLaunchKernelGGL(al::k_scale_matrix_rows, dim3((unsigned)(blocks < 2048 ? blocks : 2048), rows), dim3(256), 0,
+  hipLaunchKernelGGL(al::k_scale_matrix_rows, dim3(grid_1d(cols, 2048), rows), dim3(256), 0,
                      (hipStream_t)stream, x, cols, scale);
   return check_launch("k_scale_matrix_rows");
 }
@@ -886,37 +605,8 @@ int al_pack_ragged_irs(const void *src, int32_t src_is_f64, const int64_t *offse
 int al_ism_shoebox(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
                    const double *beta, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, float *out,
                    al_stream_t stream) {
-  if (!sources || !capsules || !L || !beta || !out) return fail(AL_E_BADARG, "al_ism_shoebox: null pointer");
-  if (n_sources < 1 || n_capsules < 1) return fail(AL_E_BADARG, "al_ism_shoebox: n_sources and n_capsules must be >= 1");
-  if (ir_len < 1) return fail(AL_E_BADARG, "al_ism_shoebox: ir_len must be >= 1");
-  if (pitch < ir_len || (pitch & 3)) return fail(AL_E_BADARG, "al_ism_shoebox: pitch must be >= ir_len and a multiple of 4");
-  if (max_order < -1) return fail(AL_E_BADARG, "al_ism_shoebox: max_order must be >= 0, or -1 for none");
-  if (!isfinite(c) || !(c > 0.0) || !isfinite(fs) || !(fs > 0.0)) return fail(AL_E_BADARG, "al_ism_shoebox: c and fs must be finite and positive");
   al::IsmJob job;
-  for (int i = 0; i < 3; ++i) {
-    if (!isfinite(L[i]) || !(L[i] > 0.0)) return fail(AL_E_BADARG, "al_ism_shoebox: room dimensions must be finite and positive");
-    if (!(c * ((double)ir_len + 42.0) / fs / L[i] + 2.0 <= al::ISM_MAX_HALF_WIDTH))
-      return fail(AL_E_BADARG, "al_ism_shoebox: c (ir_len + 42) / fs spans more than 2^20 mirror cells of the room");
-    job.L[i] = L[i];
-  }
-  for (int i = 0; i < 6; ++i) {
-    if (!(beta[i] >= 0.0 && beta[i] <= 1.0)) return fail(AL_E_BADARG, "al_ism_shoebox: reflection coefficients must be in [0, 1]");
-    job.beta_zero[i] = beta[i] == 0.0;
-    job.ln_beta[i] = beta[i] == 0.0 ? 0.0 : log(beta[i]);
-  }
-  job.n_tiles = (pitch + al::ISM_TILE - 1) / al::ISM_TILE;
-  if ((int64_t)job.n_tiles * n_sources * n_capsules > 0x7fffffff)
-    return fail(AL_E_BADARG, "al_ism_shoebox: more than 2^31 - 1 workgroups (tiles of 256 samples x pairs): split the call");
-  job.sources = sources;
-  job.capsules = capsules;
-  job.out = out;
-  job.n_sources = n_sources;
-  job.n_capsules = n_capsules;
-  job.ir_len = ir_len;
-  job.pitch = pitch;
-  job.max_order = max_order;
-  job.c = c;
-  job.fs = fs;
+  if (int rc = al::ism_prepare(sources, n_sources, capsules, n_capsules, L, beta, c, fs, max_order, ir_len, pitch, out, &job)) return rc;
   al::launch_ism_shoebox(job, (hipStream_t)stream);
   return check_launch("k_ism_shoebox");
 }
@@ -926,8 +616,7 @@ int al_resample_poly(const float *x, int32_t rows, int64_t n_in, const float *ta
   if (!x || !taps || !out || rows <= 0 || rows > 65535 || n_in <= 0 || half_len < 0 || up <= 0 || down <= 0 || n_out <= 0 ||
       out_pitch < n_out)
     return fail(AL_E_BADARG, "bad resample_poly arguments");
-  const int64_t blocks = (out_pitch + 255) / 256;
-  hipLaunchKernelGGL(al::k_resample_poly, dim3((unsigned)(blocks < 4096 ? blocks : 4096), rows), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(al::k_resample_poly, dim3(grid_1d(out_pitch, 4096), rows), dim3(256), 0, (hipStream_t)stream,
                      x, n_in, taps, half_len, up, down, out, n_out, out_pitch);
   return check_launch("k_resample_poly");
 }
@@ -947,8 +636,7 @@ int al_encode_frames(const float *scene, int32_t n_capsules, int64_t n_samples, 
 
 int al_wrap_copy(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream) {
   if (!src || !dst || m <= 0 || n <= 0 || src == dst) return fail(AL_E_BADARG, "bad wrap_copy arguments");
-  const int64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(al::k_wrap_copy, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
+  hipLaunchKernelGGL(al::k_wrap_copy, dim3(grid_1d(n, 4096)), dim3(256), 0,
                      (hipStream_t)stream, src, m, dst, n);
   return check_launch("k_wrap_copy");
 }

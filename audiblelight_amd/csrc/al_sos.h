@@ -18,8 +18,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <string.h>
 
 #include "al_common.h"
+#include "al_status.h"
 
 namespace al {
 
@@ -161,7 +164,7 @@ __global__ __launch_bounds__(1024) void k_fx_sos(const SosJob *__restrict__ tabl
   }
 }
 
-// ---- host side (al_fx_sos): Phi = A^run in float64 by repeated squaring
+// ---- host side (al_fx_sos, al_fx_batch_pack): Phi = A^run in float64 by repeated squaring
 inline void sos_transition_power(double a1, double a2, int64_t p, double out[4]) {
   double r[4] = {1.0, 0.0, 0.0, 1.0}, m[4] = {-a1, 1.0, -a2, 0.0};
   while (p > 0) {
@@ -176,6 +179,49 @@ inline void sos_transition_power(double a1, double a2, int64_t p, double out[4])
     p >>= 1;
   }
   for (int i = 0; i < 4; ++i) out[i] = r[i];
+}
+
+// 0 with *job filled (every section divided by its a0, with its Phi), or the error of the first bad argument
+inline int sos_prepare(const al_fx_sos_job &in, SosJob *job) {
+  if (!in.src || !in.dst || !in.sos) return fail(AL_E_BADARG, "al_fx_sos: null pointer");
+  if (in.n < 1) return fail(AL_E_BADARG, "al_fx_sos: n must be >= 1");
+  if (in.n_sections < 1 || in.n_sections > AL_SOS_MAX_SECTIONS)
+    return fail(AL_E_BADARG, "al_fx_sos: n_sections must be in 1..AL_SOS_MAX_SECTIONS (16); split longer cascades");
+  const int64_t run = sos_run_length(in.n);
+  memset(job, 0, sizeof(*job));
+  job->src = in.src;
+  job->dst = in.dst;
+  job->n = in.n;
+  job->run = run;
+  SosArgs &a = job->a;
+  a.n_sections = in.n_sections;
+  char msg[160];
+  for (int k = 0; k < in.n_sections; ++k) {
+    const double *row = in.sos + 6 * k;
+    for (int i = 0; i < 6; ++i)
+      if (!isfinite(row[i])) {
+        snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a non-finite coefficient", k);
+        return fail(AL_E_BADARG, msg);
+      }
+    if (row[3] == 0.0) {
+      snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a0 == 0", k);
+      return fail(AL_E_BADARG, msg);
+    }
+    const double c[5] = {row[0] / row[3], row[1] / row[3], row[2] / row[3], row[4] / row[3], row[5] / row[3]};
+    for (int i = 0; i < 5; ++i)
+      if (!isfinite(c[i])) {
+        snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a non-finite coefficient after division by a0", k);
+        return fail(AL_E_BADARG, msg);
+      }
+    // both roots of z^2 + a1 z + a2 inside the unit circle (Jury): |a2| < 1 and |a1| < 1 + a2
+    if (!(fabs(c[4]) < 1.0 && fabs(c[3]) < 1.0 + c[4])) {
+      snprintf(msg, sizeof(msg), "al_fx_sos: section %d has a pole of magnitude >= 1 (unstable filter)", k);
+      return fail(AL_E_BADARG, msg);
+    }
+    for (int i = 0; i < 5; ++i) a.c[k][i] = c[i];
+    sos_transition_power(c[3], c[4], run, a.phi[k]);
+  }
+  return AL_OK;
 }
 
 }  // namespace al

@@ -29,9 +29,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "al_bigfft.h"
 #include "al_common.h"
+#include "al_status.h"
 #include "al_stft.h"
 
 namespace al {
@@ -272,10 +274,31 @@ inline PvPlan pv_plan(int64_t n, double rate, int32_t n_fft) {
   return p;
 }
 
-inline unsigned pv_flat_grid(int64_t elements) {
-  const int64_t blocks = (elements + 255) / 256;
-  return (unsigned)(blocks < 65536 ? blocks : 65536);
+// 0, or the error of the first bad pointer or length; src of n samples, dst of n_out
+inline int stretch_check(const char *fn, const float *src, int64_t n, const float *dst, int64_t n_out, const char *n_name,
+                         const char *n_out_name, const void *workspace, bool needs_workspace) {
+  if (!src || !dst || (needs_workspace && !workspace)) return fail_arg(fn, "null pointer");
+  if (n >= 1 && n_out >= 1) return AL_OK;
+  char why[160];
+  snprintf(why, sizeof(why), "%s must be >= 1", n < 1 ? n_name : n_out_name);
+  return fail_arg(fn, why);
 }
+
+inline int stretch_overlap_check(const char *fn, const float *src, int64_t n, const float *dst, int64_t n_out) {
+  return fx_ranges_overlap(src, n, dst, n_out) ? fail_arg(fn, "dst overlaps src (out of place only)") : AL_OK;
+}
+
+// 0, or the error of a bad (n, rate, n_fft): the geometry both time-stretch entries derive
+inline int stretch_geometry_check(const char *fn, int64_t n, double rate, int32_t n_fft) {
+  const char *why = nullptr;
+  if (!pv_fft_ok(n_fft)) why = "n_fft must be a power of two in [64, 4096]";
+  else if (!isfinite(rate) || rate < 0.25 || rate > 4.0) why = "rate must be finite and in [0.25, 4]";
+  else if (pv_frames_in(n, n_fft) > PV_MAX_FRAMES) why = "too many analysis frames (F = 1 + n / hop must be <= 2^30)";
+  else if (pv_frames_out(pv_frames_in(n, n_fft), rate) > PV_MAX_FRAMES) why = "too many output frames (T must be <= 2^30)";
+  return why ? fail_arg(fn, why) : AL_OK;
+}
+
+inline unsigned pv_flat_grid(int64_t elements) { return grid_1d(elements, 65536); }
 
 // every argument checked by the caller; workspace: pv_plan(...).floats floats, 16-byte aligned
 inline void launch_time_stretch(const float *src, int64_t n, float *dst, int64_t n_out, double rate, int32_t n_fft, float *workspace,
@@ -307,8 +330,7 @@ inline void launch_time_stretch(const float *src, int64_t n, float *dst, int64_t
     float2 *z = big_fft(sa + t0 * n_fft, sb + t0 * n_fft, g, n_fft, +1, st);
     frames = z == sa + t0 * n_fft ? sa : sb;   // every group ends in the same buffer (same pass count)
   }
-  const int64_t blocks = (n_out + 255) / 256;
-  hipLaunchKernelGGL(k_pv_ola, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, frames, p.T, n_fft, dst, n_out);
+  hipLaunchKernelGGL(k_pv_ola, dim3(grid_1d(n_out, 8192)), dim3(256), 0, st, frames, p.T, n_fft, dst, n_out);
 }
 
 inline void launch_resample_sinc(const float *src, int64_t m, float *dst, int64_t n, hipStream_t st) {
@@ -320,9 +342,7 @@ inline void launch_resample_sinc(const float *src, int64_t m, float *dst, int64_
     i0 += term;
     if (term < 1e-17 * i0) break;
   }
-  const int64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(k_resample_sinc, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, src, m, dst, n, c, H,
-                     1.0 / i0);
+  hipLaunchKernelGGL(k_resample_sinc, dim3(grid_1d(n, 16384)), dim3(256), 0, st, src, m, dst, n, c, H, 1.0 / i0);
 }
 
 }  // namespace al
