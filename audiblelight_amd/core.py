@@ -299,12 +299,14 @@ class ShoeboxIRState:
     (shoebox.py, DESIGN.md "Shoebox IRs"): the reference's ``WorldStateShoebox`` (worldstate.py:3105-3110) is declared and left
     empty.  ``betas``: six wall reflection coefficients (x0, x1, y0, y1, z0, z1), or ``rt60`` for one uniform coefficient by
     Sabine's law.  Microphones are sets of omnidirectional point capsules; emitters are IR columns in event order (a moving event
-    contributes one row per trajectory point).  ``simulate()`` enqueues one generation per microphone; the tensors stay in HBM."""
+    contributes one row per trajectory point).  ``simulate()`` enqueues one generation per microphone; the tensors stay in HBM.
+    ``tail``: a ``shoebox.ShoeboxTail`` (or its dictionary) gives every row a diffuse tail past the mixing time; capsules are
+    numbered through the microphones in their order, so no two rows of the state share noise."""
 
     name = "SHOEBOX"
 
     def __init__(self, room, betas=None, rt60: Optional[float] = None, ir_len: int = 4096, sample_rate: int = config.SAMPLE_RATE,
-                 c: float = 343.0, max_order: Optional[int] = None, renderer=None, metadata: Optional[dict] = None):
+                 c: float = 343.0, max_order: Optional[int] = None, renderer=None, metadata: Optional[dict] = None, tail=None):
         from . import shoebox
 
         if (betas is None) == (rt60 is None):
@@ -314,6 +316,7 @@ class ShoeboxIRState:
         self.betas = shoebox.betas_from_rt60(self.room, rt60, c) if betas is None else np.array(betas, dtype=np.float64)
         self.ir_len, self.sample_rate, self.c = int(ir_len), int(sample_rate), float(c)
         self.max_order = None if max_order is None else int(max_order)
+        self.tail = shoebox.ShoeboxTail.from_dict(tail) if isinstance(tail, dict) else tail
         self.renderer = renderer
         self.metadata = dict(metadata or {})
         self.microphones: "OrderedDict[str, MicArray]" = OrderedDict()
@@ -323,7 +326,7 @@ class ShoeboxIRState:
         # refuse bad room parameters here, not at the first simulate()
         inside = 0.5 * self.room[None, :]
         shoebox.check_arguments(self.room, self.betas, inside, inside + 0.25 * self.room[None, :], self.ir_len, self.sample_rate,
-                                self.c, self.max_order)
+                                self.c, self.max_order, self.tail)
 
     def add_microphone(self, alias: str, capsule_positions) -> MicArray:
         from . import shoebox
@@ -365,10 +368,12 @@ class ShoeboxIRState:
         r = self.renderer or synthesize.get_renderer()
         sources = self.emitter_positions
         irs = OrderedDict()
+        capsule_id0 = 0     # the tail's noise: capsules are numbered through the microphones, emitters are one table already
         for alias, capsules in self._capsules.items():
             buf, strides, _ = shoebox.shoebox_irs_device(r, self.room, self.betas, sources, capsules, self.ir_len, self.sample_rate,
-                                                         self.c, self.max_order)
+                                                         self.c, self.max_order, self.tail, 0, capsule_id0)
             irs[alias] = shoebox.DeviceIRTensor(r, buf, strides, (len(capsules), len(sources), self.ir_len))
+            capsule_id0 += len(capsules)
         self._irs = irs
 
     @property
@@ -386,6 +391,8 @@ class ShoeboxIRState:
                  microphones={k: m.to_dict() for k, m in self.microphones.items()},
                  shoebox=dict(room=self.room.tolist(), betas=self.betas.tolist(), rt60=self.rt60, ir_len=self.ir_len, c=self.c,
                               max_order=self.max_order))
+        if self.tail is not None:
+            d["shoebox"]["tail"] = self.tail.to_dict()
         d.update({k: v for k, v in self.metadata.items() if k not in d})
         return d
 
@@ -402,7 +409,7 @@ class ShoeboxIRState:
         box = state_d["shoebox"]
         keep = {k: v for k, v in state_d.items() if k not in ("backend", "sample_rate", "emitters", "microphones", "shoebox")}
         state = cls(box["room"], betas=box["betas"], ir_len=box["ir_len"], sample_rate=state_d.get("sample_rate") or config.SAMPLE_RATE,
-                    c=box.get("c", 343.0), max_order=box.get("max_order"), renderer=renderer, metadata=keep)
+                    c=box.get("c", 343.0), max_order=box.get("max_order"), renderer=renderer, metadata=keep, tail=box.get("tail"))
         state.rt60 = box.get("rt60")
         for alias, md in state_d["microphones"].items():
             mic = state.add_microphone(alias, md["coordinates_absolute"])

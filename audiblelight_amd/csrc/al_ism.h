@@ -22,12 +22,30 @@
 // A tap costs one LDS entry, two table reads and a division: sin(pi (t - tau)) = -(-1)^j sin(pi f) and the window's cosine by the
 // angle sum over a table of cos / sin(2 pi j / 81), with t0 = rint(tau), f = tau - t0 (exact) and j = t - t0.
 // All geometry, tau, the tap weight and the accumulator are float64.
+//
+// THE DIFFUSE TAIL (al_ism_shoebox_tail; DESIGN.md "Shoebox IRs: the diffuse tail").  Past a mixing sample M the row continues as
+// seeded Gaussian noise under an envelope e(t) read from a table of log-amplitude knots, one per ISM_TILE samples; between M and
+// M + F the two are cross-faded with cos / sin(pi x / 2), x = (t - M) / F.  Sample t of row (c, n) draws normal t % 4 of the
+// Philox-4x32-10 block with counter (t / 4, source_id0 + n, ISM_TAIL_TAG, capsule_id0 + c) and key (seed lo, seed hi): a pure
+// function of the seed, the two ids and t, so a row's bits do not depend on the call it is generated in.  Two kernels share a row:
+//   k_ism_shoebox<true>  the tiles below SPLIT = ceil((M + F) / ISM_TILE) * ISM_TILE.  The image search ends at min(ir_len, M + F)
+//     (the images past it are never visited: that is the whole saving), the epilogue applies the fade and adds the noise term, a
+//     Philox block per sample (at most F + ISM_TILE such samples per row).  A sample at or below M is the image sum alone
+//     (w_e = 1, w_l = 0 exactly, no noise term formed): with M >= ir_len the bits are those of k_ism_shoebox<false>.
+//   k_ism_tail  every sample at or past SPLIT, pad included: w_l = 1 there, so out = (float)(e(t) g(t)).  A lane takes four
+//     consecutive samples (one Philox block, one knot interval since 4 divides ISM_TILE) and writes them with one 16-byte store;
+//     a workgroup takes ISM_TAIL_SPAN consecutive samples of one row.  No LDS, no barrier, no atomics; the only global reads are
+//     the two knots.  e(t) = exp((1 - p) ln_env[k] + p ln_env[k + 1]) in float64 (p == 0 reads knot k alone, so a table of -inf
+//     gives zeros and not 0 * inf); the quad's later three samples are e(t) times powers of exp((ln_env[k + 1] - ln_env[k]) / 256),
+//     two exp per quad instead of four (a few float64 ulp from the definition, ten orders below the draw's tolerance).
+// Every output sample is written exactly once per call by exactly one of the two kernels; out is never read.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "al_common.h"
+#include "al_rng.h"
 #include "al_status.h"
 
 namespace al {
@@ -39,6 +57,20 @@ constexpr int ISM_HALF = 40;      // taps on either side of rint(tau): |t - tau|
 constexpr int ISM_TAPS = 2 * ISM_HALF + 1;
 constexpr int ISM_LIST = 128;     // images per LDS list window (48 bytes each)
 constexpr double ISM_MAX_HALF_WIDTH = 1048576.0;   // mirror cells per axis and side al_ism_shoebox accepts
+constexpr uint32_t ISM_TAIL_TAG = 4u;                 // third counter word of the tail's draws: 1, 2 and 3 are the ambience's (al_rng.h)
+constexpr int ISM_TAIL_THREADS = 256;
+constexpr int ISM_TAIL_QUADS = 4;                     // 16-byte stores per lane of k_ism_tail, ISM_TAIL_THREADS quads apart
+constexpr int ISM_TAIL_SPAN = ISM_TAIL_THREADS * 4 * ISM_TAIL_QUADS;   // samples per workgroup of k_ism_tail
+
+// the diffuse tail of a row (all zero for al_ism_shoebox)
+struct IsmTail {
+  const double *ln_env;   // n_knots log-amplitude knots (device), knot k at sample ISM_TILE k
+  int64_t mix, fade;      // M, F
+  int32_t y_end;          // min(ir_len, M + F): the image sum is needed below it only
+  int32_t split;          // ceil((M + F) / ISM_TILE) * ISM_TILE, at most pitch rounded up to ISM_TILE: k_ism_tail owns [split, pitch)
+  int32_t tail_blocks;    // workgroups of k_ism_tail per row
+  uint32_t seed_lo, seed_hi, source_id0, capsule_id0, reserved;
+};
 
 struct IsmJob {
   const double *sources, *capsules;   // (N, 3), (C, 3)
@@ -47,6 +79,7 @@ struct IsmJob {
   double L[3], ln_beta[6];            // ln_beta: 0 where beta == 0 (see beta_zero)
   int32_t beta_zero[6];
   double c, fs;
+  IsmTail tail;
 };
 
 struct alignas(16) IsmEntry {
@@ -81,6 +114,22 @@ struct IsmColumn {
 
 __device__ __forceinline__ int ism_clamp(double v, int lo, int hi) { return v < (double)lo ? lo : v > (double)hi ? hi : (int)v; }
 
+// e(t) of the tail: the knot table interpolated in the logarithm, float64
+__device__ __forceinline__ double ism_envelope(const double *ln_env, int t) {
+  const int k = t / ISM_TILE, r = t % ISM_TILE;
+  if (r == 0) return exp(ln_env[k]);
+  const double p = (double)r / (double)ISM_TILE;
+  return exp((1.0 - p) * ln_env[k] + p * ln_env[k + 1]);
+}
+// the four normals of samples 4 q .. 4 q + 3 of row (cap, n)
+__device__ __forceinline__ float4 ism_tail_normal4(const IsmTail &tail, int q, int n, int cap) {
+  const Philox4 p = philox4x32_10((uint32_t)q, tail.source_id0 + (uint32_t)n, ISM_TAIL_TAG, tail.capsule_id0 + (uint32_t)cap, tail.seed_lo,
+                                  tail.seed_hi);
+  const float2 a = box_muller(p.x, p.y), b = box_muller(p.z, p.w);
+  return make_float4(a.x, a.y, b.x, b.y);
+}
+
+template <bool TAIL>
 __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
   __shared__ IsmEntry list[ISM_LIST];
   __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];   // cos, sin(2 pi j / 81), j = -40 .. 40
@@ -90,7 +139,9 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
   const int64_t pair = blockIdx.x / (unsigned)job.n_tiles;   // c * N + n
   const int n = (int)(pair % job.n_sources), cap = (int)(pair / job.n_sources);
   const int t_lo = tile * ISM_TILE, t = t_lo + tid;
-  const int t_hi = min(t_lo + ISM_TILE, job.ir_len) - 1;
+  // the image sum is needed below y_end only: past the fade the row is the tail's
+  const int y_end = TAIL ? job.tail.y_end : job.ir_len;
+  const int t_hi = min(t_lo + ISM_TILE, y_end) - 1;
   float *row = job.out + pair * (int64_t)job.pitch;
   if (t_lo >= job.ir_len) {   // a tile of pad samples only
     for (int s = 0; s < ISM_PER_LANE; ++s)
@@ -215,7 +266,7 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
 #pragma unroll
         for (int s = 0; s < ISM_PER_LANE; ++s) {
           const int j = j0 + s * ISM_THREADS;
-          if (j < -ISM_HALF || j > ISM_HALF || t + s * ISM_THREADS >= job.ir_len) continue;
+          if (j < -ISM_HALF || j > ISM_HALF || t + s * ISM_THREADS >= y_end) continue;
           const double u = (double)j - e.f;
           if (!(fabs(u) < 0.5 * (double)ISM_TAPS)) continue;
           if (u == 0.0) {
@@ -232,7 +283,59 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
 #pragma unroll
   for (int s = 0; s < ISM_PER_LANE; ++s) {
     const int ts = t + s * ISM_THREADS;
-    if (ts < job.pitch) row[ts] = ts < job.ir_len ? (float)acc[s] : 0.f;
+    if (ts >= job.pitch) continue;
+    double v = acc[s];
+    if constexpr (TAIL) {
+      if (ts > job.tail.mix && ts < job.ir_len) {   // at or below M: w_e = 1, w_l = 0, the image sum as it is
+        const double x = ((double)ts - (double)job.tail.mix) / (double)job.tail.fade;
+        double w_e = 0.0, w_l = 1.0;
+        if (x < 1.0) sincospi(0.5 * x, &w_l, &w_e);
+        const float4 g4 = ism_tail_normal4(job.tail, ts >> 2, n, cap);
+        const float g = (ts & 2) ? ((ts & 1) ? g4.w : g4.z) : ((ts & 1) ? g4.y : g4.x);
+        v = w_e * v + w_l * ism_envelope(job.tail.ln_env, ts) * (double)g;
+      }
+    }
+    row[ts] = ts < job.ir_len ? (float)v : 0.f;
+  }
+}
+
+// the samples [split, pitch) of every row: envelope times noise, pad zeros; grid: tail_blocks workgroups per pair
+__global__ __launch_bounds__(ISM_TAIL_THREADS) void k_ism_tail(IsmJob job) {
+  const int block = (int)(blockIdx.x % (unsigned)job.tail.tail_blocks);
+  const int64_t pair = blockIdx.x / (unsigned)job.tail.tail_blocks;
+  const int n = (int)(pair % job.n_sources), cap = (int)(pair / job.n_sources);
+  float *row = job.out + pair * (int64_t)job.pitch;
+  const int64_t t_first = (int64_t)job.tail.split + (int64_t)block * ISM_TAIL_SPAN + 4 * (int)threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < ISM_TAIL_QUADS; ++i) {
+    const int64_t t64 = t_first + (int64_t)i * (4 * ISM_TAIL_THREADS);
+    if (t64 >= job.pitch) return;   // pitch is a multiple of 4: a quad is inside the row or outside it
+    const int t = (int)t64;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (t < job.ir_len) {
+      const float4 g = ism_tail_normal4(job.tail, t >> 2, n, cap);
+      const int k = t / ISM_TILE, r = t % ISM_TILE;   // r + 3 < ISM_TILE: the quad lies in one knot interval
+      const double a = job.tail.ln_env[k], b = job.tail.ln_env[k + 1];
+      const double inv = 1.0 / (double)ISM_TILE, p = (double)r * inv, step = (b - a) * inv;
+      const double e0 = exp(r == 0 ? a : (1.0 - p) * a + p * b);
+      double e1, e2, e3;
+      if (fabs(step) < 1.0) {   // ln e is linear in t between two knots: one more exp serves the quad, e(t + 1) = e(t) exp(step)
+        const double q = exp(step);
+        e1 = e0 * q;
+        e2 = e1 * q;
+        e3 = e2 * q;
+      } else {   // a knot of -inf, a table that is not finite or one that leaps: every sample as the definition has it
+        const double p1 = (double)(r + 1) * inv, p2 = (double)(r + 2) * inv, p3 = (double)(r + 3) * inv;
+        e1 = exp((1.0 - p1) * a + p1 * b);
+        e2 = exp((1.0 - p2) * a + p2 * b);
+        e3 = exp((1.0 - p3) * a + p3 * b);
+      }
+      v.x = (float)(e0 * (double)g.x);
+      if (t + 1 < job.ir_len) v.y = (float)(e1 * (double)g.y);
+      if (t + 2 < job.ir_len) v.z = (float)(e2 * (double)g.z);
+      if (t + 3 < job.ir_len) v.w = (float)(e3 * (double)g.w);
+    }
+    *reinterpret_cast<float4 *>(row + t) = v;
   }
 }
 
@@ -270,12 +373,51 @@ inline int ism_prepare(const double *sources, int32_t n_sources, const double *c
   job->max_order = max_order;
   job->c = c;
   job->fs = fs;
+  job->tail = IsmTail{};
   return AL_OK;
 }
 
 inline void launch_ism_shoebox(const IsmJob &job, hipStream_t stream) {
   const int64_t groups = (int64_t)job.n_tiles * job.n_sources * job.n_capsules;
-  hipLaunchKernelGGL(k_ism_shoebox, dim3((unsigned)groups), dim3(ISM_THREADS), 0, stream, job);
+  hipLaunchKernelGGL(k_ism_shoebox<false>, dim3((unsigned)groups), dim3(ISM_THREADS), 0, stream, job);
+}
+
+// al_ism_shoebox_tail's further arguments into a job ism_prepare has filled: the tail, the split, the two grids
+inline int ism_tail_prepare(int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env,
+                            int32_t n_knots, IsmJob *job) {
+  if (!ln_env) return fail(AL_E_BADARG, "al_ism_shoebox_tail: null envelope table");
+  if (mix < 0) return fail(AL_E_BADARG, "al_ism_shoebox_tail: mix must be >= 0");
+  if (fade < 1) return fail(AL_E_BADARG, "al_ism_shoebox_tail: fade must be >= 1");
+  if (source_id0 < 0 || capsule_id0 < 0) return fail(AL_E_BADARG, "al_ism_shoebox_tail: source_id0 and capsule_id0 must be >= 0");
+  if (source_id0 + job->n_sources > 0x100000000ll || capsule_id0 + job->n_capsules > 0x100000000ll)
+    return fail(AL_E_BADARG, "al_ism_shoebox_tail: source_id0 + n_sources and capsule_id0 + n_capsules must not exceed 2^32");
+  if (n_knots != (job->ir_len - 1) / ISM_TILE + 2) return fail(AL_E_BADARG, "al_ism_shoebox_tail: n_knots must be (ir_len - 1) / 256 + 2");
+  if (((uintptr_t)job->out & 15) != 0) return fail(AL_E_BADARG, "al_ism_shoebox_tail: out must be 16-byte aligned");
+  const int64_t row_tiles = ((int64_t)job->pitch + ISM_TILE - 1) / ISM_TILE;
+  const int64_t cap = row_tiles * ISM_TILE;
+  IsmTail &tail = job->tail;
+  tail.ln_env = ln_env;
+  tail.mix = mix < cap ? mix : cap;   // a mix past the row is a mix at its end (and M + F cannot overflow)
+  tail.fade = fade;
+  tail.split = (int32_t)cap;
+  tail.y_end = fade < job->ir_len && tail.mix + fade < job->ir_len ? (int32_t)(tail.mix + fade) : job->ir_len;
+  if (fade < cap && tail.mix + fade < cap) tail.split = (int32_t)((tail.mix + fade + ISM_TILE - 1) / ISM_TILE * ISM_TILE);
+  tail.tail_blocks = tail.split < job->pitch ? (job->pitch - tail.split + ISM_TAIL_SPAN - 1) / ISM_TAIL_SPAN : 0;
+  tail.seed_lo = (uint32_t)seed;
+  tail.seed_hi = (uint32_t)(seed >> 32);
+  tail.source_id0 = (uint32_t)source_id0;
+  tail.capsule_id0 = (uint32_t)capsule_id0;
+  job->n_tiles = (int32_t)(tail.split < job->pitch ? tail.split / ISM_TILE : row_tiles);   // k_ism_shoebox<true> stops at the split
+  if ((int64_t)tail.tail_blocks * job->n_sources * job->n_capsules > 0x7fffffff)
+    return fail(AL_E_BADARG, "al_ism_shoebox_tail: more than 2^31 - 1 workgroups (spans of 4096 samples x pairs): split the call");
+  return AL_OK;
+}
+
+inline void launch_ism_shoebox_tail(const IsmJob &job, hipStream_t stream) {
+  const int64_t pairs = (int64_t)job.n_sources * job.n_capsules;
+  hipLaunchKernelGGL(k_ism_shoebox<true>, dim3((unsigned)(job.n_tiles * pairs)), dim3(ISM_THREADS), 0, stream, job);
+  if (job.tail.tail_blocks > 0)
+    hipLaunchKernelGGL(k_ism_tail, dim3((unsigned)(job.tail.tail_blocks * pairs)), dim3(ISM_TAIL_THREADS), 0, stream, job);
 }
 
 }  // namespace al

@@ -3,18 +3,24 @@
 ``shoebox_irs_device`` makes the one call of the C ABI (``al_ism_shoebox``): the (C, N, ir_len) tensor of a rectangular room is
 born in HBM in the layout ``Renderer.prepare(plan, clips, irs, ir_strides)`` reads and never crosses PCIe.  ``DeviceIRTensor`` wraps
 it as a lazy array: the render path takes its buffer (``result()``), a host consumer downloads it once.  Omnidirectional point
-capsules, frequency-independent walls, no diffuse tail, no air absorption.  Without ``max_order`` the cost grows as
-``ir_len**3 / (Lx * Ly * Lz)`` per (capsule, source) pair.
+capsules, frequency-independent walls, no air absorption.  Without ``max_order`` the cost grows as
+``ir_len**3 / (Lx * Ly * Lz)`` per (capsule, source) pair; with a ``ShoeboxTail`` the exact image sum ends a fade after the mixing
+time and the row continues as seeded Gaussian noise under an envelope that matches the image field in level and decay
+(``al_ism_shoebox_tail``, ``tail_envelope``; DESIGN.md "Shoebox IRs: the diffuse tail"), so a row of seconds costs a write of its bytes.
 """
 from __future__ import annotations
 
 import ctypes as ct
+from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
 SPEED_OF_SOUND = 343.0
 MIN_DISTANCE = 0.01     # metres between a source and a capsule
+KNOT_SPACING = 256      # samples between two knots of the tail's envelope table (the kernel's tile)
+MIXED_ECHO_DENSITY = 1.0e4   # echoes per second at which a field is heard as diffuse (Griesinger's figure): default_mix_time
+ENVELOPE_QUADRATURE = 64     # Gauss-Legendre points per variable of tail_envelope's direction average
 
 
 def betas_from_absorption(alpha) -> np.ndarray:
@@ -61,7 +67,130 @@ def pitch_of(ir_len: int) -> int:
     return (int(ir_len) + 3) // 4 * 4
 
 
-def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED_OF_SOUND, max_order=None):
+_REAL = (int, float, np.integer, np.floating)
+
+
+@dataclass(frozen=True)
+class ShoeboxTail:
+    """The diffuse tail of a shoebox IR: the image sum is exact up to ``mix_time`` seconds (None: ``default_mix_time``), cross-faded
+    over ``fade_time`` seconds (None: a quarter of the mix time; at least one sample) into seeded Gaussian noise.  The noise decays
+    as the image-source field of the room does (``tail_envelope``), or, with ``rt60`` given, exponentially at that reverberation
+    time from the image field's level at the mixing time.  ``seed``: 64 bits; a row's noise is a function of the seed and of its
+    source and capsule numbers alone.  Validated by ``check_arguments``."""
+
+    mix_time: Optional[float] = None
+    fade_time: Optional[float] = None
+    rt60: Optional[float] = None
+    seed: int = 0
+
+    def to_dict(self) -> dict:
+        return dict(mix_time=self.mix_time, fade_time=self.fade_time, rt60=self.rt60, seed=int(self.seed))
+
+    @classmethod
+    def from_dict(cls, d) -> "ShoeboxTail":
+        if isinstance(d, cls):
+            return d
+        return cls(mix_time=d.get("mix_time"), fade_time=d.get("fade_time"), rt60=d.get("rt60"), seed=d.get("seed", 0))
+
+
+def default_mix_time(room, c: float = SPEED_OF_SOUND) -> float:
+    """Seconds after which the echo density ``4 pi c^3 tau^2 / V`` of the room reaches ``MIXED_ECHO_DENSITY`` per second:
+    ``sqrt(MIXED_ECHO_DENSITY V / (4 pi c^3))``, 42 ms in a 6 x 5 x 3 m room."""
+    room = _room(room)
+    if not (np.isfinite(c) and c > 0.0):
+        raise ValueError("c must be finite and positive")
+    return float(np.sqrt(MIXED_ECHO_DENSITY * float(np.prod(room)) / (4.0 * np.pi * float(c) ** 3)))
+
+
+def n_knots_of(ir_len: int) -> int:
+    return (int(ir_len) - 1) // KNOT_SPACING + 2
+
+
+def _check_tail(tail, betas: np.ndarray) -> None:
+    if not isinstance(tail, ShoeboxTail):
+        raise ValueError("tail must be a ShoeboxTail or None")
+    if np.any(betas == 0.0):
+        raise ValueError("a diffuse tail needs every reflection coefficient > 0: a wall of beta = 0 leaves an image lattice of "
+                         "lower dimension, whose decay the envelope law does not describe")
+    for name in ("mix_time", "fade_time"):
+        v = getattr(tail, name)
+        if v is not None and not (isinstance(v, _REAL) and not isinstance(v, bool) and np.isfinite(v) and v >= 0.0):
+            raise ValueError(f"tail.{name} must be None or a finite time >= 0 in seconds")
+    if tail.rt60 is not None and not (isinstance(tail.rt60, _REAL) and not isinstance(tail.rt60, bool) and np.isfinite(tail.rt60)
+                                      and tail.rt60 > 0.0):
+        raise ValueError("tail.rt60 must be None or a finite reverberation time > 0 in seconds")
+    if isinstance(tail.seed, (bool, np.bool_)) or not isinstance(tail.seed, (int, np.integer)) or not 0 <= int(tail.seed) < 1 << 64:
+        raise ValueError("tail.seed must be an integer in [0, 2^64)")
+
+
+def tail_samples(tail: ShoeboxTail, room, sample_rate: float, c: float = SPEED_OF_SOUND) -> Tuple[int, int]:
+    """``(M, F)``: the mixing sample and the fade length of a tail at this sample rate."""
+    mix_time = default_mix_time(room, c) if tail.mix_time is None else float(tail.mix_time)
+    fade_time = 0.25 * mix_time if tail.fade_time is None else float(tail.fade_time)
+    return int(round(mix_time * sample_rate)), max(1, int(round(fade_time * sample_rate)))
+
+
+def tail_energy_law(room, betas, sample_rate: float, c: float = SPEED_OF_SOUND):
+    """``tau -> ln(sigma^2 D(tau))``, ``tau`` in seconds: the expected squared sample of the image-source field (``tail_envelope``
+    states the law and the quadrature rule)."""
+    room = _room(room)
+    betas = np.ascontiguousarray(betas, dtype=np.float64)
+    if betas.shape != (6,) or not np.all(np.isfinite(betas)) or np.any(betas <= 0.0) or np.any(betas > 1.0):
+        raise ValueError("the tail's envelope needs six reflection coefficients in (0, 1]")
+    if not (np.isfinite(sample_rate) and sample_rate > 0.0 and np.isfinite(c) and c > 0.0):
+        raise ValueError("sample_rate and c must be finite and positive")
+    c = float(c)
+    ln_sigma2 = np.log(c / (4.0 * np.pi * float(np.prod(room)) * float(sample_rate)))
+    lam = -np.log(betas[0::2] * betas[1::2]) / room
+    x, w = np.polynomial.legendre.leggauss(ENVELOPE_QUADRATURE)
+    mu, w_mu = 0.5 * (x + 1.0), 0.5 * w
+    phi, w_phi = 0.25 * np.pi * (x + 1.0), 0.25 * np.pi * w
+    s = np.sqrt(1.0 - mu * mu)
+    rate = (lam[0] * np.cos(phi)[None, :] + lam[1] * np.sin(phi)[None, :]) * s[:, None] + lam[2] * mu[:, None]     # (mu, phi)
+    ln_w = np.log(w_mu[:, None] * w_phi[None, :]) + np.log(2.0 / np.pi)
+
+    def ln_energy(tau: float) -> float:
+        e = ln_w - c * float(tau) * rate
+        top = e.max()
+        return float(ln_sigma2 + top + np.log(np.exp(e - top).sum()))
+
+    return ln_energy
+
+
+def tail_envelope(room, betas, ir_len: int, sample_rate: float, mix: int, c: float = SPEED_OF_SOUND,
+                  rt60: Optional[float] = None) -> np.ndarray:
+    """The float64 table ``ln_env`` of ``n_knots_of(ir_len)`` log-amplitude knots of the tail, knot ``k`` at sample ``256 k``: THE
+    TABLE THIS RETURNS IS THE DEFINITION the kernel is held to.
+
+    ``sigma^2 = c / (4 pi V fs)``: images are uniform in space at density ``1 / V``, each carries ``a^2 = gain / (4 pi d)^2``, and
+    ``4 pi d^2 (c / fs) / V`` of them land per sample.  An image in direction ``n`` at distance ``d`` has been reflected about
+    ``d |n_i| / L_i`` times on axis ``i``, half by each wall, so with ``lambda_i = -ln(beta_i0 beta_i1) / L_i`` its energy gain
+    is ``exp(-d sum_i lambda_i |n_i|)``; averaged over the directions of an octant, at ``d = c tau``,
+
+        D(tau) = (2 / pi) int_0^1 dmu int_0^(pi/2) dphi exp(-c tau (lambda_x s cos phi + lambda_y s sin phi + lambda_z mu)),
+
+    ``s = sqrt(1 - mu^2)``.  THE RULE: both integrals by the 64-point Gauss-Legendre rule
+    (``numpy.polynomial.legendre.leggauss(64)``, nodes ``x_j`` and weights ``w_j`` on [-1, 1]) mapped linearly:
+    ``mu_j = (x_j + 1) / 2`` with weight ``w_j / 2``, ``phi_j = pi (x_j + 1) / 4`` with weight ``pi w_j / 4``; the double sum is
+    taken in the logarithm (the largest exponent is subtracted first), so a ``D`` below the float64 range still gives a finite
+    knot.
+
+    Model "ism" (``rt60`` None): ``ln_env[k] = 0.5 ln(sigma^2 D(256 k / fs))``.  With ``rt60 = T``:
+    ``ln_env[k] = 0.5 ln(sigma^2 D(mix / fs)) - (3 ln 10 / T) (256 k - mix) / fs``: level-matched to the image field at the mixing
+    sample, then exponential at the requested rate.  A ``beta`` of 0 is a ValueError."""
+    ln_energy = tail_energy_law(room, betas, sample_rate, c)
+    if int(ir_len) != ir_len or ir_len < 1 or int(mix) != mix or mix < 0:
+        raise ValueError("ir_len must be an integer >= 1 and mix an integer >= 0")
+    if rt60 is not None and not (np.isfinite(rt60) and rt60 > 0.0):
+        raise ValueError("rt60 must be finite and positive")
+    fs = float(sample_rate)
+    knots = KNOT_SPACING * np.arange(n_knots_of(ir_len), dtype=np.float64)
+    if rt60 is None:
+        return np.array([0.5 * ln_energy(t / fs) for t in knots], dtype=np.float64)
+    return 0.5 * ln_energy(int(mix) / fs) - (3.0 * np.log(10.0) / float(rt60)) * (knots - int(mix)) / fs
+
+
+def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED_OF_SOUND, max_order=None, tail=None):
     """The host-side validation of ``shoebox_irs_device`` (ValueError); returns the arguments as the call takes them."""
     room = _room(room)
     betas = np.ascontiguousarray(betas, dtype=np.float64)
@@ -74,6 +203,8 @@ def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED
         raise ValueError("sample_rate and c must be finite and positive")
     if max_order is not None and (int(max_order) != max_order or max_order < 0):
         raise ValueError("max_order must be None or an integer >= 0")
+    if tail is not None:
+        _check_tail(tail, betas)
     gap = np.sqrt(((capsules[:, None, :] - sources[None, :, :]) ** 2).sum(axis=2))
     if gap.min() < MIN_DISTANCE:
         raise ValueError(f"every source must be at least {MIN_DISTANCE} m from every capsule (closest: {gap.min():.4g} m)")
@@ -81,16 +212,32 @@ def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED
 
 
 def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sample_rate: float, c: float = SPEED_OF_SOUND,
-                       max_order: Optional[int] = None):
+                       max_order: Optional[int] = None, tail: Optional[ShoeboxTail] = None, source_id0: int = 0,
+                       capsule_id0: int = 0):
     """The IRs of ``sources`` (N, 3) at ``capsules`` (C, 3) in the room ``(Lx, Ly, Lz)`` with wall reflection coefficients
     ``betas = (x0, x1, y0, y1, z0, z1)``: ``(device buffer, (stride_c, stride_n), ir_len)`` as ``ingest.pack_ragged_irs`` returns
-    it, enqueued on the renderer's stream.  The two coordinate tables are all that is uploaded."""
+    it, enqueued on the renderer's stream.  The two coordinate tables are all that is uploaded.  With ``tail`` (a ``ShoeboxTail``)
+    the rows carry a diffuse tail (``al_ism_shoebox_tail``; the envelope's knot table is uploaded too); row (c, n) draws its
+    noise as source ``source_id0 + n`` at capsule ``capsule_id0 + c``, so a caller that splits a tensor over several calls gives
+    each part its offsets."""
     room, betas, sources, capsules, ir_len, fs, c, order = check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c,
-                                                                          max_order)
+                                                                          max_order, tail)
+    if tail is not None:
+        for name, v, count in (("source_id0", source_id0, len(sources)), ("capsule_id0", capsule_id0, len(capsules))):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0 or int(v) + count > 1 << 32:
+                raise ValueError(f"{name} must be an integer >= 0 with {name} + count <= 2^32")
     mem, lib = renderer.mem, renderer.lib
     n, n_cap, pitch = len(sources), len(capsules), pitch_of(ir_len)
     src_dev, cap_dev = mem.upload(sources.reshape(-1)), mem.upload(capsules.reshape(-1))
     out = mem.empty(n_cap * n * pitch)
+    if tail is not None:
+        mix, fade = tail_samples(tail, room, fs, c)
+        ln_env = tail_envelope(room, betas, ir_len, fs, mix, c, tail.rt60)
+        env_dev = mem.upload(ln_env)
+        lib.call("al_ism_shoebox_tail", mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, room.ctypes.data_as(ct.POINTER(ct.c_double)),
+                 betas.ctypes.data_as(ct.POINTER(ct.c_double)), c, fs, order, ir_len, pitch, mix, fade, int(tail.seed), int(source_id0),
+                 int(capsule_id0), mem.ptr(env_dev), len(ln_env), mem.ptr(out), mem.stream())
+        return out, (n * pitch, pitch), ir_len
     lib.call("al_ism_shoebox", mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, room.ctypes.data_as(ct.POINTER(ct.c_double)),
              betas.ctypes.data_as(ct.POINTER(ct.c_double)), c, fs, order, ir_len, pitch, mem.ptr(out), mem.stream())
     return out, (n * pitch, pitch), ir_len

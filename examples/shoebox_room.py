@@ -2,7 +2,10 @@
 """Render a scene in a rectangular room whose impulse responses are generated on the MI355X (image-source method): no IR array is
 ever made on the host or sent over PCIe.
 
-    python examples/shoebox_room.py [output_dir]
+    python examples/shoebox_room.py [--tail] [output_dir]
+
+--tail: two seconds of IR instead of half a second, exact images up to the mixing time (42 ms) and a diffuse tail of seeded noise
+past it (shoebox.ShoeboxTail), with no order limit: the long rows cost a write of their bytes.
 """
 import os
 import sys
@@ -11,14 +14,18 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from audiblelight_amd import core  # noqa: E402
+from audiblelight_amd import core, shoebox  # noqa: E402
 
 
-def main(out_dir="shoebox_out"):
+def main(out_dir="shoebox_out", tail=False):
     rng = np.random.default_rng(0)
     sr = 24000
-    # a 6 x 5 x 3 m room with a reverberation time of 0.4 s (Sabine), half a second of IR, images up to order 20
-    state = core.ShoeboxIRState((6.0, 5.0, 3.0), rt60=0.4, ir_len=sr // 2, sample_rate=sr, max_order=20)
+    if tail:
+        # the same room, two seconds of IR: every image of the first 53 ms, then the diffuse tail
+        state = core.ShoeboxIRState((6.0, 5.0, 3.0), rt60=0.4, ir_len=2 * sr, sample_rate=sr, tail=shoebox.ShoeboxTail(seed=2024))
+    else:
+        # a 6 x 5 x 3 m room with a reverberation time of 0.4 s (Sabine), half a second of IR, images up to order 20
+        state = core.ShoeboxIRState((6.0, 5.0, 3.0), rt60=0.4, ir_len=sr // 2, sample_rate=sr, max_order=20)
     centre, radius = np.array([3.1, 2.4, 1.5]), 0.042
     tetra = np.array([[1, 1, 1], [1, -1, -1], [-1, 1, -1], [-1, -1, 1]]) / np.sqrt(3.0)
     state.add_microphone("mic000", centre + radius * tetra)            # four omnidirectional point capsules
@@ -37,4 +44,4 @@ def main(out_dir="shoebox_out"):
 
 
 if __name__ == "__main__":
-    main(*sys.argv[1:])
+    main(*[a for a in sys.argv[1:] if a != "--tail"], tail="--tail" in sys.argv[1:])

@@ -611,6 +611,28 @@ int al_mix_plan_get(const al_mix_plan *plan, al_mix_tables *tables);
 int al_ism_shoebox(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
                    const double *beta, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, float *out,
                    al_stream_t stream);
+/* The same rows with a DIFFUSE TAIL (DESIGN.md "Shoebox IRs: the diffuse tail"): the exact image sum up to a mixing sample, seeded
+ * Gaussian noise under an envelope past it.  Everything of al_ism_shoebox stands; further, with M = mix >= 0, F = fade >= 1 and
+ * ln_env a float64 DEVICE table of n_knots = (ir_len - 1) / 256 + 2 log-amplitude knots, knot k at sample 256 k, for t in [0, ir_len)
+ * of row (c, n):
+ *   x = clamp((t - M) / F, 0, 1), w_e = cos(pi x / 2), w_l = sin(pi x / 2): exactly (1, 0) for t <= M, exactly (0, 1) for t >= M + F;
+ *   e(t) = exp((1 - p) ln_env[k] + p ln_env[k + 1]), k = t / 256, p = (t % 256) / 256 (p == 0 reads knot k alone);
+ *   g(t) = normal number t % 4 of the Philox-4x32-10 block with counter (t / 4, source_id0 + n, 4, capsule_id0 + c) and key
+ *          (seed lo, seed hi), Box-Muller as al_normal_fill has it (u1, u2 formed in float32; pairs (x, y) and (z, w));
+ *   out[(c * n_sources + n) * pitch + t] = w_e y_ism(t) + w_l e(t) g(t), y_ism the float64 image sum of al_ism_shoebox (max_order still
+ *   applies; needed for t < M + F only, and the images past it are never visited), combined in float64 and rounded to float32 once;
+ *   where w_l == 0 no noise term is formed.  Pad samples [ir_len, pitch) are +0.
+ * A row's bits depend on the room, the pair, the seed and the two ids alone: not on n_sources, n_capsules, the pitch, the grid or
+ * the other rows; two runs are identical; with mix >= ir_len the output has the bits of al_ism_shoebox.  Every sample is written
+ * exactly once and out is never read.  Two launches on `stream` (the image part below ceil((M + F) / 256) * 256, the tail from there
+ * on); no allocation, no synchronisation.
+ * AL_E_BADARG: everything al_ism_shoebox refuses; mix < 0; fade < 1; a negative id; source_id0 + n_sources or capsule_id0 +
+ * n_capsules above 2^32; n_knots other than (ir_len - 1) / 256 + 2; a null table; an `out` that is not 16-byte aligned (REFUSED, not
+ * worked around: the tail is written with 16-byte stores). */
+int al_ism_shoebox_tail(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
+                        const double *beta, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix,
+                        int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots,
+                        float *out, al_stream_t stream);
 
 /* dst[t] = src[t mod m] for t < n: np.pad(..., mode="wrap") of Augmentation.process. */
 int al_wrap_copy(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream);
