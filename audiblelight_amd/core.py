@@ -249,8 +249,10 @@ def stage_event_chains(events, ignore_cache: bool = False) -> list:
 class MicArray:
     """Capsule count holder (micarrays.py:36-162): only ``n_capsules`` / ``n_listeners`` matter to the path."""
 
-    def __init__(self, alias: str, n_capsules: int, metadata: Optional[dict] = None):
-        self.alias, self.n_capsules, self.n_listeners = alias, int(n_capsules), int(n_capsules)
+    def __init__(self, alias: str, n_capsules: int, metadata: Optional[dict] = None, n_listeners: Optional[int] = None):
+        # n_listeners: points in space (an FOA listener is one point with four channels); None: one per capsule
+        self.alias, self.n_capsules = alias, int(n_capsules)
+        self.n_listeners = int(n_capsules) if n_listeners is None else int(n_listeners)
         self.metadata = dict(metadata or {})
 
     def to_dict(self) -> dict:   # micarrays.py:207-240 (coordinates only when loaded from a reference file)
@@ -298,9 +300,11 @@ class ShoeboxIRState:
     """WorldState stand-in for a rectangular room whose IRs are generated on the device by the image-source method
     (shoebox.py, DESIGN.md "Shoebox IRs"): the reference's ``WorldStateShoebox`` (worldstate.py:3105-3110) is declared and left
     empty.  ``betas``: six wall reflection coefficients (x0, x1, y0, y1, z0, z1), or ``rt60`` for one uniform coefficient by
-    Sabine's law.  Microphones are sets of omnidirectional point capsules; emitters are IR columns in event order (a moving event
-    contributes one row per trajectory point).  ``simulate()`` enqueues one generation per microphone; the tensors stay in HBM.
-    ``tail``: a ``shoebox.ShoeboxTail`` (or its dictionary) gives every row a diffuse tail past the mixing time; capsules are
+    Sabine's law.  Microphones are sets of point capsules, omnidirectional or with a first-order pattern each
+    (``add_microphone(patterns=...)``), or one point with the four channels of first-order ambisonics (``add_foa_listener``);
+    emitters are IR columns in event order (a moving event contributes one row per trajectory point).  ``simulate()`` enqueues one
+    generation per microphone; the tensors stay in HBM.
+    ``tail``: a ``shoebox.ShoeboxTail`` (or its dictionary) gives every row a diffuse tail past the mixing time; channels are
     numbered through the microphones in their order, so no two rows of the state share noise."""
 
     name = "SHOEBOX"
@@ -321,21 +325,59 @@ class ShoeboxIRState:
         self.metadata = dict(metadata or {})
         self.microphones: "OrderedDict[str, MicArray]" = OrderedDict()
         self.emitters: "OrderedDict[str, np.ndarray]" = OrderedDict()
-        self._capsules: "OrderedDict[str, np.ndarray]" = OrderedDict()
+        self._capsules: "OrderedDict[str, np.ndarray]" = OrderedDict()      # receiver positions (P, 3) of each microphone
+        self._patterns: "OrderedDict[str, Optional[np.ndarray]]" = OrderedDict()     # None (omni) or (P, K, 4)
         self._irs = None
         # refuse bad room parameters here, not at the first simulate()
         inside = 0.5 * self.room[None, :]
         shoebox.check_arguments(self.room, self.betas, inside, inside + 0.25 * self.room[None, :], self.ir_len, self.sample_rate,
                                 self.c, self.max_order, self.tail)
 
-    def add_microphone(self, alias: str, capsule_positions) -> MicArray:
+    def add_microphone(self, alias: str, capsule_positions, patterns=None, capsule_names=None) -> MicArray:
+        """``capsule_positions`` (C, 3).  ``patterns`` (C, 4): one first-order pattern ``(w, vx, vy, vz)`` per capsule in room axes
+        (``shoebox.omni``, ``first_order``, ``cardioid``); None: omnidirectional capsules."""
+        from . import shoebox
+
+        capsules = shoebox._points(capsule_positions, self.room, f"capsules of {alias}")
+        if patterns is not None:
+            patterns = np.asarray(patterns, dtype=np.float64)
+            if patterns.shape != (len(capsules), 4):
+                raise ValueError(f"patterns of {alias} must have shape ({len(capsules)} capsules, 4), not {patterns.shape}")
+            patterns = patterns[:, None, :]
+        return self._add_receivers(alias, capsules, patterns, capsule_names, {})
+
+    def add_foa_listener(self, alias: str, position, order: str = "wyzx") -> MicArray:
+        """One point with the four channels of first-order ambisonics (the reference's ``FOAListener``, micarrays.py:371-394), SN3D
+        weights, channels in ``order`` ("wyzx": AmbiX), axes the room's."""
+        from . import shoebox
+
+        patterns = shoebox.foa_patterns(order)
+        point = shoebox._points(np.atleast_2d(np.asarray(position, dtype=np.float64)), self.room, f"position of {alias}")
+        if len(point) != 1:
+            raise ValueError("an FOA listener is one point")
+        return self._add_receivers(alias, point, patterns[None, :, :], list(order.lower()),
+                                   dict(micarray_type="FOAListener", channel_layout_type="foa"))
+
+    def _add_receivers(self, alias: str, positions: np.ndarray, patterns, capsule_names, metadata: dict) -> MicArray:
+        """``positions`` (P, 3) with ``patterns`` None (omni, one channel each) or (P, K, 4): a microphone of P K channels."""
         from . import shoebox
 
         if alias in self.microphones:
             raise KeyError(f"Microphone with alias {alias} already exists")
-        capsules = shoebox._points(capsule_positions, self.room, f"capsules of {alias}")
-        self._capsules[alias] = capsules
-        self.microphones[alias] = MicArray(alias, len(capsules), dict(micarray_type="MicArray", coordinates_absolute=capsules.tolist()))
+        md = dict(micarray_type="MicArray", coordinates_absolute=positions.tolist())
+        n_channels = len(positions)
+        if patterns is not None:
+            patterns = shoebox.check_patterns(patterns, len(positions))
+            n_channels = len(positions) * patterns.shape[1]
+            md["patterns"] = patterns.reshape(-1, 4).tolist()      # one row per channel, c = p K + k
+        if capsule_names is not None:
+            capsule_names = [str(v) for v in capsule_names]
+            if len(capsule_names) != n_channels:
+                raise ValueError(f"{alias} has {n_channels} channels but {len(capsule_names)} capsule names")
+            md["capsule_names"] = capsule_names
+        md.update(metadata)
+        self._capsules[alias], self._patterns[alias] = positions, patterns
+        self.microphones[alias] = MicArray(alias, n_channels, md, n_listeners=len(positions))
         self._irs = None
         return self.microphones[alias]
 
@@ -368,12 +410,13 @@ class ShoeboxIRState:
         r = self.renderer or synthesize.get_renderer()
         sources = self.emitter_positions
         irs = OrderedDict()
-        capsule_id0 = 0     # the tail's noise: capsules are numbered through the microphones, emitters are one table already
+        capsule_id0 = 0     # the tail's noise: channels are numbered through the microphones, emitters are one table already
         for alias, capsules in self._capsules.items():
             buf, strides, _ = shoebox.shoebox_irs_device(r, self.room, self.betas, sources, capsules, self.ir_len, self.sample_rate,
-                                                         self.c, self.max_order, self.tail, 0, capsule_id0)
-            irs[alias] = shoebox.DeviceIRTensor(r, buf, strides, (len(capsules), len(sources), self.ir_len))
-            capsule_id0 += len(capsules)
+                                                         self.c, self.max_order, self.tail, 0, capsule_id0, self._patterns[alias])
+            n_channels = self.microphones[alias].n_capsules
+            irs[alias] = shoebox.DeviceIRTensor(r, buf, strides, (n_channels, len(sources), self.ir_len))
+            capsule_id0 += n_channels
         self._irs = irs
 
     @property
@@ -406,13 +449,22 @@ class ShoeboxIRState:
 
     @classmethod
     def from_dict(cls, state_d: dict, renderer=None) -> "ShoeboxIRState":
+        from . import shoebox
+
         box = state_d["shoebox"]
         keep = {k: v for k, v in state_d.items() if k not in ("backend", "sample_rate", "emitters", "microphones", "shoebox")}
         state = cls(box["room"], betas=box["betas"], ir_len=box["ir_len"], sample_rate=state_d.get("sample_rate") or config.SAMPLE_RATE,
                     c=box.get("c", 343.0), max_order=box.get("max_order"), renderer=renderer, metadata=keep, tail=box.get("tail"))
         state.rt60 = box.get("rt60")
         for alias, md in state_d["microphones"].items():
-            mic = state.add_microphone(alias, md["coordinates_absolute"])
+            positions = shoebox._points(md["coordinates_absolute"], state.room, f"capsules of {alias}")
+            patterns = md.get("patterns")      # one row per channel; several channels share a coordinate row (an FOA listener)
+            if patterns is not None:
+                patterns = np.asarray(patterns, dtype=np.float64)
+                if patterns.ndim != 2 or patterns.shape[1:] != (4,) or len(patterns) % len(positions):
+                    raise ValueError(f"patterns of {alias} must be (channels, 4) with a whole number of channels per position")
+                patterns = patterns.reshape(len(positions), -1, 4)
+            mic = state._add_receivers(alias, positions, patterns, md.get("capsule_names"), {})
             mic.metadata.update({k: v for k, v in md.items() if k not in ("n_capsules",)})
         for alias, rows in state_d["emitters"].items():
             state.add_emitters(rows, alias)

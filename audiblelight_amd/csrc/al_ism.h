@@ -69,7 +69,8 @@ struct IsmTail {
   int32_t y_end;          // min(ir_len, M + F): the image sum is needed below it only
   int32_t split;          // ceil((M + F) / ISM_TILE) * ISM_TILE, at most pitch rounded up to ISM_TILE: k_ism_tail owns [split, pitch)
   int32_t tail_blocks;    // workgroups of k_ism_tail per row
-  uint32_t seed_lo, seed_hi, source_id0, capsule_id0, reserved;
+  uint32_t seed_lo, seed_hi, source_id0, capsule_id0;
+  uint32_t env_stride;    // knots between the tables of two rows c (al_ism_shoebox_dir_tail: n_knots); 0: one table serves every row
 };
 
 struct IsmJob {
@@ -315,7 +316,8 @@ __global__ __launch_bounds__(ISM_TAIL_THREADS) void k_ism_tail(IsmJob job) {
     if (t < job.ir_len) {
       const float4 g = ism_tail_normal4(job.tail, t >> 2, n, cap);
       const int k = t / ISM_TILE, r = t % ISM_TILE;   // r + 3 < ISM_TILE: the quad lies in one knot interval
-      const double a = job.tail.ln_env[k], b = job.tail.ln_env[k + 1];
+      const double *ln_env = job.tail.ln_env + (int64_t)cap * job.tail.env_stride;   // the row's own table
+      const double a = ln_env[k], b = ln_env[k + 1];
       const double inv = 1.0 / (double)ISM_TILE, p = (double)r * inv, step = (b - a) * inv;
       const double e0 = exp(r == 0 ? a : (1.0 - p) * a + p * b);
       double e1, e2, e3;
@@ -418,6 +420,274 @@ inline void launch_ism_shoebox_tail(const IsmJob &job, hipStream_t stream) {
   hipLaunchKernelGGL(k_ism_shoebox<true>, dim3((unsigned)(job.n_tiles * pairs)), dim3(ISM_THREADS), 0, stream, job);
   if (job.tail.tail_blocks > 0)
     hipLaunchKernelGGL(k_ism_tail, dim3((unsigned)(job.tail.tail_blocks * pairs)), dim3(ISM_TAIL_THREADS), 0, stream, job);
+}
+
+// DIRECTIONAL RECEIVERS (al_ism_shoebox_dir, al_ism_shoebox_dir_tail; DESIGN.md "Shoebox IRs: directional receivers").  A call takes
+// P receiver positions with K <= 4 channels each and a pattern table pat[P][K][4] = (w, vx, vy, vz); row c = p K + k of the output
+// is the image sum of position p with every amplitude multiplied by w + v . R / |R|.  The K channels of a position share every
+// image, its delay and its 81 taps, so
+//   k_ism_shoebox_dir<K, TAIL>  one workgroup of one wave per (position, source, tile) serves all K rows: the lattice walk, the
+//     count, the prefix sum and the LDS list of k_ism_shoebox happen once (the same walk, the same canonical order, the same shell),
+//     a list entry carries the K gains beside what is common, and a lane forms the tap's shape once per (image, sample) and adds it
+//     into K float64 accumulators: a channel costs a multiply-add per tap.  The list window is ISM_DIR_LIST = 96 entries of
+//     48 + 8 K bytes (rounded to 16), which keeps the workgroup's LDS at 7448 B (K <= 2) or 8984 B (K >= 3): the register count,
+//     not the LDS, sets the occupancy.  The order of a sample's sum does not depend on the window's length.
+//   k_ism_tail  as it is, over the P K rows, each row reading its own knot table (IsmTail::env_stride).
+constexpr int ISM_MAX_CHANNELS = 4;
+constexpr int ISM_DIR_LIST = 96;
+
+struct IsmDirJob {
+  IsmJob base;              // n_capsules: the P K ROWS (what k_ism_tail and the id ranges count); capsules: the P positions
+  const double *patterns;   // (P, K, 4), device
+  int32_t n_positions, n_channels;
+};
+
+template <int K>
+struct alignas(16) IsmDirEntry {
+  double f, g, a, c81, s81;   // as IsmEntry, a and g of the omnidirectional image
+  int32_t t0, reserved;
+  double gain[K];             // w + v . R / d of each channel
+};
+
+template <int K, bool TAIL>
+__global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox_dir(IsmDirJob dj) {
+  __shared__ IsmDirEntry<K> list[ISM_DIR_LIST];
+  __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];   // cos, sin(2 pi j / 81), j = -40 .. 40
+  __shared__ int wave_total[2];
+  const IsmJob &job = dj.base;
+  const int tid = threadIdx.x, lane = tid;
+  const int tile = (int)(blockIdx.x % (unsigned)job.n_tiles);
+  const int64_t pair = blockIdx.x / (unsigned)job.n_tiles;   // p * N + n
+  const int n = (int)(pair % job.n_sources), pos = (int)(pair / job.n_sources);
+  const int t_lo = tile * ISM_TILE, t = t_lo + tid;
+  const int y_end = TAIL ? job.tail.y_end : job.ir_len;
+  const int t_hi = min(t_lo + ISM_TILE, y_end) - 1;
+  const int64_t row_stride = (int64_t)job.n_sources * job.pitch;   // from channel k to channel k + 1
+  float *row = job.out + ((int64_t)pos * K * job.n_sources + n) * (int64_t)job.pitch;   // channel 0
+  if (t_lo >= job.ir_len) {   // a tile of pad samples only
+    for (int k = 0; k < K; ++k)
+      for (int s = 0; s < ISM_PER_LANE; ++s)
+        if (t + s * ISM_THREADS < job.pitch) row[k * row_stride + t + s * ISM_THREADS] = 0.f;
+    return;
+  }
+  for (int i = tid; i < ISM_TAPS; i += ISM_THREADS) sincospi(2.0 * (double)(i - ISM_HALF) / (double)ISM_TAPS, &win_s[i], &win_c[i]);
+  const double *pat = dj.patterns + (int64_t)pos * (4 * K);   // uniform over the wave: scalar loads, no vector register holds a pattern
+
+  const double sx = job.sources[3 * n], sy = job.sources[3 * n + 1], sz = job.sources[3 * n + 2];
+  const double rx = job.capsules[3 * pos], ry = job.capsules[3 * pos + 1], rz = job.capsules[3 * pos + 2];
+  const double Lx = job.L[0], Ly = job.L[1], Lz = job.L[2];
+  // the shell of this tile, a sample wider than the taps reach on either side
+  const double d_hi = (double)(t_hi + ISM_HALF + 2) * job.c / job.fs, d_lo = (double)(t_lo - ISM_HALF - 2) * job.c / job.fs;
+  const double hi2 = d_hi * d_hi, lo2 = d_lo > 0.0 ? d_lo * d_lo : 0.0;
+  const int order = job.max_order;
+  int Qx = ism_clamp(floor(d_hi / Lx) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH), Qy = ism_clamp(floor(d_hi / Ly) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH),
+      Qz = ism_clamp(floor(d_hi / Lz) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH);
+  if (order >= 0) {
+    Qx = min(Qx, order);
+    Qy = min(Qy, order);
+    Qz = min(Qz, order);
+  }
+  const int64_t ny = 2 * (int64_t)Qy + 1, n_columns = (2 * (int64_t)Qx + 1) * ny;
+
+  // does image qz of column `col` touch the tile?  Rz, t0, tau and d of the image either way
+  auto touches = [&](const IsmColumn &col, int qz, double &Rz, double &d, double &tau, int &t0) {
+    Rz = ism_offset(qz, sz, rz, Lz);
+    d = sqrt(col.rho2 + Rz * Rz);
+    tau = d * job.fs / job.c;
+    if (!(tau < 2.0e9) || !(d > 0.0)) return false;
+    t0 = (int)rint(tau);
+    return t0 + ISM_HALF >= t_lo && t0 - ISM_HALF <= t_hi;
+  };
+
+  double acc[ISM_PER_LANE][K] = {};
+  int parity = 0;
+  for (int64_t base = 0; base < n_columns; base += ISM_THREADS, parity ^= 1) {
+    // 1. this lane's column
+    const int64_t ci = base + tid;
+    IsmColumn col;
+    col.a1 = col.a2 = 0;
+    col.b1 = col.b2 = -1;
+    bool dead = true;
+    if (ci < n_columns) {
+      const int qx = (int)(ci / ny) - Qx, qy = (int)(ci % ny) - Qy;
+      const int k_xy = abs(qx) + abs(qy);
+      const double Rx = ism_offset(qx, sx, rx, Lx), Ry = ism_offset(qy, sy, ry, Ly);
+      col.rho2 = Rx * Rx + Ry * Ry;
+      if ((order < 0 || k_xy <= order) && col.rho2 < hi2) {
+        dead = false;
+        col.ln_xy = ism_log_gain(qx, job.ln_beta, job.beta_zero, dead) + ism_log_gain(qy, job.ln_beta + 2, job.beta_zero + 2, dead);
+        const int Kz = order < 0 ? Qz : min(Qz, order - k_xy);
+        const double z_max = sqrt(hi2 - col.rho2);
+        // image qz lies in (qz Lz, (qz + 1) Lz): one cell of margin on either side
+        col.a1 = ism_clamp(floor((rz - z_max) / Lz) - 1.0, -Kz, Kz);
+        const int top = ism_clamp(floor((rz + z_max) / Lz) + 1.0, -Kz, Kz);
+        col.b1 = top;   // one run, unless the inner sphere cuts it in two
+        if (lo2 > col.rho2) {   // the cells wholly inside the inner sphere are left out
+          const double z_min = sqrt(lo2 - col.rho2);
+          const double ea = ceil((rz - z_min) / Lz) + 1.0, eb = floor((rz + z_min) / Lz) - 2.0;
+          if (ea <= eb) {
+            col.b1 = ism_clamp(ea - 1.0, -Kz - 1, Kz);
+            col.a2 = ism_clamp(eb + 1.0, -Kz, Kz + 1);
+            col.b2 = top;
+          }
+        }
+      }
+    }
+    int count = 0;
+    if (!dead) {
+      double Rz, d, tau;
+      int t0;
+      for (int run = 0; run < 2; ++run)
+        for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz) {
+          bool gone = false;
+          ism_log_gain(qz, job.ln_beta + 4, job.beta_zero + 4, gone);
+          if (!gone && touches(col, qz, Rz, d, tau, t0)) ++count;
+        }
+    }
+    // 2. exclusive prefix sum of the counts: suffix sums by shuffles, the total (lane 0's) through LDS
+    int suffix = count;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int other = __shfl_down(suffix, off, 64);
+      if (lane + off < 64) suffix += other;
+    }
+    if (lane == 0) wave_total[parity] = suffix;
+    __syncthreads();
+    const int total = wave_total[parity], offset = total - suffix;
+    // 3. + 4. the list, a window of ISM_DIR_LIST at a time
+    for (int w0 = 0; w0 < total; w0 += ISM_DIR_LIST) {
+      if (count > 0 && offset < w0 + ISM_DIR_LIST && offset + count > w0) {
+        // the column's Rx, Ry again (not kept across the gather: registers)
+        const double Rx = ism_offset((int)(ci / ny) - Qx, sx, rx, Lx), Ry = ism_offset((int)(ci % ny) - Qy, sy, ry, Ly);
+        int at = offset;
+        for (int run = 0; run < 2; ++run)
+          for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz) {
+            bool gone = false;
+            const double ln_z = ism_log_gain(qz, job.ln_beta + 4, job.beta_zero + 4, gone);
+            double Rz, d, tau;
+            int t0;
+            if (gone || !touches(col, qz, Rz, d, tau, t0)) continue;
+            if (at >= w0 && at < w0 + ISM_DIR_LIST) {
+              // the gains go to the list before the common part is formed: neither is live while the other is computed
+              IsmDirEntry<K> &e = list[at - w0];
+              {
+                const double ux = Rx / d, uy = Ry / d, uz = Rz / d;   // the direction the image arrives from
+#pragma unroll
+                for (int k = 0; k < K; ++k) e.gain[k] = pat[4 * k] + (pat[4 * k + 1] * ux + pat[4 * k + 2] * uy + pat[4 * k + 3] * uz);
+              }
+              double sp, cp, s81, c81;
+              const double f = tau - (double)t0, a = exp(col.ln_xy + ln_z) / (4.0 * M_PI * d);
+              sincospi(f, &sp, &cp);
+              sincospi(2.0 * f / (double)ISM_TAPS, &s81, &c81);
+              e.t0 = t0;
+              e.reserved = 0;
+              e.f = f;
+              e.a = a;
+              e.g = -0.5 * a * sp / M_PI;
+              e.s81 = s81;
+              e.c81 = c81;
+            }
+            ++at;
+          }
+      }
+      __syncthreads();
+      const int n_list = min(ISM_DIR_LIST, total - w0);
+      for (int i = 0; i < n_list; ++i) {
+        const int j0 = t - list[i].t0;   // of the lane's first sample; the others are 64 apart, so at most two are in reach
+        if (j0 > ISM_HALF || j0 + (ISM_PER_LANE - 1) * ISM_THREADS < -ISM_HALF) continue;
+        const IsmDirEntry<K> e = list[i];
+#pragma unroll
+        for (int s = 0; s < ISM_PER_LANE; ++s) {
+          const int j = j0 + s * ISM_THREADS;
+          if (j < -ISM_HALF || j > ISM_HALF || t + s * ISM_THREADS >= y_end) continue;
+          const double u = (double)j - e.f;
+          if (!(fabs(u) < 0.5 * (double)ISM_TAPS)) continue;
+          if (u == 0.0) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) acc[s][k] += e.a * e.gain[k];
+          } else {   // the omnidirectional tap, once for the K channels
+            const double window = 1.0 + (win_c[j + ISM_HALF] * e.c81 + win_s[j + ISM_HALF] * e.s81);
+            const double shape = ((j & 1) ? -e.g : e.g) * window / u;
+#pragma unroll
+            for (int k = 0; k < K; ++k) acc[s][k] += shape * e.gain[k];
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < ISM_PER_LANE; ++s) {
+    const int ts = t + s * ISM_THREADS;
+    if (ts >= job.pitch) continue;
+    bool mixed = false;
+    double w_e = 1.0, w_l = 0.0;
+    if constexpr (TAIL) {
+      if (ts > job.tail.mix && ts < job.ir_len) {   // at or below M: w_e = 1, w_l = 0, the image sum as it is
+        mixed = true;
+        const double x = ((double)ts - (double)job.tail.mix) / (double)job.tail.fade;
+        w_e = 0.0, w_l = 1.0;
+        if (x < 1.0) sincospi(0.5 * x, &w_l, &w_e);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      double v = acc[s][k];
+      if constexpr (TAIL) {
+        if (mixed) {
+          const int c = pos * K + k;   // the row: its own noise stream and its own knot table
+          const float4 g4 = ism_tail_normal4(job.tail, ts >> 2, n, c);
+          const float g = (ts & 2) ? ((ts & 1) ? g4.w : g4.z) : ((ts & 1) ? g4.y : g4.x);
+          v = w_e * v + w_l * ism_envelope(job.tail.ln_env + (int64_t)c * job.tail.env_stride, ts) * (double)g;
+        }
+      }
+      row[k * row_stride + ts] = ts < job.ir_len ? (float)v : 0.f;
+    }
+  }
+}
+
+// al_ism_shoebox_dir's arguments as the kernel's job (ism_prepare counts the image workgroups per POSITION; the rows are P K)
+inline int ism_dir_prepare(const double *sources, int32_t n_sources, const double *receivers, int32_t n_receivers, const double *patterns,
+                           int32_t n_channels, const double *L, const double *beta, double c, double fs, int32_t max_order,
+                           int32_t ir_len, int32_t pitch, float *out, IsmDirJob *dj) {
+  if (n_channels < 1 || n_channels > ISM_MAX_CHANNELS) return fail(AL_E_BADARG, "al_ism_shoebox_dir: n_channels must be in 1 .. 4");
+  if (!patterns) return fail(AL_E_BADARG, "al_ism_shoebox_dir: null pattern table");
+  if (int rc = ism_prepare(sources, n_sources, receivers, n_receivers, L, beta, c, fs, max_order, ir_len, pitch, out, &dj->base)) return rc;
+  if ((int64_t)n_receivers * n_channels > 0x7fffffff) return fail(AL_E_BADARG, "al_ism_shoebox_dir: more than 2^31 - 1 rows (n_receivers x n_channels)");
+  dj->patterns = patterns;
+  dj->n_positions = n_receivers;
+  dj->n_channels = n_channels;
+  dj->base.n_capsules = n_receivers * n_channels;
+  return AL_OK;
+}
+
+// al_ism_shoebox_dir_tail's further arguments: ism_tail_prepare over the P K rows, a knot table per row
+inline int ism_dir_tail_prepare(int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env,
+                                int32_t n_knots, IsmDirJob *dj) {
+  if (int rc = ism_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, &dj->base)) return rc;
+  dj->base.tail.env_stride = (uint32_t)n_knots;
+  return AL_OK;
+}
+
+template <bool TAIL>
+inline void launch_ism_dir_images(const IsmDirJob &dj, hipStream_t stream) {
+  const dim3 grid((unsigned)((int64_t)dj.base.n_tiles * dj.base.n_sources * dj.n_positions)), block(ISM_THREADS);
+  switch (dj.n_channels) {
+    case 1: hipLaunchKernelGGL((k_ism_shoebox_dir<1, TAIL>), grid, block, 0, stream, dj); break;
+    case 2: hipLaunchKernelGGL((k_ism_shoebox_dir<2, TAIL>), grid, block, 0, stream, dj); break;
+    case 3: hipLaunchKernelGGL((k_ism_shoebox_dir<3, TAIL>), grid, block, 0, stream, dj); break;
+    default: hipLaunchKernelGGL((k_ism_shoebox_dir<4, TAIL>), grid, block, 0, stream, dj); break;
+  }
+}
+
+inline void launch_ism_shoebox_dir(const IsmDirJob &dj, hipStream_t stream) { launch_ism_dir_images<false>(dj, stream); }
+
+inline void launch_ism_shoebox_dir_tail(const IsmDirJob &dj, hipStream_t stream) {
+  launch_ism_dir_images<true>(dj, stream);
+  const IsmJob &job = dj.base;
+  if (job.tail.tail_blocks > 0)
+    hipLaunchKernelGGL(k_ism_tail, dim3((unsigned)((int64_t)job.tail.tail_blocks * job.n_sources * job.n_capsules)), dim3(ISM_TAIL_THREADS),
+                       0, stream, job);
 }
 
 }  // namespace al

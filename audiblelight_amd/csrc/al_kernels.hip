@@ -622,6 +622,32 @@ int al_ism_shoebox_tail(const double *sources, int32_t n_sources, const double *
   return check_launch("k_ism_tail");
 }
 
+// ---- the same with first-order directional receivers: DESIGN.md "Shoebox IRs: directional receivers"
+int al_ism_shoebox_dir(const double *sources, int32_t n_sources, const double *receivers, int32_t n_receivers, const double *patterns,
+                       int32_t n_channels, const double *L, const double *beta, double c, double fs, int32_t max_order, int32_t ir_len,
+                       int32_t pitch, float *out, al_stream_t stream) {
+  al::IsmDirJob job;
+  if (int rc = al::ism_dir_prepare(sources, n_sources, receivers, n_receivers, patterns, n_channels, L, beta, c, fs, max_order, ir_len,
+                                   pitch, out, &job))
+    return rc;
+  al::launch_ism_shoebox_dir(job, (hipStream_t)stream);
+  return check_launch("k_ism_shoebox_dir");
+}
+
+int al_ism_shoebox_dir_tail(const double *sources, int32_t n_sources, const double *receivers, int32_t n_receivers,
+                            const double *patterns, int32_t n_channels, const double *L, const double *beta, double c, double fs,
+                            int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade, uint64_t seed,
+                            int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, float *out,
+                            al_stream_t stream) {
+  al::IsmDirJob job;
+  if (int rc = al::ism_dir_prepare(sources, n_sources, receivers, n_receivers, patterns, n_channels, L, beta, c, fs, max_order, ir_len,
+                                   pitch, out, &job))
+    return rc;
+  if (int rc = al::ism_dir_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, &job)) return rc;
+  al::launch_ism_shoebox_dir_tail(job, (hipStream_t)stream);
+  return check_launch("k_ism_tail");
+}
+
 int al_resample_poly(const float *x, int32_t rows, int64_t n_in, const float *taps, int32_t half_len, int32_t up, int32_t down,
                      float *out, int64_t n_out, int64_t out_pitch, al_stream_t stream) {
   if (!x || !taps || !out || rows <= 0 || rows > 65535 || n_in <= 0 || half_len < 0 || up <= 0 || down <= 0 || n_out <= 0 ||

@@ -2,8 +2,9 @@
 
 ``shoebox_irs_device`` makes the one call of the C ABI (``al_ism_shoebox``): the (C, N, ir_len) tensor of a rectangular room is
 born in HBM in the layout ``Renderer.prepare(plan, clips, irs, ir_strides)`` reads and never crosses PCIe.  ``DeviceIRTensor`` wraps
-it as a lazy array: the render path takes its buffer (``result()``), a host consumer downloads it once.  Omnidirectional point
-capsules, frequency-independent walls, no air absorption.  Without ``max_order`` the cost grows as
+it as a lazy array: the render path takes its buffer (``result()``), a host consumer downloads it once.  Point capsules,
+omnidirectional or with first-order patterns (``patterns=``: ``omni``, ``first_order``, ``cardioid``, ``foa_patterns``; the channels
+of a point share one image search, ``al_ism_shoebox_dir``), frequency-independent walls, no air absorption.  Without ``max_order`` the cost grows as
 ``ir_len**3 / (Lx * Ly * Lz)`` per (capsule, source) pair; with a ``ShoeboxTail`` the exact image sum ends a fade after the mixing
 time and the row continues as seeded Gaussian noise under an envelope that matches the image field in level and decay
 (``al_ism_shoebox_tail``, ``tail_envelope``; DESIGN.md "Shoebox IRs: the diffuse tail"), so a row of seconds costs a write of its bytes.
@@ -130,9 +131,72 @@ def tail_samples(tail: ShoeboxTail, room, sample_rate: float, c: float = SPEED_O
     return int(round(mix_time * sample_rate)), max(1, int(round(fade_time * sample_rate)))
 
 
-def tail_energy_law(room, betas, sample_rate: float, c: float = SPEED_OF_SOUND):
+MAX_CHANNELS = 4        # channels per receiver position of al_ism_shoebox_dir
+_FOA_AXES = {"w": (1.0, 0.0, 0.0, 0.0), "x": (0.0, 1.0, 0.0, 0.0), "y": (0.0, 0.0, 1.0, 0.0), "z": (0.0, 0.0, 0.0, 1.0)}
+
+
+def omni() -> np.ndarray:
+    """The pattern ``(w, vx, vy, vz) = (1, 0, 0, 0)``: a channel's amplitude is ``a (w + v . u)``, ``u`` the unit vector towards the
+    image, in room axes."""
+    return np.array([1.0, 0.0, 0.0, 0.0])
+
+
+def first_order(alpha: float, direction) -> np.ndarray:
+    """``(alpha, (1 - alpha) direction / |direction|)``: ``alpha + (1 - alpha) cos(angle to direction)``.  1: omni, 0.5: cardioid,
+    0.25: hypercardioid, 0: figure of eight."""
+    direction = np.asarray(direction, dtype=np.float64)
+    if not (isinstance(alpha, _REAL) and not isinstance(alpha, bool) and np.isfinite(alpha)):
+        raise ValueError("alpha must be a finite number")
+    if direction.shape != (3,) or not np.all(np.isfinite(direction)):
+        raise ValueError("direction must be three finite numbers")
+    norm = float(np.sqrt((direction * direction).sum()))
+    if not norm > 0.0:
+        raise ValueError("direction must not be the zero vector")
+    return np.concatenate([[float(alpha)], (1.0 - float(alpha)) * direction / norm])
+
+
+def cardioid(direction) -> np.ndarray:
+    return first_order(0.5, direction)
+
+
+def foa_patterns(order: str = "wyzx") -> np.ndarray:
+    """The four patterns (4, 4) of a first-order ambisonic listener with SN3D weights (W = 1, the dipoles of unit peak), in the
+    channel order ``order``, any permutation of the letters w, x, y, z.  ``"wyzx"`` is AmbiX (ACN order)."""
+    if not isinstance(order, str) or sorted(order.lower()) != ["w", "x", "y", "z"]:
+        raise ValueError("order must be a permutation of the letters w, x, y, z")
+    return np.array([_FOA_AXES[ch] for ch in order.lower()], dtype=np.float64)
+
+
+def _pattern(pattern) -> np.ndarray:
+    pattern = np.asarray(pattern, dtype=np.float64)
+    if pattern.shape != (4,) or not np.all(np.isfinite(pattern)):
+        raise ValueError("a pattern is four finite numbers (w, vx, vy, vz)")
+    if not np.any(pattern != 0.0):
+        raise ValueError("a pattern must not be all zero")
+    return pattern
+
+
+def check_patterns(patterns, n_positions: int) -> np.ndarray:
+    """The pattern table of ``shoebox_irs_device`` as float64 ``(n_positions, K, 4)``, ``K`` in 1 .. 4, finite, no channel all zero
+    (ValueError)."""
+    try:
+        patterns = np.ascontiguousarray(patterns, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("patterns must be an array of shape (positions, channels, 4)")
+    if patterns.ndim != 3 or patterns.shape[0] != n_positions or patterns.shape[2] != 4:
+        raise ValueError(f"patterns must have shape ({n_positions} positions, channels, 4), not {patterns.shape}")
+    if not 1 <= patterns.shape[1] <= MAX_CHANNELS:
+        raise ValueError(f"a position takes 1 to {MAX_CHANNELS} channels, not {patterns.shape[1]}")
+    if not np.all(np.isfinite(patterns)):
+        raise ValueError("patterns must be finite")
+    if np.any(np.all(patterns == 0.0, axis=2)):
+        raise ValueError("a channel's pattern must not be all zero")
+    return patterns
+
+
+def tail_energy_law(room, betas, sample_rate: float, c: float = SPEED_OF_SOUND, pattern=None):
     """``tau -> ln(sigma^2 D(tau))``, ``tau`` in seconds: the expected squared sample of the image-source field (``tail_envelope``
-    states the law and the quadrature rule)."""
+    states the law and the quadrature rule), seen through ``pattern`` (None: omni)."""
     room = _room(room)
     betas = np.ascontiguousarray(betas, dtype=np.float64)
     if betas.shape != (6,) or not np.all(np.isfinite(betas)) or np.any(betas <= 0.0) or np.any(betas > 1.0):
@@ -148,6 +212,12 @@ def tail_energy_law(room, betas, sample_rate: float, c: float = SPEED_OF_SOUND):
     s = np.sqrt(1.0 - mu * mu)
     rate = (lam[0] * np.cos(phi)[None, :] + lam[1] * np.sin(phi)[None, :]) * s[:, None] + lam[2] * mu[:, None]     # (mu, phi)
     ln_w = np.log(w_mu[:, None] * w_phi[None, :]) + np.log(2.0 / np.pi)
+    if pattern is not None:     # the direction weight of a first-order pattern, inside the log-sum (omni: ln 1 = 0, today's bits)
+        pw, vx, vy, vz = _pattern(pattern)
+        weight = (pw * pw + (vx * vx * np.cos(phi)[None, :] ** 2 + vy * vy * np.sin(phi)[None, :] ** 2) * (s * s)[:, None]
+                  + vz * vz * (mu * mu)[:, None])
+        with np.errstate(divide="ignore"):
+            ln_w = ln_w + np.log(weight)
 
     def ln_energy(tau: float) -> float:
         e = ln_w - c * float(tau) * rate
@@ -158,7 +228,7 @@ def tail_energy_law(room, betas, sample_rate: float, c: float = SPEED_OF_SOUND):
 
 
 def tail_envelope(room, betas, ir_len: int, sample_rate: float, mix: int, c: float = SPEED_OF_SOUND,
-                  rt60: Optional[float] = None) -> np.ndarray:
+                  rt60: Optional[float] = None, pattern=None) -> np.ndarray:
     """The float64 table ``ln_env`` of ``n_knots_of(ir_len)`` log-amplitude knots of the tail, knot ``k`` at sample ``256 k``: THE
     TABLE THIS RETURNS IS THE DEFINITION the kernel is held to.
 
@@ -177,8 +247,13 @@ def tail_envelope(room, betas, ir_len: int, sample_rate: float, mix: int, c: flo
 
     Model "ism" (``rt60`` None): ``ln_env[k] = 0.5 ln(sigma^2 D(256 k / fs))``.  With ``rt60 = T``:
     ``ln_env[k] = 0.5 ln(sigma^2 D(mix / fs)) - (3 ln 10 / T) (256 k - mix) / fs``: level-matched to the image field at the mixing
-    sample, then exponential at the requested rate.  A ``beta`` of 0 is a ValueError."""
-    ln_energy = tail_energy_law(room, betas, sample_rate, c)
+    sample, then exponential at the requested rate.  A ``beta`` of 0 is a ValueError.
+
+    ``pattern = (w, vx, vy, vz)`` (a channel of a directional receiver; None: omni): the image field is symmetric under a sign flip
+    of each axis, so the cross terms of ``(w + v . n)^2`` average out and the integrand carries the weight
+    ``w^2 + vx^2 s^2 cos^2 phi + vy^2 s^2 sin^2 phi + vz^2 mu^2``, inside the same rule; ``rt60`` level-matches with the weighted
+    law.  The omni pattern gives the bits of None."""
+    ln_energy = tail_energy_law(room, betas, sample_rate, c, pattern)
     if int(ir_len) != ir_len or ir_len < 1 or int(mix) != mix or mix < 0:
         raise ValueError("ir_len must be an integer >= 1 and mix an integer >= 0")
     if rt60 is not None and not (np.isfinite(rt60) and rt60 > 0.0):
@@ -190,8 +265,9 @@ def tail_envelope(room, betas, ir_len: int, sample_rate: float, mix: int, c: flo
     return 0.5 * ln_energy(int(mix) / fs) - (3.0 * np.log(10.0) / float(rt60)) * (knots - int(mix)) / fs
 
 
-def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED_OF_SOUND, max_order=None, tail=None):
-    """The host-side validation of ``shoebox_irs_device`` (ValueError); returns the arguments as the call takes them."""
+def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED_OF_SOUND, max_order=None, tail=None, patterns=None):
+    """The host-side validation of ``shoebox_irs_device`` (ValueError); returns the arguments as the call takes them (the pattern
+    table through ``check_patterns``)."""
     room = _room(room)
     betas = np.ascontiguousarray(betas, dtype=np.float64)
     if betas.shape != (6,) or not np.all(np.isfinite(betas)) or np.any(betas < 0.0) or np.any(betas > 1.0):
@@ -205,6 +281,8 @@ def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED
         raise ValueError("max_order must be None or an integer >= 0")
     if tail is not None:
         _check_tail(tail, betas)
+    if patterns is not None:
+        check_patterns(patterns, len(capsules))
     gap = np.sqrt(((capsules[:, None, :] - sources[None, :, :]) ** 2).sum(axis=2))
     if gap.min() < MIN_DISTANCE:
         raise ValueError(f"every source must be at least {MIN_DISTANCE} m from every capsule (closest: {gap.min():.4g} m)")
@@ -213,23 +291,50 @@ def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED
 
 def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sample_rate: float, c: float = SPEED_OF_SOUND,
                        max_order: Optional[int] = None, tail: Optional[ShoeboxTail] = None, source_id0: int = 0,
-                       capsule_id0: int = 0):
+                       capsule_id0: int = 0, patterns=None):
     """The IRs of ``sources`` (N, 3) at ``capsules`` (C, 3) in the room ``(Lx, Ly, Lz)`` with wall reflection coefficients
     ``betas = (x0, x1, y0, y1, z0, z1)``: ``(device buffer, (stride_c, stride_n), ir_len)`` as ``ingest.pack_ragged_irs`` returns
     it, enqueued on the renderer's stream.  The two coordinate tables are all that is uploaded.  With ``tail`` (a ``ShoeboxTail``)
     the rows carry a diffuse tail (``al_ism_shoebox_tail``; the envelope's knot table is uploaded too); row (c, n) draws its
     noise as source ``source_id0 + n`` at capsule ``capsule_id0 + c``, so a caller that splits a tensor over several calls gives
-    each part its offsets."""
+    each part its offsets.
+
+    ``patterns`` (P, K, 4), K in 1 .. 4: ``capsules`` are P receiver POSITIONS with K first-order channels each, channel k of
+    position p with the pattern ``(w, vx, vy, vz) = patterns[p, k]`` in room axes (``omni``, ``first_order``, ``cardioid``,
+    ``foa_patterns``); the tensor has the P K rows ``c = p K + k`` (``al_ism_shoebox_dir``; DESIGN.md "Shoebox IRs: directional
+    receivers"), one image search per position.  With a tail, row c draws as capsule ``capsule_id0 + c`` under the envelope of
+    its own pattern.  None: omnidirectional capsules, the call above."""
     room, betas, sources, capsules, ir_len, fs, c, order = check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c,
                                                                           max_order, tail)
+    if patterns is not None:
+        patterns = check_patterns(patterns, len(capsules))
+    n_rows = len(capsules) * (1 if patterns is None else patterns.shape[1])
     if tail is not None:
-        for name, v, count in (("source_id0", source_id0, len(sources)), ("capsule_id0", capsule_id0, len(capsules))):
+        for name, v, count in (("source_id0", source_id0, len(sources)), ("capsule_id0", capsule_id0, n_rows)):
             if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0 or int(v) + count > 1 << 32:
                 raise ValueError(f"{name} must be an integer >= 0 with {name} + count <= 2^32")
     mem, lib = renderer.mem, renderer.lib
     n, n_cap, pitch = len(sources), len(capsules), pitch_of(ir_len)
     src_dev, cap_dev = mem.upload(sources.reshape(-1)), mem.upload(capsules.reshape(-1))
-    out = mem.empty(n_cap * n * pitch)
+    out = mem.empty(n_rows * n * pitch)
+    if patterns is not None:
+        pat_dev, n_channels = mem.upload(patterns.reshape(-1)), patterns.shape[1]
+        L, B = room.ctypes.data_as(ct.POINTER(ct.c_double)), betas.ctypes.data_as(ct.POINTER(ct.c_double))
+        if tail is not None:
+            mix, fade = tail_samples(tail, room, fs, c)
+            tables = {}     # one knot table per distinct pattern, one row of the upload per channel
+            for pattern in patterns.reshape(-1, 4):
+                if pattern.tobytes() not in tables:
+                    tables[pattern.tobytes()] = tail_envelope(room, betas, ir_len, fs, mix, c, tail.rt60, pattern)
+            ln_env = np.stack([tables[pattern.tobytes()] for pattern in patterns.reshape(-1, 4)])
+            env_dev = mem.upload(ln_env.reshape(-1))
+            lib.call("al_ism_shoebox_dir_tail", mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, mem.ptr(pat_dev), n_channels, L, B, c, fs,
+                     order, ir_len, pitch, mix, fade, int(tail.seed), int(source_id0), int(capsule_id0), mem.ptr(env_dev),
+                     ln_env.shape[1], mem.ptr(out), mem.stream())
+        else:
+            lib.call("al_ism_shoebox_dir", mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, mem.ptr(pat_dev), n_channels, L, B, c, fs, order,
+                     ir_len, pitch, mem.ptr(out), mem.stream())
+        return out, (n * pitch, pitch), ir_len
     if tail is not None:
         mix, fade = tail_samples(tail, room, fs, c)
         ln_env = tail_envelope(room, betas, ir_len, fs, mix, c, tail.rt60)

@@ -633,6 +633,29 @@ int al_ism_shoebox_tail(const double *sources, int32_t n_sources, const double *
                         const double *beta, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix,
                         int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots,
                         float *out, al_stream_t stream);
+/* The same rows for FIRST-ORDER DIRECTIONAL RECEIVERS (DESIGN.md "Shoebox IRs: directional receivers").  `receivers` holds
+ * n_receivers positions, each with n_channels (1 .. 4) channels; `patterns` is a float64 DEVICE table (n_receivers, n_channels, 4) of
+ * finite (w, vx, vy, vz) in room axes (not checked: the table is never read on the host).  Row c = p * n_channels + k of the output
+ * is the image sum of al_ism_shoebox for position p with every amplitude a replaced by a (w + vx ux + vy uy + vz uz), u = R / |R| the
+ * direction the image arrives from (R: image position minus receiver); tap shape, reach, order rule and the beta = 0 rule are
+ * al_ism_shoebox's.  out[(c * n_sources + n) * pitch + t], c < n_receivers * n_channels; pads are +0.  Every sample is the float64 sum
+ * of its taps in the same fixed image order, rounded to float32 once; a row's bits depend on the room, the pair, its position's
+ * patterns and n_channels alone, not on n_receivers, n_sources, the pitch or the other positions.  The channels of a position share
+ * one image search: one launch of one workgroup per (position, source, tile of 256 samples).
+ * AL_E_BADARG: everything al_ism_shoebox refuses (workgroups counted per position); n_channels outside 1 .. 4; a null `patterns`;
+ * more than 2^31 - 1 rows. */
+int al_ism_shoebox_dir(const double *sources, int32_t n_sources, const double *receivers, int32_t n_receivers, const double *patterns,
+                       int32_t n_channels, const double *L, const double *beta, double c, double fs, int32_t max_order, int32_t ir_len,
+                       int32_t pitch, float *out, al_stream_t stream);
+/* al_ism_shoebox_dir with the diffuse tail of al_ism_shoebox_tail.  Row c draws as capsule capsule_id0 + c and reads ITS OWN knot
+ * table: ln_env is a DEVICE table (n_receivers * n_channels, n_knots), n_knots = (ir_len - 1) / 256 + 2.  With mix >= ir_len the output
+ * has the bits of al_ism_shoebox_dir.  AL_E_BADARG: everything al_ism_shoebox_dir and al_ism_shoebox_tail refuse, the id range and the
+ * tail's workgroup limit counted over the n_receivers * n_channels rows. */
+int al_ism_shoebox_dir_tail(const double *sources, int32_t n_sources, const double *receivers, int32_t n_receivers,
+                            const double *patterns, int32_t n_channels, const double *L, const double *beta, double c, double fs,
+                            int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade, uint64_t seed,
+                            int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, float *out,
+                            al_stream_t stream);
 
 /* dst[t] = src[t mod m] for t < n: np.pad(..., mode="wrap") of Augmentation.process. */
 int al_wrap_copy(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream);
