@@ -305,16 +305,36 @@ class ShoeboxIRState:
     emitters are IR columns in event order (a moving event contributes one row per trajectory point).  ``simulate()`` enqueues one
     generation per microphone; the tensors stay in HBM.
     ``tail``: a ``shoebox.ShoeboxTail`` (or its dictionary) gives every row a diffuse tail past the mixing time; channels are
-    numbered through the microphones in their order, so no two rows of the state share noise."""
+    numbered through the microphones in their order, so no two rows of the state share noise.
+    ``bands``: a ``shoebox.ShoeboxBands`` (or its dictionary) gives the walls a reflection coefficient per band (DESIGN.md "Shoebox
+    IRs: frequency-dependent walls"): ``betas`` then has shape (6, B), or ``materials`` names six walls (or one name for all) in
+    ``material_table`` (``shoebox.load_materials``), read at the band centres.  The names are kept with the betas in ``to_dict``;
+    ``from_dict`` needs no material file."""
 
     name = "SHOEBOX"
 
     def __init__(self, room, betas=None, rt60: Optional[float] = None, ir_len: int = 4096, sample_rate: int = config.SAMPLE_RATE,
-                 c: float = 343.0, max_order: Optional[int] = None, renderer=None, metadata: Optional[dict] = None, tail=None):
+                 c: float = 343.0, max_order: Optional[int] = None, renderer=None, metadata: Optional[dict] = None, tail=None,
+                 bands=None, materials=None, material_table=None):
         from . import shoebox
 
+        self.bands = shoebox.ShoeboxBands.from_dict(bands) if isinstance(bands, dict) else bands
+        self.materials = None
+        if materials is not None:
+            if betas is not None or rt60 is not None:
+                raise ValueError("give either materials, betas or rt60")
+            if material_table is None:
+                raise ValueError("materials needs a material_table (shoebox.load_materials)")
+            if self.bands is None:
+                self.bands = shoebox.ShoeboxBands()
+            if not isinstance(self.bands, shoebox.ShoeboxBands):
+                raise ValueError("bands must be a ShoeboxBands, its dictionary or None")
+            self.materials = [materials] * 6 if isinstance(materials, str) else [str(v) for v in materials]
+            betas = shoebox.material_betas(material_table, self.materials, self.bands.centres)
         if (betas is None) == (rt60 is None):
             raise ValueError("give either betas or rt60")
+        if self.bands is not None and rt60 is not None:
+            raise ValueError("rt60 gives one broadband coefficient: with bands give betas (6, B) or materials")
         self.room = shoebox._room(room)
         self.rt60 = None if rt60 is None else float(rt60)
         self.betas = shoebox.betas_from_rt60(self.room, rt60, c) if betas is None else np.array(betas, dtype=np.float64)
@@ -331,7 +351,7 @@ class ShoeboxIRState:
         # refuse bad room parameters here, not at the first simulate()
         inside = 0.5 * self.room[None, :]
         shoebox.check_arguments(self.room, self.betas, inside, inside + 0.25 * self.room[None, :], self.ir_len, self.sample_rate,
-                                self.c, self.max_order, self.tail)
+                                self.c, self.max_order, self.tail, None, self.bands)
 
     def add_microphone(self, alias: str, capsule_positions, patterns=None, capsule_names=None) -> MicArray:
         """``capsule_positions`` (C, 3).  ``patterns`` (C, 4): one first-order pattern ``(w, vx, vy, vz)`` per capsule in room axes
@@ -368,6 +388,8 @@ class ShoeboxIRState:
         n_channels = len(positions)
         if patterns is not None:
             patterns = shoebox.check_patterns(patterns, len(positions))
+            if self.bands is not None:
+                raise ValueError("bands together with patterns are not yet supported (K x B gains per image)")
             n_channels = len(positions) * patterns.shape[1]
             md["patterns"] = patterns.reshape(-1, 4).tolist()      # one row per channel, c = p K + k
         if capsule_names is not None:
@@ -413,7 +435,8 @@ class ShoeboxIRState:
         capsule_id0 = 0     # the tail's noise: channels are numbered through the microphones, emitters are one table already
         for alias, capsules in self._capsules.items():
             buf, strides, _ = shoebox.shoebox_irs_device(r, self.room, self.betas, sources, capsules, self.ir_len, self.sample_rate,
-                                                         self.c, self.max_order, self.tail, 0, capsule_id0, self._patterns[alias])
+                                                         self.c, self.max_order, self.tail, 0, capsule_id0, self._patterns[alias],
+                                                         self.bands)
             n_channels = self.microphones[alias].n_capsules
             irs[alias] = shoebox.DeviceIRTensor(r, buf, strides, (n_channels, len(sources), self.ir_len))
             capsule_id0 += n_channels
@@ -436,6 +459,10 @@ class ShoeboxIRState:
                               max_order=self.max_order))
         if self.tail is not None:
             d["shoebox"]["tail"] = self.tail.to_dict()
+        if self.bands is not None:      # betas is (6, B) then; the material names are a record, the betas are what is read back
+            d["shoebox"]["bands"] = self.bands.to_dict()
+            if self.materials is not None:
+                d["shoebox"]["materials"] = list(self.materials)
         d.update({k: v for k, v in self.metadata.items() if k not in d})
         return d
 
@@ -454,8 +481,10 @@ class ShoeboxIRState:
         box = state_d["shoebox"]
         keep = {k: v for k, v in state_d.items() if k not in ("backend", "sample_rate", "emitters", "microphones", "shoebox")}
         state = cls(box["room"], betas=box["betas"], ir_len=box["ir_len"], sample_rate=state_d.get("sample_rate") or config.SAMPLE_RATE,
-                    c=box.get("c", 343.0), max_order=box.get("max_order"), renderer=renderer, metadata=keep, tail=box.get("tail"))
+                    c=box.get("c", 343.0), max_order=box.get("max_order"), renderer=renderer, metadata=keep, tail=box.get("tail"),
+                    bands=box.get("bands"))
         state.rt60 = box.get("rt60")
+        state.materials = None if box.get("materials") is None else [str(v) for v in box["materials"]]
         for alias, md in state_d["microphones"].items():
             positions = shoebox._points(md["coordinates_absolute"], state.room, f"capsules of {alias}")
             patterns = md.get("patterns")      # one row per channel; several channels share a coordinate row (an FOA listener)

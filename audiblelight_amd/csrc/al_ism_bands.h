@@ -1,0 +1,579 @@
+// Shoebox room impulse responses with FREQUENCY-DEPENDENT WALLS in B <= 8 bands (al_ism_shoebox_bands; DESIGN.md "Shoebox IRs:
+// frequency-dependent walls").  Every band b has its own column beta[:, b] of six reflection coefficients and its own zero-phase
+// FIR phi_b of 2 half + 1 taps (shoebox.band_filters; sum_b phi_b = delta).  With y_b the image sum of al_ism.h under beta[:, b],
+// evaluated at every integer s in [-half, y_end + half) (negative s included: the row boundary does not truncate a band sum),
+//   y(t) = sum_b sum_{j = -half .. half} phi_b[j] y_b[t - j],   float64, b ascending, then j ascending,
+// rounded to float32 once.  Two kernels share a row through a caller-provided float64 workspace [pair in pass][B][W],
+// W = y_end + 2 half rounded up to ISM_TILE, whose index w holds sample s = w - half:
+//   k_ism_bands<NB>  the gather of k_ism_shoebox_dir over the shifted axis: one workgroup of ONE WAVE per (pair, tile of W), the same
+//     lattice walk, the same canonical order (qx, qy, qz), the same shell.  A list entry carries NB <= 4 BAND GAINS
+//     exp(sum k ln beta_b) in place of the pattern gains (logarithms taken on the host; a wall of beta_b == 0 in the path makes gain b
+//     exactly 0, which adds +-0 to that band's sum: the bits of leaving the image out; an image dead in every band of the group is
+//     left out of the list), a lane forms the tap's shape once per (image, sample) and adds it into NB float64 accumulators.  B > 4
+//     takes ceil(B / 4) launches over groups of bands: each band's sum keeps the canonical order, so grouping cannot change bits.
+//     Every word of the workspace rows of the pass is written (zeros where no image reaches), none is read.
+//   k_ism_band_combine  one workgroup of ONE WAVE per (pair, output tile of ISM_TILE samples), as every kernel of al_ism.h.  Band
+//     rows and phi_b go through LDS one band at a time, ISM_BAND_CHUNK taps at a time (2 ISM_BAND_CHUNK - 1 row samples serve a
+//     chunk: 6 KB of LDS whatever `half` is); a lane keeps ONE float64 accumulator for each of its ISM_PER_LANE outputs
+//     (t_lo + lane + 64 s) and adds the products in the stated order; one float32 store per sample, pads +0.  With one wave no
+//     wave can be out of step with another: the __syncthreads() order LDS traffic only and there is no barrier instruction.
+// THE DIFFUSE TAIL WITH BANDS (al_ism_shoebox_bands_tail).  ln_env is a table (B, n_knots): band b decays under its own knots.  With
+// g(s) the row's draws of al_ism.h (zero outside [0, ir_len)), psi_k[j] = sum_b exp(ln_env[b][k]) phi_b[j], k = t / 256, p = (t % 256) / 256,
+//   n(t) = (1 - p) sum_j psi_k[j] g(t - j) + p sum_j psi_{k+1}[j] g(t - j)      (p == 0 reads knot k alone),
+//   h = float32(w_e y(t) + w_l n(t)) with the fade weights of al_ism.h; where w_l == 0 no noise term is formed.
+// The band sums end at y_end = min(ir_len, M + F) and a row is shared as in al_ism.h:
+//   k_ism_band_combine<true>  the tiles below SPLIT.  A tile with a sample past M stages the draws beside the band rows and runs a
+//     second FIR per band over them, n(t) = sum_b ((1 - p) e_b[k] + p e_b[k + 1]) sum_j phi_b[j] g(t - j): the same number with the
+//     two sums exchanged (the bound carries the difference), so no psi is formed for at most F + 256 samples of a row.
+//   k_ism_band_tail<HCAP>  every sample at or past SPLIT, pad included.  One workgroup of ONE WAVE takes ISM_BT_SPAN = 1024 samples
+//     of a row, four knot intervals one after the other.  It holds in LDS the draws of its span +- half as float32 and
+//     (psi_k, psi_{k+1}) of the interval at hand, interleaved in pairs of 16 bytes and formed in-kernel from the knot tables and phi (b
+//     ascending; a knot of -inf gives e_b = 0); from one interval to the next psi_{k+1} becomes psi_k and one psi is formed.  A lane
+//     owns FOUR consecutive outputs: per tap it reads one pair of psi (a broadcast) and ONE new draw, the other three slide
+//     through registers, and does eight float64 multiply-adds into eight accumulators; one 16-byte store per lane and interval.
+//     Accumulation is float64: the draws are float32 values and psi spans the decay of a whole row, so float32 sums would put
+//     about 1025 * 2^-24 of sum |psi| |g| into every sample, and the FIR is bound by multiply-add issue either way.  HCAP (256,
+//     512, 1024: the smallest that holds `half`) sizes the LDS arrays; ISM_BAND_TAIL_MAX_HALF = 1024 is the cap with a tail.
+// The entry walks the pairs in PASSES of workspace_bytes / bytes_per_pair pairs, gather then combine, in order on the one stream: the
+// workspace is reused in stream order, nothing is allocated and nothing synchronises.  A row's bits do not depend on the pass it is
+// generated in: both kernels index the workspace by the pair's place in its pass only to find their own rows.
+#pragma once
+#include "al_ism.h"
+
+namespace al {
+
+constexpr int ISM_MAX_BANDS = 8;
+constexpr int ISM_BAND_GROUP = 4;        // bands per launch of k_ism_bands (the accumulators of k_ism_shoebox_dir<4>)
+constexpr int ISM_BAND_MAX_HALF = 4096;  // the cap on `half`: 8193 taps per band
+constexpr int ISM_BAND_CHUNK = 256;      // taps staged per step of k_ism_band_combine
+constexpr int ISM_BAND_TAIL_MAX_HALF = 1024;   // the cap on `half` with a tail (the LDS of k_ism_band_tail)
+constexpr int ISM_BT_PER_LANE = 4;             // consecutive outputs per lane of k_ism_band_tail: one knot interval per wave
+constexpr int ISM_BT_INTERVALS = 4;            // knot intervals per workgroup
+constexpr int ISM_BT_SPAN = ISM_BT_INTERVALS * ISM_TILE;
+static_assert(ISM_THREADS * ISM_BT_PER_LANE == ISM_TILE, "k_ism_band_tail: a wave covers one knot interval");
+static_assert(ISM_BAND_CHUNK == ISM_TILE, "k_ism_band_combine: the staged row segment spans a tile of outputs and a chunk of taps");
+
+struct IsmBandJob {
+  IsmJob base;                       // ln_beta / beta_zero unused: the per-band tables below
+  double ln_beta[ISM_MAX_BANDS][6];  // 0 where beta == 0
+  int32_t beta_zero[ISM_MAX_BANDS][6];
+  const double *filters;             // (n_bands, 2 half + 1), device
+  double *workspace;                 // [pair in pass][n_bands][W], device
+  int32_t n_bands, half, y_end;      // y_end: the image sum is formed below it (ir_len, or min(ir_len, M + F) with a tail)
+  int32_t band_tail_blocks;          // workgroups of k_ism_band_tail per row
+  int32_t W, n_ws_tiles;             // W = n_ws_tiles * ISM_TILE
+  int32_t n_out_tiles;               // ceil(pitch / ISM_TILE)
+  int32_t band0;                     // first band of this launch of k_ism_bands
+  int64_t pair0;                     // first pair of the pass
+  int64_t pairs_per_pass;
+};
+
+struct alignas(16) IsmPsi {
+  double x, y;   // psi_k[j], psi_{k+1}[j]: one 16-byte LDS read per tap
+};
+
+// reflections of image q of an axis by its wall at 0 and its wall at L
+__device__ __forceinline__ void ism_counts(int q, int &k0, int &k1) {
+  int m, p;
+  ism_mp(q, m, p);
+  k0 = abs(m - p);
+  k1 = abs(m);
+}
+// the bands of [band0, band0 + NB) in which image q of axis `axis` is alive (no wall of beta == 0 hit), as a bit mask
+template <int NB>
+__device__ __forceinline__ unsigned ism_band_alive(const IsmBandJob &bj, int axis, int q) {
+  int k0, k1;
+  ism_counts(q, k0, k1);
+  unsigned alive = 0;
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    const int32_t *zero = bj.beta_zero[bj.band0 + k] + 2 * axis;
+    if (!((k0 > 0 && zero[0]) || (k1 > 0 && zero[1]))) alive |= 1u << k;
+  }
+  return alive;
+}
+
+template <int NB>
+__global__ __launch_bounds__(ISM_THREADS) void k_ism_bands(IsmBandJob bj) {
+  __shared__ IsmDirEntry<NB> list[ISM_DIR_LIST];
+  __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];   // cos, sin(2 pi j / 81), j = -40 .. 40
+  __shared__ int wave_total[2];
+  const IsmJob &job = bj.base;
+  const int tid = threadIdx.x, lane = tid;
+  const int tile = (int)(blockIdx.x % (unsigned)bj.n_ws_tiles);
+  const int64_t local = blockIdx.x / (unsigned)bj.n_ws_tiles, pair = bj.pair0 + local;   // c * N + n
+  const int n = (int)(pair % job.n_sources), cap = (int)(pair / job.n_sources);
+  // the tile in workspace words w and in samples s = w - half
+  const int w_lo = tile * ISM_TILE, w = w_lo + tid;
+  const int s_lo = w_lo - bj.half, t = s_lo + tid;
+  const int s_end = bj.y_end + bj.half;                // the band sums are formed for s < s_end
+  const int t_hi = min(s_lo + ISM_TILE, s_end) - 1;
+  double *rows = bj.workspace + (local * bj.n_bands + bj.band0) * (int64_t)bj.W;   // band band0 of the pair; band k is k * W on
+  if (t_hi < s_lo || t_hi < -ISM_HALF) {   // a tile past s_end, or so far below sample 0 that no tap reaches it (tau > 0)
+    for (int k = 0; k < NB; ++k)
+      for (int s = 0; s < ISM_PER_LANE; ++s) rows[(int64_t)k * bj.W + w + s * ISM_THREADS] = 0.0;
+    return;
+  }
+  for (int i = tid; i < ISM_TAPS; i += ISM_THREADS) sincospi(2.0 * (double)(i - ISM_HALF) / (double)ISM_TAPS, &win_s[i], &win_c[i]);
+
+  const double sx = job.sources[3 * n], sy = job.sources[3 * n + 1], sz = job.sources[3 * n + 2];
+  const double rx = job.capsules[3 * cap], ry = job.capsules[3 * cap + 1], rz = job.capsules[3 * cap + 2];
+  const double Lx = job.L[0], Ly = job.L[1], Lz = job.L[2];
+  // the shell of this tile, a sample wider than the taps reach on either side
+  const double d_hi = (double)(t_hi + ISM_HALF + 2) * job.c / job.fs, d_lo = (double)(s_lo - ISM_HALF - 2) * job.c / job.fs;
+  const double hi2 = d_hi * d_hi, lo2 = d_lo > 0.0 ? d_lo * d_lo : 0.0;
+  const int order = job.max_order;
+  int Qx = ism_clamp(floor(d_hi / Lx) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH), Qy = ism_clamp(floor(d_hi / Ly) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH),
+      Qz = ism_clamp(floor(d_hi / Lz) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH);
+  if (order >= 0) {
+    Qx = min(Qx, order);
+    Qy = min(Qy, order);
+    Qz = min(Qz, order);
+  }
+  const int64_t ny = 2 * (int64_t)Qy + 1, n_columns = (2 * (int64_t)Qx + 1) * ny;
+
+  // does image qz of column `col` touch the tile?  t0, tau and d of the image either way
+  auto touches = [&](const IsmColumn &col, int qz, double &d, double &tau, int &t0) {
+    const double Rz = ism_offset(qz, sz, rz, Lz);
+    d = sqrt(col.rho2 + Rz * Rz);
+    tau = d * job.fs / job.c;
+    if (!(tau < 2.0e9) || !(d > 0.0)) return false;
+    t0 = (int)rint(tau);
+    return t0 + ISM_HALF >= s_lo && t0 - ISM_HALF <= t_hi;
+  };
+
+  double acc[ISM_PER_LANE][NB] = {};
+  int parity = 0;
+  for (int64_t base = 0; base < n_columns; base += ISM_THREADS, parity ^= 1) {
+    // 1. this lane's column
+    const int64_t ci = base + tid;
+    IsmColumn col;
+    col.a1 = col.a2 = 0;
+    col.b1 = col.b2 = -1;
+    unsigned alive_xy = 0;   // the bands of the group in which the column is alive
+    if (ci < n_columns) {
+      const int qx = (int)(ci / ny) - Qx, qy = (int)(ci % ny) - Qy;
+      const int k_xy = abs(qx) + abs(qy);
+      const double Rx = ism_offset(qx, sx, rx, Lx), Ry = ism_offset(qy, sy, ry, Ly);
+      col.rho2 = Rx * Rx + Ry * Ry;
+      if ((order < 0 || k_xy <= order) && col.rho2 < hi2) {
+        alive_xy = ism_band_alive<NB>(bj, 0, qx) & ism_band_alive<NB>(bj, 1, qy);
+        const int Kz = order < 0 ? Qz : min(Qz, order - k_xy);
+        const double z_max = sqrt(hi2 - col.rho2);
+        // image qz lies in (qz Lz, (qz + 1) Lz): one cell of margin on either side
+        col.a1 = ism_clamp(floor((rz - z_max) / Lz) - 1.0, -Kz, Kz);
+        const int top = ism_clamp(floor((rz + z_max) / Lz) + 1.0, -Kz, Kz);
+        col.b1 = top;   // one run, unless the inner sphere cuts it in two
+        if (lo2 > col.rho2) {   // the cells wholly inside the inner sphere are left out
+          const double z_min = sqrt(lo2 - col.rho2);
+          const double ea = ceil((rz - z_min) / Lz) + 1.0, eb = floor((rz + z_min) / Lz) - 2.0;
+          if (ea <= eb) {
+            col.b1 = ism_clamp(ea - 1.0, -Kz - 1, Kz);
+            col.a2 = ism_clamp(eb + 1.0, -Kz, Kz + 1);
+            col.b2 = top;
+          }
+        }
+      }
+    }
+    int count = 0;
+    if (alive_xy) {
+      double d, tau;
+      int t0;
+      for (int run = 0; run < 2; ++run)
+        for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz)
+          if ((alive_xy & ism_band_alive<NB>(bj, 2, qz)) && touches(col, qz, d, tau, t0)) ++count;
+    }
+    // 2. exclusive prefix sum of the counts: suffix sums by shuffles, the total (lane 0's) through LDS
+    int suffix = count;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int other = __shfl_down(suffix, off, 64);
+      if (lane + off < 64) suffix += other;
+    }
+    if (lane == 0) wave_total[parity] = suffix;
+    __syncthreads();
+    const int total = wave_total[parity], offset = total - suffix;
+    // 3. + 4. the list, a window of ISM_DIR_LIST at a time
+    for (int w0 = 0; w0 < total; w0 += ISM_DIR_LIST) {
+      if (count > 0 && offset < w0 + ISM_DIR_LIST && offset + count > w0) {
+        int kx0, kx1, ky0, ky1;
+        ism_counts((int)(ci / ny) - Qx, kx0, kx1);
+        ism_counts((int)(ci % ny) - Qy, ky0, ky1);
+        int at = offset;
+        for (int run = 0; run < 2; ++run)
+          for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz) {
+            const unsigned alive = alive_xy & ism_band_alive<NB>(bj, 2, qz);
+            double d, tau;
+            int t0;
+            if (!alive || !touches(col, qz, d, tau, t0)) continue;
+            if (at >= w0 && at < w0 + ISM_DIR_LIST) {
+              IsmDirEntry<NB> &e = list[at - w0];
+              int kz0, kz1;
+              ism_counts(qz, kz0, kz1);
+#pragma unroll
+              for (int k = 0; k < NB; ++k) {   // prod beta_b^k, the logarithms summed as al_ism.h sums them: (x + y) + z
+                const double *lb = bj.ln_beta[bj.band0 + k];
+                const double ln_xy = ((double)kx0 * lb[0] + (double)kx1 * lb[1]) + ((double)ky0 * lb[2] + (double)ky1 * lb[3]);
+                const double ln_z = (double)kz0 * lb[4] + (double)kz1 * lb[5];
+                e.gain[k] = ((alive >> k) & 1u) ? exp(ln_xy + ln_z) : 0.0;
+              }
+              double sp, cp, s81, c81;
+              const double f = tau - (double)t0, a = 1.0 / (4.0 * M_PI * d);   // a, g of the image between rigid walls
+              sincospi(f, &sp, &cp);
+              sincospi(2.0 * f / (double)ISM_TAPS, &s81, &c81);
+              e.t0 = t0;
+              e.reserved = 0;
+              e.f = f;
+              e.a = a;
+              e.g = -0.5 * a * sp / M_PI;
+              e.s81 = s81;
+              e.c81 = c81;
+            }
+            ++at;
+          }
+      }
+      __syncthreads();
+      const int n_list = min(ISM_DIR_LIST, total - w0);
+      for (int i = 0; i < n_list; ++i) {
+        const int j0 = t - list[i].t0;   // of the lane's first sample; the others are 64 apart, so at most two are in reach
+        if (j0 > ISM_HALF || j0 + (ISM_PER_LANE - 1) * ISM_THREADS < -ISM_HALF) continue;
+        const IsmDirEntry<NB> e = list[i];
+#pragma unroll
+        for (int s = 0; s < ISM_PER_LANE; ++s) {
+          const int j = j0 + s * ISM_THREADS;
+          if (j < -ISM_HALF || j > ISM_HALF || t + s * ISM_THREADS >= s_end) continue;
+          const double u = (double)j - e.f;
+          if (!(fabs(u) < 0.5 * (double)ISM_TAPS)) continue;
+          if (u == 0.0) {
+#pragma unroll
+            for (int k = 0; k < NB; ++k) acc[s][k] += e.a * e.gain[k];
+          } else {   // the tap between rigid walls, once for the NB bands
+            const double window = 1.0 + (win_c[j + ISM_HALF] * e.c81 + win_s[j + ISM_HALF] * e.s81);
+            const double shape = ((j & 1) ? -e.g : e.g) * window / u;
+#pragma unroll
+            for (int k = 0; k < NB; ++k) acc[s][k] += shape * e.gain[k];
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < ISM_PER_LANE; ++s)   // w + s * ISM_THREADS < W: the tile lies inside the row
+#pragma unroll
+    for (int k = 0; k < NB; ++k) rows[(int64_t)k * bj.W + w + s * ISM_THREADS] = acc[s][k];
+}
+
+// draw s of row (cap, n); zero outside [0, ir_len)
+__device__ __forceinline__ float ism_band_draw(const IsmJob &job, int s, int n, int cap) {
+  if (s < 0 || s >= job.ir_len) return 0.f;
+  const float4 g4 = ism_tail_normal4(job.tail, s >> 2, n, cap);
+  return (s & 2) ? ((s & 1) ? g4.w : g4.z) : ((s & 1) ? g4.y : g4.x);
+}
+
+// out[t] = float32(sum_b sum_j phi_b[j] y_b[t - j]); grid: n_out_tiles workgroups of ONE WAVE per pair of the pass, a lane owning
+// outputs t_lo + lane + 64 s, s < ISM_PER_LANE (so the lanes of a wave read consecutive LDS words), each with an accumulator of its
+// own.  TAIL: the fade and the noise term for the samples past M (the tiles below the split).  (One wave: the __syncthreads() below
+// order LDS traffic only, hipcc emits no barrier instruction for them.)
+template <bool TAIL>
+__global__ __launch_bounds__(ISM_THREADS) void k_ism_band_combine(IsmBandJob bj) {
+  __shared__ double seg[2 * ISM_BAND_CHUNK], tap[ISM_BAND_CHUNK];
+  __shared__ float gseg[TAIL ? 2 * ISM_BAND_CHUNK : 1];
+  const IsmJob &job = bj.base;
+  const int tid = threadIdx.x;
+  const int tile = (int)(blockIdx.x % (unsigned)bj.n_out_tiles);
+  const int64_t local = blockIdx.x / (unsigned)bj.n_out_tiles, pair = bj.pair0 + local;
+  const int n = (int)(pair % job.n_sources), cap = (int)(pair / job.n_sources);
+  const int t_lo = tile * ISM_TILE, t = t_lo + tid;   // the lane's first output
+  float *row = job.out + pair * (int64_t)job.pitch;
+  if (t_lo >= job.ir_len) {   // a tile of pad samples only
+    for (int s = 0; s < ISM_PER_LANE; ++s)
+      if (t + s * ISM_THREADS < job.pitch) row[t + s * ISM_THREADS] = 0.f;
+    return;
+  }
+  // does a sample of this tile carry noise?  (uniform over the workgroup)
+  const bool noisy = TAIL && (int64_t)t_lo + ISM_TILE - 1 > job.tail.mix;
+  const int n_taps = 2 * bj.half + 1;
+  double acc[ISM_PER_LANE] = {}, noise[ISM_PER_LANE] = {};
+  for (int b = 0; b < bj.n_bands; ++b) {
+    const double *y = bj.workspace + (local * bj.n_bands + b) * (int64_t)bj.W;
+    const double *phi = bj.filters + (int64_t)b * n_taps;
+    double acc_g[ISM_PER_LANE] = {};   // sum_j phi_b[j] g(t - j)
+    for (int c0 = 0; c0 < n_taps; c0 += ISM_BAND_CHUNK) {
+      // taps j = -half + c0 + i, i < ISM_BAND_CHUNK: output t_lo + o reads word t - j + half = first + (ISM_BAND_CHUNK - 1) + o - i
+      const int first = t_lo + 2 * bj.half - c0 - (ISM_BAND_CHUNK - 1);
+      __syncthreads();   // the reads of the chunk before are over
+      for (int k = tid; k < 2 * ISM_BAND_CHUNK - 1; k += ISM_THREADS) {
+        const int idx = first + k;   // below 0 only under taps past the last one, at or past W only under outputs past y_end
+        seg[k] = idx >= 0 && idx < bj.W ? y[idx] : 0.0;
+        if constexpr (TAIL)
+          if (noisy) gseg[k] = ism_band_draw(job, idx - bj.half, n, cap);   // word idx holds sample idx - half
+      }
+      for (int k = tid; k < ISM_BAND_CHUNK; k += ISM_THREADS) tap[k] = c0 + k < n_taps ? phi[c0 + k] : 0.0;
+      __syncthreads();
+      const int m = min(ISM_BAND_CHUNK, n_taps - c0);
+      const double *mine = seg + (ISM_BAND_CHUNK - 1) + tid;
+      for (int i = 0; i < m; ++i) {
+        const double w = tap[i];
+#pragma unroll
+        for (int s = 0; s < ISM_PER_LANE; ++s) acc[s] += w * mine[s * ISM_THREADS - i];
+      }
+      if constexpr (TAIL) {
+        if (noisy) {
+          const float *mine_g = gseg + (ISM_BAND_CHUNK - 1) + tid;
+          for (int i = 0; i < m; ++i) {
+            const double w = tap[i];
+#pragma unroll
+            for (int s = 0; s < ISM_PER_LANE; ++s) acc_g[s] += w * (double)mine_g[s * ISM_THREADS - i];
+          }
+        }
+      }
+    }
+    if constexpr (TAIL) {
+      if (noisy) {
+        const double *ln_env = job.tail.ln_env + (int64_t)b * job.tail.env_stride;
+#pragma unroll
+        for (int s = 0; s < ISM_PER_LANE; ++s) {
+          const int ts = t + s * ISM_THREADS;
+          if (ts > job.tail.mix && ts < job.ir_len) {   // the band's envelope at ts, interpolated in amplitude
+            const int k = ts / ISM_TILE, r = ts % ISM_TILE;
+            const double p = (double)r / (double)ISM_TILE;
+            const double e = r == 0 ? exp(ln_env[k]) : (1.0 - p) * exp(ln_env[k]) + p * exp(ln_env[k + 1]);
+            noise[s] += e * acc_g[s];
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < ISM_PER_LANE; ++s) {
+    const int ts = t + s * ISM_THREADS;
+    if (ts >= job.pitch) continue;
+    double v = acc[s];
+    if constexpr (TAIL) {
+      if (ts > job.tail.mix && ts < job.ir_len) {   // at or below M: w_e = 1, w_l = 0, the image part as it is
+        const double x = ((double)ts - (double)job.tail.mix) / (double)job.tail.fade;
+        if (x < 1.0) {
+          double w_e, w_l;
+          sincospi(0.5 * x, &w_l, &w_e);
+          v = w_e * acc[s] + w_l * noise[s];
+        } else {
+          v = noise[s];
+        }
+      }
+    }
+    row[ts] = ts < job.ir_len ? (float)v : 0.f;
+  }
+}
+
+// the samples [split, pitch) of every row: the draws through psi_k, psi_{k+1}; grid: band_tail_blocks workgroups of one wave per pair
+template <int HCAP>
+__global__ __launch_bounds__(ISM_THREADS) void k_ism_band_tail(IsmBandJob bj) {
+  __shared__ IsmPsi psi[2 * HCAP + 1];             // (psi_k[j], psi_{k+1}[j]) at j + half
+  __shared__ float g[ISM_BT_SPAN + 2 * HCAP];      // draw span_lo - half + i at i
+  const IsmJob &job = bj.base;
+  const int lane = threadIdx.x;
+  const int block = (int)(blockIdx.x % (unsigned)bj.band_tail_blocks);
+  const int64_t pair = blockIdx.x / (unsigned)bj.band_tail_blocks;   // every pair in one launch: no workspace is touched
+  const int n = (int)(pair % job.n_sources), cap = (int)(pair / job.n_sources);
+  float *row = job.out + pair * (int64_t)job.pitch;
+  const int half = bj.half, n_taps = 2 * half + 1;
+  const int64_t span_lo = (int64_t)job.tail.split + (int64_t)block * ISM_BT_SPAN;   // < pitch <= 2^31 - 1
+  // the draws of the span +- half, a Philox block of four at a time (span_lo - half may not be a multiple of 4: block by block)
+  const int g_len = ISM_BT_SPAN + 2 * half, s_first = (int)span_lo - half;
+  const int q_first = s_first >> 2;   // arithmetic shift: floor for negative samples too
+  for (int q = q_first + lane; 4 * q < s_first + g_len; q += ISM_THREADS) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (q >= 0 && 4 * (int64_t)q < job.ir_len) v = ism_tail_normal4(job.tail, q, n, cap);
+    const float vs[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int s = 4 * q + i, at = s - s_first;
+      if (at >= 0 && at < g_len) g[at] = s >= 0 && s < job.ir_len ? vs[i] : 0.f;
+    }
+  }
+  // psi of one knot into half `which` of the double2 table
+  auto form = [&](int knot, int which) {
+    double e[ISM_MAX_BANDS];   // unrolled to the full count: registers, no indexed array
+#pragma unroll
+    for (int b = 0; b < ISM_MAX_BANDS; ++b) e[b] = b < bj.n_bands ? exp(job.tail.ln_env[(int64_t)b * job.tail.env_stride + knot]) : 0.0;
+    for (int m = lane; m < n_taps; m += ISM_THREADS) {
+      double v = 0.0;
+#pragma unroll
+      for (int b = 0; b < ISM_MAX_BANDS; ++b)
+        if (b < bj.n_bands) v += e[b] * bj.filters[(int64_t)b * n_taps + m];
+      if (which) psi[m].y = v; else psi[m].x = v;
+    }
+  };
+  for (int iv = 0; iv < ISM_BT_INTERVALS; ++iv) {
+    const int64_t t_base64 = span_lo + (int64_t)iv * ISM_TILE;
+    if (t_base64 >= job.pitch) break;   // uniform over the wave
+    const int t_base = (int)t_base64, t0 = t_base + ISM_BT_PER_LANE * lane;
+    if (t_base >= job.ir_len) {   // pad samples only
+      if (t0 < job.pitch) *reinterpret_cast<float4 *>(row + t0) = make_float4(0.f, 0.f, 0.f, 0.f);
+      continue;
+    }
+    const int knot = t_base / ISM_TILE;   // knot + 1 <= (ir_len - 1) / 256 + 1: inside the table
+    __syncthreads();   // one wave: orders the LDS traffic (the draws, the table's readers of the interval before)
+    if (iv == 0) {
+      form(knot, 0);
+    } else {
+      for (int m = lane; m < n_taps; m += ISM_THREADS) psi[m].x = psi[m].y;   // psi_{k+1} of the interval before is this one's psi_k
+    }
+    form(knot + 1, 1);
+    __syncthreads();
+    // output t0 + q reads draw t0 + q - j at g[at + q - m], m = j + half
+    const int at = t0 - (int)span_lo + 2 * half;
+    double a[ISM_BT_PER_LANE] = {}, c[ISM_BT_PER_LANE] = {};
+    // the window slides as float64: one conversion per tap, of the draw that enters
+    double d0 = (double)g[at], d1 = (double)g[at + 1], d2 = (double)g[at + 2], d3 = (double)g[at + 3];
+#pragma unroll 4
+    for (int m = 0; m < n_taps; ++m) {
+      const IsmPsi ps = psi[m];
+      a[0] += ps.x * d0, a[1] += ps.x * d1, a[2] += ps.x * d2, a[3] += ps.x * d3;
+      c[0] += ps.y * d0, c[1] += ps.y * d1, c[2] += ps.y * d2, c[3] += ps.y * d3;
+      d3 = d2, d2 = d1, d1 = d0;
+      d0 = (double)g[max(at - m - 1, 0)];   // at - m - 1 >= 0 but behind the last tap, whose draw is not used
+    }
+    if (t0 < job.pitch) {   // pitch is a multiple of 4: a quad is inside the row or outside it
+      float vs[ISM_BT_PER_LANE];
+#pragma unroll
+      for (int q = 0; q < ISM_BT_PER_LANE; ++q) {
+        const int r = ISM_BT_PER_LANE * lane + q;
+        const double p = (double)r / (double)ISM_TILE;
+        const double v = r == 0 ? a[q] : (1.0 - p) * a[q] + p * c[q];
+        vs[q] = t0 + q < job.ir_len ? (float)v : 0.f;
+      }
+      *reinterpret_cast<float4 *>(row + t0) = make_float4(vs[0], vs[1], vs[2], vs[3]);
+    }
+  }
+}
+
+// W of a row: y_end + 2 half rounded up to the tile
+inline int64_t ism_bands_width(int64_t y_end, int64_t half) { return (y_end + 2 * half + ISM_TILE - 1) / ISM_TILE * ISM_TILE; }
+
+// al_ism_shoebox_bands_workspace_bytes: bytes per pair, or AL_E_BADARG.  mix < 0: no tail (y_end = ir_len)
+inline int64_t ism_bands_workspace_bytes(int32_t n_bands, int32_t half, int32_t ir_len, int64_t mix, int64_t fade) {
+  if (n_bands < 1 || n_bands > ISM_MAX_BANDS) return fail(AL_E_BADARG, "al_ism_shoebox_bands: n_bands must be in 1 .. 8");
+  if (half < 1 || half > ISM_BAND_MAX_HALF) return fail(AL_E_BADARG, "al_ism_shoebox_bands: half must be in 1 .. 4096");
+  if (ir_len < 1) return fail(AL_E_BADARG, "al_ism_shoebox_bands: ir_len must be >= 1");
+  if (mix >= 0 && fade < 1) return fail(AL_E_BADARG, "al_ism_shoebox_bands: fade must be >= 1");
+  int64_t y_end = ir_len;
+  if (mix >= 0 && mix < ir_len && fade < ir_len && mix + fade < ir_len) y_end = mix + fade;
+  return (int64_t)n_bands * ism_bands_width(y_end, half) * (int64_t)sizeof(double);
+}
+
+// al_ism_shoebox_bands's arguments as the kernels' job: 0 with *bj filled, or the error of the first bad argument
+inline int ism_bands_prepare(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
+                             const double *beta, int32_t n_bands, const double *filters, int32_t half, double c, double fs,
+                             int32_t max_order, int32_t ir_len, int32_t pitch, void *workspace, int64_t workspace_bytes, float *out,
+                             IsmBandJob *bj, bool with_tail = false) {
+  if (n_bands < 1 || n_bands > ISM_MAX_BANDS) return fail(AL_E_BADARG, "al_ism_shoebox_bands: n_bands must be in 1 .. 8");
+  if (half < 1 || half > ISM_BAND_MAX_HALF) return fail(AL_E_BADARG, "al_ism_shoebox_bands: half must be in 1 .. 4096");
+  if (!beta) return fail(AL_E_BADARG, "al_ism_shoebox: null pointer");
+  if (!filters) return fail(AL_E_BADARG, "al_ism_shoebox_bands: null filter table");
+  double column[6];
+  for (int b = 0; b < n_bands; ++b) {   // ism_prepare refuses what al_ism_shoebox refuses, band by band
+    for (int i = 0; i < 6; ++i) column[i] = beta[i * n_bands + b];
+    if (int rc = ism_prepare(sources, n_sources, capsules, n_capsules, L, column, c, fs, max_order, ir_len, pitch, out, &bj->base)) return rc;
+    for (int i = 0; i < 6; ++i) {
+      bj->ln_beta[b][i] = bj->base.ln_beta[i];
+      bj->beta_zero[b][i] = bj->base.beta_zero[i];
+    }
+  }
+  for (int b = n_bands; b < ISM_MAX_BANDS; ++b)
+    for (int i = 0; i < 6; ++i) bj->ln_beta[b][i] = 0.0, bj->beta_zero[b][i] = 0;
+  for (int i = 0; i < 3; ++i)   // the band sums reach `half` past the row
+    if (!(c * ((double)ir_len + (double)half + 42.0) / fs / L[i] + 2.0 <= ISM_MAX_HALF_WIDTH))
+      return fail(AL_E_BADARG, "al_ism_shoebox_bands: c (ir_len + half + 42) / fs spans more than 2^20 mirror cells of the room");
+  const int64_t W = ism_bands_width(ir_len, half), per_pair = (int64_t)n_bands * W * (int64_t)sizeof(double);
+  if (!workspace || ((uintptr_t)workspace & 15) != 0) return fail(AL_E_BADARG, "al_ism_shoebox_bands: workspace must be 16-byte aligned and not null");
+  if (!with_tail && workspace_bytes < per_pair)   // with a tail: ism_bands_tail_prepare, against the shorter row
+    return fail(AL_E_BADARG, "al_ism_shoebox_bands: workspace smaller than al_ism_shoebox_bands_workspace_bytes (one pair)");
+  bj->filters = filters;
+  bj->workspace = (double *)workspace;
+  bj->n_bands = n_bands;
+  bj->half = half;
+  bj->y_end = ir_len;
+  bj->W = (int32_t)W;
+  bj->n_ws_tiles = (int32_t)(W / ISM_TILE);
+  bj->n_out_tiles = bj->base.n_tiles;
+  bj->band0 = 0;
+  bj->pair0 = 0;
+  bj->band_tail_blocks = 0;
+  // pairs per pass: what the workspace holds, and no grid above 2^31 - 1 workgroups
+  const int64_t most_tiles = bj->n_ws_tiles > bj->n_out_tiles ? bj->n_ws_tiles : bj->n_out_tiles;
+  int64_t per_pass = workspace_bytes / per_pair;
+  if (per_pass > 0x7fffffff / most_tiles) per_pass = 0x7fffffff / most_tiles;
+  bj->pairs_per_pass = per_pass > 0 ? per_pass : 1;
+  return AL_OK;
+}
+
+// al_ism_shoebox_bands_tail's further arguments into a job ism_bands_prepare has filled (with the workspace check left to here:
+// a row with a tail needs y_end = min(ir_len, M + F) band samples only)
+inline int ism_bands_tail_prepare(int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env,
+                                  int32_t n_knots, int64_t workspace_bytes, IsmBandJob *bj) {
+  if (bj->half > ISM_BAND_TAIL_MAX_HALF) return fail(AL_E_BADARG, "al_ism_shoebox_bands_tail: half must be in 1 .. 1024 with a tail");
+  if (int rc = ism_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, &bj->base)) return rc;
+  if (bj->base.pitch > 0x7fffffff - 2 * (ISM_BT_SPAN + ISM_BAND_TAIL_MAX_HALF))   // k_ism_band_tail counts span + half past the row in int32
+    return fail(AL_E_BADARG, "al_ism_shoebox_bands_tail: pitch must be at most 2^31 - 4097");
+  IsmTail &tail = bj->base.tail;
+  tail.env_stride = (uint32_t)n_knots;   // from band b to band b + 1
+  bj->y_end = tail.y_end;
+  const int64_t W = ism_bands_width(bj->y_end, bj->half), per_pair = (int64_t)bj->n_bands * W * (int64_t)sizeof(double);
+  if (workspace_bytes < per_pair) return fail(AL_E_BADARG, "al_ism_shoebox_bands: workspace smaller than al_ism_shoebox_bands_workspace_bytes (one pair)");
+  bj->W = (int32_t)W;
+  bj->n_ws_tiles = (int32_t)(W / ISM_TILE);
+  bj->n_out_tiles = bj->base.n_tiles;   // the tiles below the split
+  const int64_t most_tiles = bj->n_ws_tiles > bj->n_out_tiles ? bj->n_ws_tiles : bj->n_out_tiles;
+  int64_t per_pass = workspace_bytes / per_pair;
+  if (per_pass > 0x7fffffff / most_tiles) per_pass = 0x7fffffff / most_tiles;
+  bj->pairs_per_pass = per_pass;
+  bj->band_tail_blocks = tail.split < bj->base.pitch ? (bj->base.pitch - tail.split + ISM_BT_SPAN - 1) / ISM_BT_SPAN : 0;
+  if ((int64_t)bj->band_tail_blocks * bj->base.n_sources * bj->base.n_capsules > 0x7fffffff)
+    return fail(AL_E_BADARG, "al_ism_shoebox_bands_tail: more than 2^31 - 1 workgroups (spans of 1024 samples x pairs): split the call");
+  return AL_OK;
+}
+
+template <int NB>
+inline void launch_ism_bands_group(const IsmBandJob &bj, int64_t pairs, hipStream_t stream) {
+  hipLaunchKernelGGL((k_ism_bands<NB>), dim3((unsigned)(pairs * bj.n_ws_tiles)), dim3(ISM_THREADS), 0, stream, bj);
+}
+
+template <bool TAIL>
+inline void launch_ism_bands_passes(const IsmBandJob &job, hipStream_t stream) {
+  const int64_t pairs = (int64_t)job.base.n_sources * job.base.n_capsules;
+  IsmBandJob bj = job;
+  for (int64_t pair0 = 0; pair0 < pairs; pair0 += job.pairs_per_pass) {
+    const int64_t in_pass = pairs - pair0 < job.pairs_per_pass ? pairs - pair0 : job.pairs_per_pass;
+    bj.pair0 = pair0;
+    for (int band0 = 0; band0 < job.n_bands; band0 += ISM_BAND_GROUP) {
+      bj.band0 = band0;
+      switch (job.n_bands - band0 < ISM_BAND_GROUP ? job.n_bands - band0 : ISM_BAND_GROUP) {
+        case 1: launch_ism_bands_group<1>(bj, in_pass, stream); break;
+        case 2: launch_ism_bands_group<2>(bj, in_pass, stream); break;
+        case 3: launch_ism_bands_group<3>(bj, in_pass, stream); break;
+        default: launch_ism_bands_group<4>(bj, in_pass, stream); break;
+      }
+    }
+    bj.band0 = 0;
+    hipLaunchKernelGGL(k_ism_band_combine<TAIL>, dim3((unsigned)(in_pass * bj.n_out_tiles)), dim3(ISM_THREADS), 0, stream, bj);
+  }
+}
+
+inline void launch_ism_shoebox_bands(const IsmBandJob &job, hipStream_t stream) { launch_ism_bands_passes<false>(job, stream); }
+
+inline void launch_ism_shoebox_bands_tail(const IsmBandJob &job, hipStream_t stream) {
+  launch_ism_bands_passes<true>(job, stream);
+  if (job.band_tail_blocks > 0) {
+    const dim3 grid((unsigned)((int64_t)job.band_tail_blocks * job.base.n_sources * job.base.n_capsules)), block(ISM_THREADS);
+    if (job.half <= 256)
+      hipLaunchKernelGGL(k_ism_band_tail<256>, grid, block, 0, stream, job);
+    else if (job.half <= 512)
+      hipLaunchKernelGGL(k_ism_band_tail<512>, grid, block, 0, stream, job);
+    else
+      hipLaunchKernelGGL(k_ism_band_tail<1024>, grid, block, 0, stream, job);
+  }
+}
+
+}  // namespace al

@@ -30,6 +30,7 @@
 #include "al_fft.h"
 #include "al_ingest.h"
 #include "al_ism.h"
+#include "al_ism_bands.h"
 #include "al_levels.h"
 #include "al_mac.h"
 #include "al_mixdown.h"
@@ -646,6 +647,37 @@ int al_ism_shoebox_dir_tail(const double *sources, int32_t n_sources, const doub
   if (int rc = al::ism_dir_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, &job)) return rc;
   al::launch_ism_shoebox_dir_tail(job, (hipStream_t)stream);
   return check_launch("k_ism_tail");
+}
+
+// ---- the same with frequency-dependent walls in bands: DESIGN.md "Shoebox IRs: frequency-dependent walls"
+int64_t al_ism_shoebox_bands_workspace_bytes(int32_t n_bands, int32_t half, int32_t ir_len, int64_t mix, int64_t fade) {
+  return al::ism_bands_workspace_bytes(n_bands, half, ir_len, mix, fade);
+}
+
+int al_ism_shoebox_bands(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
+                         const double *beta, int32_t n_bands, const double *filters, int32_t half, double c, double fs,
+                         int32_t max_order, int32_t ir_len, int32_t pitch, void *workspace, int64_t workspace_bytes, float *out,
+                         al_stream_t stream) {
+  al::IsmBandJob job;
+  if (int rc = al::ism_bands_prepare(sources, n_sources, capsules, n_capsules, L, beta, n_bands, filters, half, c, fs, max_order, ir_len,
+                                     pitch, workspace, workspace_bytes, out, &job))
+    return rc;
+  al::launch_ism_shoebox_bands(job, (hipStream_t)stream);
+  return check_launch("k_ism_band_combine");
+}
+
+int al_ism_shoebox_bands_tail(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
+                              const double *beta, int32_t n_bands, const double *filters, int32_t half, double c, double fs,
+                              int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade, uint64_t seed,
+                              int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, void *workspace,
+                              int64_t workspace_bytes, float *out, al_stream_t stream) {
+  al::IsmBandJob job;
+  if (int rc = al::ism_bands_prepare(sources, n_sources, capsules, n_capsules, L, beta, n_bands, filters, half, c, fs, max_order, ir_len,
+                                     pitch, workspace, workspace_bytes, out, &job, true))
+    return rc;
+  if (int rc = al::ism_bands_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, workspace_bytes, &job)) return rc;
+  al::launch_ism_shoebox_bands_tail(job, (hipStream_t)stream);
+  return check_launch("k_ism_band_tail");
 }
 
 int al_resample_poly(const float *x, int32_t rows, int64_t n_in, const float *taps, int32_t half_len, int32_t up, int32_t down,

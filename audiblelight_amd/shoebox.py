@@ -4,7 +4,9 @@
 born in HBM in the layout ``Renderer.prepare(plan, clips, irs, ir_strides)`` reads and never crosses PCIe.  ``DeviceIRTensor`` wraps
 it as a lazy array: the render path takes its buffer (``result()``), a host consumer downloads it once.  Point capsules,
 omnidirectional or with first-order patterns (``patterns=``: ``omni``, ``first_order``, ``cardioid``, ``foa_patterns``; the channels
-of a point share one image search, ``al_ism_shoebox_dir``), frequency-independent walls, no air absorption.  Without ``max_order`` the cost grows as
+of a point share one image search, ``al_ism_shoebox_dir``), no air absorption.  Walls are one broadband coefficient each, or, with
+``bands=`` (a ``ShoeboxBands``), a column of coefficients per octave band, from a material table if wanted (``load_materials``,
+``material_betas``, ``al_ism_shoebox_bands``; DESIGN.md "Shoebox IRs: frequency-dependent walls").  Without ``max_order`` the cost grows as
 ``ir_len**3 / (Lx * Ly * Lz)`` per (capsule, source) pair; with a ``ShoeboxTail`` the exact image sum ends a fade after the mixing
 time and the row continues as seeded Gaussian noise under an envelope that matches the image field in level and decay
 (``al_ism_shoebox_tail``, ``tail_envelope``; DESIGN.md "Shoebox IRs: the diffuse tail"), so a row of seconds costs a write of its bytes.
@@ -12,6 +14,7 @@ time and the row continues as seeded Gaussian noise under an envelope that match
 from __future__ import annotations
 
 import ctypes as ct
+import json
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
@@ -22,6 +25,11 @@ MIN_DISTANCE = 0.01     # metres between a source and a capsule
 KNOT_SPACING = 256      # samples between two knots of the tail's envelope table (the kernel's tile)
 MIXED_ECHO_DENSITY = 1.0e4   # echoes per second at which a field is heard as diffuse (Griesinger's figure): default_mix_time
 ENVELOPE_QUADRATURE = 64     # Gauss-Legendre points per variable of tail_envelope's direction average
+OCTAVE_CENTRES = (125.0, 250.0, 500.0, 1000.0, 2000.0, 4000.0)     # the band centres of the usual absorption tables, Hz
+MAX_BANDS = 8           # bands of al_ism_shoebox_bands
+MAX_BAND_HALF = 4096    # its cap on the half length of a band filter
+MAX_BAND_TAIL_HALF = 1024     # the cap of al_ism_shoebox_bands_tail
+BAND_WORKSPACE_CAP = 1 << 30     # bytes of band-sum workspace shoebox_irs_device allocates at most (never less than one pair's)
 
 
 def betas_from_absorption(alpha) -> np.ndarray:
@@ -194,6 +202,121 @@ def check_patterns(patterns, n_positions: int) -> np.ndarray:
     return patterns
 
 
+def _centres(centres, sample_rate: float) -> np.ndarray:
+    try:
+        centres = np.asarray(centres, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("band centres must be numbers")
+    if centres.ndim != 1 or not 1 <= len(centres) <= MAX_BANDS:
+        raise ValueError(f"1 to {MAX_BANDS} band centres, not an array of shape {centres.shape}")
+    if not (np.isfinite(sample_rate) and sample_rate > 0.0):
+        raise ValueError("sample_rate must be finite and positive")
+    if not np.all(np.isfinite(centres)) or np.any(centres <= 0.0) or np.any(np.diff(centres) <= 0.0) or centres[-1] >= 0.5 * sample_rate:
+        raise ValueError("band centres must be positive, strictly increasing and strictly below sample_rate / 2")
+    return centres
+
+
+def _half(half) -> int:
+    if isinstance(half, (bool, np.bool_)) or not isinstance(half, (int, np.integer)) or not 1 <= int(half) <= MAX_BAND_HALF:
+        raise ValueError(f"half must be an integer in 1 .. {MAX_BAND_HALF}")
+    return int(half)
+
+
+def band_filters(centres=OCTAVE_CENTRES, sample_rate: float = 48000.0, half: int = 512) -> np.ndarray:
+    """The float64 table ``phi`` of shape ``(B, 2 half + 1)``, ``phi[b, half + j] = phi_b[j]``, of the zero-phase band filters:
+    THE TABLE THIS RETURNS IS THE DEFINITION the kernels are handed.
+
+    On the grid ``f_k = k fs / Nf``, ``Nf = 4 half``, ``k = 0 .. Nf / 2`` the target magnitudes are ``G_0 = 1`` for ``f <= f_0``,
+    ``G_{B-1} = 1`` for ``f >= f_{B-1}``, and between two centres, with ``x = log2(f / f_b) / log2(f_{b+1} / f_b)``,
+    ``G_b = cos^2(pi x / 2)`` and ``G_{b+1} = sin^2(pi x / 2)``, every other band 0: ``sum_b G_b = 1`` at every grid point.
+    ``phi_b[j]`` for ``j = 0 .. half`` is sample ``j`` of the inverse real DFT of length ``Nf`` of ``G_b``
+    (``numpy.fft.irfft(G_b, Nf)``) times the window ``0.5 (1 + cos(pi j / (half + 1)))``, and ``phi_b[-j] = phi_b[j]`` is that same
+    number: the table is symmetric bit for bit.  ``sum_b phi_b`` is the unit impulse to 1e-15 (the window is 1 at ``j = 0`` and the
+    bands' spectra sum to 1), and one band alone is the impulse."""
+    half = _half(half)
+    centres = _centres(centres, sample_rate)
+    n_fft, n_bands = 4 * half, len(centres)
+    f = np.arange(n_fft // 2 + 1, dtype=np.float64) * float(sample_rate) / n_fft
+    G = np.zeros((n_bands, len(f)))
+    G[0, f <= centres[0]] = 1.0
+    G[-1, f >= centres[-1]] = 1.0
+    for b in range(n_bands - 1):
+        between = (f >= centres[b]) & (f < centres[b + 1])     # x = 0 at the centre itself: G_b = 1, G_{b+1} = 0 exactly
+        x = np.log2(f[between] / centres[b]) / np.log2(centres[b + 1] / centres[b])
+        G[b, between] = np.cos(0.5 * np.pi * x) ** 2
+        G[b + 1, between] = np.sin(0.5 * np.pi * x) ** 2
+    j = np.arange(half + 1)
+    right = np.fft.irfft(G, n_fft, axis=1)[:, : half + 1] * (0.5 * (1.0 + np.cos(np.pi * j / (half + 1.0))))[None, :]
+    return np.ascontiguousarray(np.concatenate([right[:, :0:-1], right], axis=1))
+
+
+@dataclass(frozen=True)
+class ShoeboxBands:
+    """The bands of a shoebox room with frequency-dependent walls: ``centres`` in Hz (1 to 8, increasing, below half the sample
+    rate) and the half length ``half`` of the band filters (``band_filters``).  ``betas`` of such a room has shape ``(6, B)``."""
+
+    centres: Tuple[float, ...] = OCTAVE_CENTRES
+    half: int = 512
+
+    def __post_init__(self):
+        object.__setattr__(self, "centres", tuple(float(v) for v in np.ravel(np.asarray(self.centres, dtype=np.float64))))
+
+    def to_dict(self) -> dict:
+        return dict(centres=list(self.centres), half=int(self.half))
+
+    @classmethod
+    def from_dict(cls, d) -> "ShoeboxBands":
+        if isinstance(d, cls):
+            return d
+        return cls(centres=tuple(d.get("centres", OCTAVE_CENTRES)), half=d.get("half", 512))
+
+
+def load_materials(path) -> dict:
+    """A material file ``{"materials": [{"name": ..., "absorption": [f0, a0, f1, a1, ...], ...}]}`` as ``name -> (freqs, alphas)``,
+    two float64 arrays with the frequencies in Hz increasing.  Every other key of a material is ignored."""
+    with open(path) as fh:
+        data = json.load(fh)
+    table = {}
+    for m in data["materials"]:
+        pairs = np.asarray(m["absorption"], dtype=np.float64)
+        if pairs.ndim != 1 or len(pairs) < 2 or len(pairs) % 2:
+            raise ValueError(f"material {m['name']!r}: absorption must be a flat list f0, a0, f1, a1, ...")
+        freqs, alphas = pairs[0::2], pairs[1::2]
+        if not np.all(np.isfinite(pairs)) or np.any(freqs <= 0.0) or np.any(np.diff(freqs) <= 0.0):
+            raise ValueError(f"material {m['name']!r}: frequencies must be positive and increasing")
+        table[str(m["name"])] = (freqs.copy(), alphas.copy())
+    return table
+
+
+def material_betas(table: dict, walls, centres=OCTAVE_CENTRES) -> np.ndarray:
+    """Reflection coefficients ``(6, B)`` of six walls ``(x0, x1, y0, y1, z0, z1)`` named in ``table`` (``load_materials``); one
+    name serves all six.  A wall's absorption is interpolated linearly in ``log2 f`` at the band centres, held at its end values
+    outside the table's range, and goes through ``betas_from_absorption``.  An unknown name is a KeyError."""
+    walls = [walls] * 6 if isinstance(walls, str) else list(walls)
+    if len(walls) != 6:
+        raise ValueError("walls must be six material names (x0, x1, y0, y1, z0, z1) or one name")
+    centres = np.asarray(centres, dtype=np.float64)
+    if centres.ndim != 1 or len(centres) < 1 or not np.all(np.isfinite(centres)) or np.any(centres <= 0.0):
+        raise ValueError("band centres must be positive numbers")
+    alphas = np.stack([np.interp(np.log2(centres), np.log2(table[name][0]), table[name][1]) for name in walls])
+    return betas_from_absorption(alphas)
+
+
+def check_bands(bands, betas, sample_rate: float) -> np.ndarray:
+    """The band checks of ``check_arguments``: ``betas`` as float64 ``(6, B)`` for ``bands`` (ValueError)."""
+    if not isinstance(bands, ShoeboxBands):
+        raise ValueError("bands must be a ShoeboxBands or None")
+    centres = _centres(bands.centres, sample_rate)
+    _half(bands.half)
+    try:
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("betas must be an array of shape (6, bands)")
+    if betas.shape != (6, len(centres)) or not np.all(np.isfinite(betas)) or np.any(betas < 0.0) or np.any(betas > 1.0):
+        raise ValueError(f"with bands, betas must have shape (6, {len(centres)}): a column of six reflection coefficients in [0, 1] per band")
+    return betas
+
+
 def tail_energy_law(room, betas, sample_rate: float, c: float = SPEED_OF_SOUND, pattern=None):
     """``tau -> ln(sigma^2 D(tau))``, ``tau`` in seconds: the expected squared sample of the image-source field (``tail_envelope``
     states the law and the quadrature rule), seen through ``pattern`` (None: omni)."""
@@ -265,13 +388,23 @@ def tail_envelope(room, betas, ir_len: int, sample_rate: float, mix: int, c: flo
     return 0.5 * ln_energy(int(mix) / fs) - (3.0 * np.log(10.0) / float(rt60)) * (knots - int(mix)) / fs
 
 
-def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED_OF_SOUND, max_order=None, tail=None, patterns=None):
+def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED_OF_SOUND, max_order=None, tail=None, patterns=None,
+                    bands=None):
     """The host-side validation of ``shoebox_irs_device`` (ValueError); returns the arguments as the call takes them (the pattern
-    table through ``check_patterns``)."""
+    table through ``check_patterns``).  With ``bands`` (a ``ShoeboxBands``) ``betas`` is ``(6, B)``."""
     room = _room(room)
-    betas = np.ascontiguousarray(betas, dtype=np.float64)
-    if betas.shape != (6,) or not np.all(np.isfinite(betas)) or np.any(betas < 0.0) or np.any(betas > 1.0):
-        raise ValueError("betas must be six reflection coefficients (x0, x1, y0, y1, z0, z1) in [0, 1]")
+    if bands is not None:
+        if not (np.isfinite(sample_rate) and sample_rate > 0.0):
+            raise ValueError("sample_rate and c must be finite and positive")
+        betas = check_bands(bands, betas, float(sample_rate))
+        if patterns is not None:
+            raise ValueError("bands together with patterns are not yet supported (K x B gains per image)")
+        if tail is not None and bands.half > MAX_BAND_TAIL_HALF:
+            raise ValueError(f"with a diffuse tail the band filters' half length is at most {MAX_BAND_TAIL_HALF}")
+    else:
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+        if betas.shape != (6,) or not np.all(np.isfinite(betas)) or np.any(betas < 0.0) or np.any(betas > 1.0):
+            raise ValueError("betas must be six reflection coefficients (x0, x1, y0, y1, z0, z1) in [0, 1]")
     sources, capsules = _points(sources, room, "sources"), _points(capsules, room, "capsules")
     if int(ir_len) != ir_len or ir_len < 1:
         raise ValueError("ir_len must be an integer >= 1")
@@ -291,7 +424,8 @@ def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED
 
 def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sample_rate: float, c: float = SPEED_OF_SOUND,
                        max_order: Optional[int] = None, tail: Optional[ShoeboxTail] = None, source_id0: int = 0,
-                       capsule_id0: int = 0, patterns=None):
+                       capsule_id0: int = 0, patterns=None, bands: Optional[ShoeboxBands] = None,
+                       workspace_cap: int = BAND_WORKSPACE_CAP):
     """The IRs of ``sources`` (N, 3) at ``capsules`` (C, 3) in the room ``(Lx, Ly, Lz)`` with wall reflection coefficients
     ``betas = (x0, x1, y0, y1, z0, z1)``: ``(device buffer, (stride_c, stride_n), ir_len)`` as ``ingest.pack_ragged_irs`` returns
     it, enqueued on the renderer's stream.  The two coordinate tables are all that is uploaded.  With ``tail`` (a ``ShoeboxTail``)
@@ -303,9 +437,46 @@ def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sa
     position p with the pattern ``(w, vx, vy, vz) = patterns[p, k]`` in room axes (``omni``, ``first_order``, ``cardioid``,
     ``foa_patterns``); the tensor has the P K rows ``c = p K + k`` (``al_ism_shoebox_dir``; DESIGN.md "Shoebox IRs: directional
     receivers"), one image search per position.  With a tail, row c draws as capsule ``capsule_id0 + c`` under the envelope of
-    its own pattern.  None: omnidirectional capsules, the call above."""
+    its own pattern.  None: omnidirectional capsules, the call above.
+
+    ``bands`` (a ``ShoeboxBands``): frequency-dependent walls, ``betas`` of shape ``(6, B)`` with a column per band
+    (``material_betas``); ``al_ism_shoebox_bands``, DESIGN.md "Shoebox IRs: frequency-dependent walls".  The band filters are
+    uploaded (``band_filters``) and a float64 workspace for the band sums is allocated for the call: what all pairs need, at most
+    ``workspace_cap`` bytes and at least one pair's; the entry walks the pairs in passes of what it holds, and the rows' bits do
+    not depend on it.  With ``tail`` every band decays under its own envelope, ``tail_envelope`` of its column of ``betas``
+    (``al_ism_shoebox_bands_tail``; every coefficient > 0).  Not yet together with ``patterns`` (ValueError)."""
     room, betas, sources, capsules, ir_len, fs, c, order = check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c,
-                                                                          max_order, tail)
+                                                                          max_order, tail, patterns, bands)
+    if bands is not None:
+        if isinstance(workspace_cap, (bool, np.bool_)) or not isinstance(workspace_cap, (int, np.integer)) or workspace_cap < 0:
+            raise ValueError("workspace_cap must be an integer >= 0 (bytes)")
+        mem, lib = renderer.mem, renderer.lib
+        n, n_cap, pitch, n_bands, half = len(sources), len(capsules), pitch_of(ir_len), betas.shape[1], int(bands.half)
+        mix, fade = (-1, 0) if tail is None else tail_samples(tail, room, fs, c)
+        if tail is not None:
+            for name, v, count in (("source_id0", source_id0, n), ("capsule_id0", capsule_id0, n_cap)):
+                if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0 or int(v) + count > 1 << 32:
+                    raise ValueError(f"{name} must be an integer >= 0 with {name} + count <= 2^32")
+        per_pair = lib.call("al_ism_shoebox_bands_workspace_bytes", n_bands, half, ir_len, mix, fade)
+        if per_pair <= 0:
+            raise ValueError(f"al_ism_shoebox_bands_workspace_bytes refused {n_bands} bands, half = {half}, ir_len = {ir_len}")
+        pairs_per_pass = max(1, min(n * n_cap, int(workspace_cap) // per_pair))
+        workspace = mem.empty(pairs_per_pass * per_pair // 8, dtype=np.float64)
+        phi_dev = mem.upload(band_filters(bands.centres, fs, half).reshape(-1))
+        src_dev, cap_dev = mem.upload(sources.reshape(-1)), mem.upload(capsules.reshape(-1))
+        out = mem.empty(n_cap * n * pitch)
+        if tail is not None:
+            ln_env = np.stack([tail_envelope(room, betas[:, b], ir_len, fs, mix, c, tail.rt60) for b in range(n_bands)])
+            env_dev = mem.upload(ln_env.reshape(-1))
+            lib.call("al_ism_shoebox_bands_tail", mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, room.ctypes.data_as(ct.POINTER(ct.c_double)),
+                     betas.ctypes.data_as(ct.POINTER(ct.c_double)), n_bands, mem.ptr(phi_dev), half, c, fs, order, ir_len, pitch, mix, fade,
+                     int(tail.seed), int(source_id0), int(capsule_id0), mem.ptr(env_dev), ln_env.shape[1], mem.ptr(workspace),
+                     pairs_per_pass * per_pair, mem.ptr(out), mem.stream())
+            return out, (n * pitch, pitch), ir_len
+        lib.call("al_ism_shoebox_bands", mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, room.ctypes.data_as(ct.POINTER(ct.c_double)),
+                 betas.ctypes.data_as(ct.POINTER(ct.c_double)), n_bands, mem.ptr(phi_dev), half, c, fs, order, ir_len, pitch,
+                 mem.ptr(workspace), pairs_per_pass * per_pair, mem.ptr(out), mem.stream())
+        return out, (n * pitch, pitch), ir_len
     if patterns is not None:
         patterns = check_patterns(patterns, len(capsules))
     n_rows = len(capsules) * (1 if patterns is None else patterns.shape[1])

@@ -657,6 +657,52 @@ int al_ism_shoebox_dir_tail(const double *sources, int32_t n_sources, const doub
                             int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, float *out,
                             al_stream_t stream);
 
+/* The same rows with FREQUENCY-DEPENDENT WALLS in n_bands (1 .. 8) bands (DESIGN.md "Shoebox IRs: frequency-dependent walls").
+ * beta is a HOST array (6, n_bands): column b holds the six reflection coefficients of band b.  filters is a float64 DEVICE table
+ * (n_bands, 2 half + 1) of zero-phase FIRs phi_b[j], j = -half .. half (shoebox.band_filters: the table IS the definition; not checked,
+ * never read on the host).  With y_b[s] the float64 image sum of al_ism_shoebox under beta[:, b] at every integer s in
+ * [-half, ir_len + half) -- negative s included, the row boundary does not truncate a band sum --
+ *   out[(c * n_sources + n) * pitch + t] = float32( sum_b sum_{j = -half .. half} phi_b[j] y_b[t - j] ),
+ * the double sum in float64 in the order b ascending, then j ascending, rounded once; pad samples [ir_len, pitch) are +0.  A row's
+ * bits depend on the room, the pair, beta, the table and half alone: not on n_sources, n_capsules, the pitch, the other rows or
+ * workspace_bytes; two runs are identical.
+ * workspace: DEVICE memory, 16-byte aligned, of workspace_bytes >= al_ism_shoebox_bands_workspace_bytes(n_bands, half, ir_len, -1, 0)
+ * (the bytes of ONE pair: n_bands rows of ir_len + 2 half float64 rounded up to 256).  The entry takes workspace_bytes / that many
+ * pairs per pass, each pass ceil(n_bands / 4) gathers and one combine, in order on `stream`: the workspace is reused in stream
+ * order; no allocation, no synchronisation.  Its contents after the call are unspecified.
+ * al_ism_shoebox_bands_workspace_bytes: mix < 0 sizes a row without a tail; mix >= 0 with fade >= 1 sizes the image part of a row
+ * with a tail (al_ism_shoebox_bands_tail), min(ir_len, mix + fade) samples.  Negative (AL_E_BADARG) for n_bands outside
+ * 1 .. 8, half outside 1 .. 4096, ir_len < 1, or mix >= 0 with fade < 1.
+ * AL_E_BADARG: everything al_ism_shoebox refuses, for every band's column; n_bands outside 1 .. 8; half < 1 or half > 4096; a null
+ * table; a workspace that is null, not 16-byte aligned or smaller than one pair; a room so small that c (ir_len + half + 42) / fs
+ * spans more than 2^20 mirror cells of an axis. */
+int64_t al_ism_shoebox_bands_workspace_bytes(int32_t n_bands, int32_t half, int32_t ir_len, int64_t mix, int64_t fade);
+int al_ism_shoebox_bands(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
+                         const double *beta, int32_t n_bands, const double *filters, int32_t half, double c, double fs,
+                         int32_t max_order, int32_t ir_len, int32_t pitch, void *workspace, int64_t workspace_bytes, float *out,
+                         al_stream_t stream);
+
+/* al_ism_shoebox_bands with the DIFFUSE TAIL of al_ism_shoebox_tail, a decay per band.  ln_env is a float64 DEVICE table
+ * (n_bands, n_knots), n_knots = (ir_len - 1) / 256 + 2: band b's log-amplitude knots (shoebox.tail_envelope of beta[:, b]).  M, F, the
+ * fade weights w_e, w_l, the draws g(s) of row (c, n) -- zero outside [0, ir_len) -- and the ids are al_ism_shoebox_tail's.  With
+ * y_end = min(ir_len, M + F) the band sums y_b are formed for s in [-half, y_end + half) and y(t) as in al_ism_shoebox_bands; with
+ *   psi_k[j] = sum_b exp(ln_env[b][k]) phi_b[j]   (a knot of -inf contributes 0),  k = t / 256,  p = (t % 256) / 256,
+ *   n(t) = (1 - p) sum_j psi_k[j] g(t - j) + p sum_j psi_{k+1}[j] g(t - j)         (p == 0 reads knot k alone),
+ *   out = float32(w_e y(t) + w_l n(t)),  no noise term where w_l == 0,  pads +0.
+ * The envelope is interpolated linearly in AMPLITUDE between two knots (al_ism_shoebox_tail interpolates its one envelope in the
+ * logarithm, which does not factor out of a sum over bands): two FIRs per sample whatever n_bands is.  Sums are float64, one rounding
+ * to float32.  With mix >= ir_len the output has the bits of al_ism_shoebox_bands.  A row's bits depend on the room, the pair, beta,
+ * the tables, half, the seed and the two ids alone.  workspace: as al_ism_shoebox_bands, a pair taking
+ * al_ism_shoebox_bands_workspace_bytes(n_bands, half, ir_len, mix, fade) bytes.  Per pass ceil(n_bands / 4) gathers and one combine (the
+ * samples below ceil((M + F) / 256) * 256), then one launch for the samples from there on of every row; no allocation, no
+ * synchronisation.
+ * AL_E_BADARG: everything al_ism_shoebox_bands and al_ism_shoebox_tail refuse; half > 1024. */
+int al_ism_shoebox_bands_tail(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
+                              const double *beta, int32_t n_bands, const double *filters, int32_t half, double c, double fs,
+                              int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade, uint64_t seed,
+                              int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, void *workspace,
+                              int64_t workspace_bytes, float *out, al_stream_t stream);
+
 /* dst[t] = src[t mod m] for t < n: np.pad(..., mode="wrap") of Augmentation.process. */
 int al_wrap_copy(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream);
 
