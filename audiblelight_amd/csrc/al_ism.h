@@ -6,9 +6,12 @@
 // the images of a (capsule, source) pair is lexicographic in (qx, qy, qz); every output sample is the float64 sum of its taps in
 // that order, rounded to float32 once.  Nothing is scattered and nothing is atomic: the kernel GATHERS.
 //
-// k_ism_shoebox  one workgroup of ONE WAVE per (pair, tile of ISM_TILE samples), ISM_PER_LANE samples per lane (lane, lane + 64, ...),
-//   the accumulators float64 registers.  (One wave: the __syncthreads() below order LDS traffic only, hipcc emits no barrier
-//   instruction for them, and no wave can be out of step with another.)
+// ism_gather  THE ONE IMAGE GATHER, behind k_ism_shoebox, k_ism_shoebox_dir and k_ism_bands (al_ism_bands.h): one workgroup of ONE WAVE
+//   per (pair or position, tile of ISM_TILE samples), ISM_PER_LANE samples per lane (lane, lane + 64, ...), the accumulators float64
+//   registers.  (One wave: the __syncthreads() below order LDS traffic only, hipcc emits no barrier instruction for them, and no
+//   wave can be out of step with another.)  A kernel decodes blockIdx, writes its pad or empty tiles, hands the gather its tile as
+//   (s_lo, t_hi, s_end) with its LDS, and stores what the gather accumulated; a small VARIANT type says which images are dead, what a
+//   list entry carries and how it is filled (IsmOmni, IsmDir<K>, IsmBands<NB>).
 //   The images that can reach the tile lie in the shell d_lo < |R| < d_hi.  The wave walks the lattice COLUMNS (qx, qy) in
 //   order, ISM_THREADS at a time, lane k taking column base + k:
 //     1. the lane bounds the column's qz by the shell (at most two runs: below and above the inner sphere; a column wholly inside the
@@ -16,7 +19,7 @@
 //        (the exact test, on the image's own rint(tau): the runs are only a superset);
 //     2. an exclusive prefix sum of the counts over the wave (suffix sums by __shfl_down, the total through LDS);
 //     3. the lane walks its runs again and writes its touching images to the LDS list at its offset: the list is in canonical order.
-//        A list longer than ISM_LIST goes in windows of ISM_LIST, in order;
+//        A list longer than the variant's window (ISM_LIST, ISM_DIR_LIST) goes in windows, in order;
 //     4. every lane then adds the taps of the list's images that reach ITS samples, in list order.
 //   The order of a sample's sum depends on the room and the pair alone, never on the grid, the other pairs or the list size.
 // A tap costs one LDS entry, two table reads and a division: sin(pi (t - tau)) = -(-1)^j sin(pi f) and the window's cosine by the
@@ -98,19 +101,38 @@ __device__ __forceinline__ double ism_offset(int q, double s, double r, double L
   ism_mp(q, m, p);
   return (double)(1 - 2 * p) * s + 2.0 * (double)m * L - r;
 }
-// k0 ln(beta0) + k1 ln(beta1) of an axis; dead: a wall of beta == 0 has been hit
-__device__ __forceinline__ double ism_log_gain(int q, const double *ln_beta, const int32_t *zero, bool &dead) {
+// reflections of image q of an axis by its wall at 0 and its wall at L
+__device__ __forceinline__ void ism_counts(int q, int &k0, int &k1) {
   int m, p;
   ism_mp(q, m, p);
-  const int k0 = abs(m - p), k1 = abs(m);
-  dead = dead || (k0 > 0 && zero[0]) || (k1 > 0 && zero[1]);
+  k0 = abs(m - p);
+  k1 = abs(m);
+}
+// k0 ln(beta0) + k1 ln(beta1) of an axis (ln_beta: the axis's two entries, 0 where beta == 0)
+__device__ __forceinline__ double ism_log_gain(int q, const double *ln_beta) {
+  int k0, k1;
+  ism_counts(q, k0, k1);
   return (double)k0 * ln_beta[0] + (double)k1 * ln_beta[1];
+}
+// image q of an axis is alive unless it has hit a wall of beta == 0 (zero: the axis's two flags)
+__device__ __forceinline__ bool ism_alive(int q, const int32_t *zero) {
+  int k0, k1;
+  ism_counts(q, k0, k1);
+  return !((k0 > 0 && zero[0]) || (k1 > 0 && zero[1]));
 }
 
 // the qz of a column, as two runs [a1, b1] and [a2, b2] (empty when a > b)
 struct IsmColumn {
-  double rho2, ln_xy;
+  double rho2;
   int a1, b1, a2, b2;
+};
+
+// an image that touches the tile, as a variant's fill sees it
+struct IsmImage {
+  int qx, qy, qz;
+  unsigned alive;   // the variant's mask of the image: alive(0, qx) & alive(1, qy) & alive(2, qz), never 0
+  double Rx, Ry, Rz, d, tau;
+  int t0;           // rint(tau)
 };
 
 __device__ __forceinline__ int ism_clamp(double v, int lo, int hi) { return v < (double)lo ? lo : v > (double)hi ? hi : (int)v; }
@@ -130,54 +152,78 @@ __device__ __forceinline__ float4 ism_tail_normal4(const IsmTail &tail, int q, i
   return make_float4(a.x, a.y, b.x, b.y);
 }
 
-template <bool TAIL>
-__global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
-  __shared__ IsmEntry list[ISM_LIST];
-  __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];   // cos, sin(2 pi j / 81), j = -40 .. 40
-  __shared__ int wave_total[2];
-  const int tid = threadIdx.x, lane = tid;
-  const int tile = (int)(blockIdx.x % (unsigned)job.n_tiles);
-  const int64_t pair = blockIdx.x / (unsigned)job.n_tiles;   // c * N + n
-  const int n = (int)(pair % job.n_sources), cap = (int)(pair / job.n_sources);
-  const int t_lo = tile * ISM_TILE, t = t_lo + tid;
-  // the image sum is needed below y_end only: past the fade the row is the tail's
-  const int y_end = TAIL ? job.tail.y_end : job.ir_len;
-  const int t_hi = min(t_lo + ISM_TILE, y_end) - 1;
-  float *row = job.out + pair * (int64_t)job.pitch;
-  if (t_lo >= job.ir_len) {   // a tile of pad samples only
-    for (int s = 0; s < ISM_PER_LANE; ++s)
-      if (t + s * ISM_THREADS < job.pitch) row[t + s * ISM_THREADS] = 0.f;
-    return;
-  }
+// draw ts of row (cap, n): normal ts % 4 of the block of samples 4 (ts / 4) ..
+__device__ __forceinline__ float ism_tail_normal(const IsmTail &tail, int ts, int n, int cap) {
+  const float4 g4 = ism_tail_normal4(tail, ts >> 2, n, cap);
+  return (ts & 2) ? ((ts & 1) ? g4.w : g4.z) : ((ts & 1) ? g4.y : g4.x);
+}
+// the fade weights of a sample ts > M: cos, sin(pi x / 2) with x = (ts - M) / F; (0, 1) from M + F on
+__device__ __forceinline__ void ism_fade(const IsmTail &tail, int ts, double &w_e, double &w_l) {
+  const double x = ((double)ts - (double)tail.mix) / (double)tail.fade;
+  w_e = 0.0, w_l = 1.0;
+  if (x < 1.0) sincospi(0.5 * x, &w_l, &w_e);
+}
+
+// what every list entry holds beside its gains: the tap's shape of an image of amplitude a
+template <class Entry>
+__device__ __forceinline__ void ism_fill_shape(Entry &e, const IsmImage &im, double a) {
+  double sp, cp, s81, c81;
+  const double f = im.tau - (double)im.t0;
+  sincospi(f, &sp, &cp);
+  sincospi(2.0 * f / (double)ISM_TAPS, &s81, &c81);
+  e.t0 = im.t0;
+  e.reserved = 0;
+  e.f = f;
+  e.a = a;
+  e.g = -0.5 * a * sp / M_PI;
+  e.s81 = s81;
+  e.c81 = c81;
+}
+
+// THE GATHER: steps 1 to 4 of the header comment for the tile of samples [s_lo, s_lo + ISM_TILE) cut at s_end (t_hi: its last
+// sample), of source n at receiver position pos.  s_lo may be negative (k_ism_bands).  Lane k adds into acc[s][g] the taps of
+// sample s_lo + k + 64 s under gain g, in canonical order.  The variant V says what differs between the kernels:
+//   V::NG, V::Entry, V::LIST   gains per image (0: none, the tap is added as it is), the list entry (f, g, a, c81, s81, t0 and
+//                              gain[NG]) and the entries per list window;
+//   v.alive(axis, q)           a bit mask, bit k clear when image q of the axis has hit a wall that is dead for gain k; an image
+//                              whose three masks have no common bit is left out of the list;
+//   v.fill(e, im)              list entry e of image im.
+// list (V::LIST entries), win_c, win_s (ISM_TAPS each) and wave_total (2) are the kernel's LDS.
+template <class V>
+__device__ __forceinline__ void ism_gather(const IsmJob &job, const V &v, int n, int pos, int s_lo, int t_hi, int s_end,
+                                           typename V::Entry *list, double *win_c, double *win_s, int *wave_total,
+                                           double (&acc)[ISM_PER_LANE][V::NG > 0 ? V::NG : 1]) {
+  constexpr int NG = V::NG, LIST = V::LIST;
+  const int tid = threadIdx.x, lane = tid, t = s_lo + tid;
+  // cos, sin(2 pi j / 81), j = -40 .. 40
   for (int i = tid; i < ISM_TAPS; i += ISM_THREADS) sincospi(2.0 * (double)(i - ISM_HALF) / (double)ISM_TAPS, &win_s[i], &win_c[i]);
 
   const double sx = job.sources[3 * n], sy = job.sources[3 * n + 1], sz = job.sources[3 * n + 2];
-  const double rx = job.capsules[3 * cap], ry = job.capsules[3 * cap + 1], rz = job.capsules[3 * cap + 2];
+  const double rx = job.capsules[3 * pos], ry = job.capsules[3 * pos + 1], rz = job.capsules[3 * pos + 2];
   const double Lx = job.L[0], Ly = job.L[1], Lz = job.L[2];
   // the shell of this tile, a sample wider than the taps reach on either side
-  const double d_hi = (double)(t_hi + ISM_HALF + 2) * job.c / job.fs, d_lo = (double)(t_lo - ISM_HALF - 2) * job.c / job.fs;
+  const double d_hi = (double)(t_hi + ISM_HALF + 2) * job.c / job.fs, d_lo = (double)(s_lo - ISM_HALF - 2) * job.c / job.fs;
   const double hi2 = d_hi * d_hi, lo2 = d_lo > 0.0 ? d_lo * d_lo : 0.0;
-  const int K = job.max_order;
+  const int order = job.max_order;
   int Qx = ism_clamp(floor(d_hi / Lx) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH), Qy = ism_clamp(floor(d_hi / Ly) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH),
       Qz = ism_clamp(floor(d_hi / Lz) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH);
-  if (K >= 0) {
-    Qx = min(Qx, K);
-    Qy = min(Qy, K);
-    Qz = min(Qz, K);
+  if (order >= 0) {
+    Qx = min(Qx, order);
+    Qy = min(Qy, order);
+    Qz = min(Qz, order);
   }
   const int64_t ny = 2 * (int64_t)Qy + 1, n_columns = (2 * (int64_t)Qx + 1) * ny;
 
-  // does image qz of column `col` touch the tile?  t0, tau and d of the image either way
-  auto touches = [&](const IsmColumn &col, int qz, double &d, double &tau, int &t0) {
-    const double Rz = ism_offset(qz, sz, rz, Lz);
+  // does image qz of column `col` touch the tile?  Rz, t0, tau and d of the image either way
+  auto touches = [&](const IsmColumn &col, int qz, double &Rz, double &d, double &tau, int &t0) {
+    Rz = ism_offset(qz, sz, rz, Lz);
     d = sqrt(col.rho2 + Rz * Rz);
     tau = d * job.fs / job.c;
     if (!(tau < 2.0e9) || !(d > 0.0)) return false;
     t0 = (int)rint(tau);
-    return t0 + ISM_HALF >= t_lo && t0 - ISM_HALF <= t_hi;
+    return t0 + ISM_HALF >= s_lo && t0 - ISM_HALF <= t_hi;
   };
 
-  double acc[ISM_PER_LANE] = {};
   int parity = 0;
   for (int64_t base = 0; base < n_columns; base += ISM_THREADS, parity ^= 1) {
     // 1. this lane's column
@@ -185,16 +231,15 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
     IsmColumn col;
     col.a1 = col.a2 = 0;
     col.b1 = col.b2 = -1;
-    bool dead = true;
+    unsigned alive_xy = 0;   // the gains for which the column is alive
     if (ci < n_columns) {
       const int qx = (int)(ci / ny) - Qx, qy = (int)(ci % ny) - Qy;
       const int k_xy = abs(qx) + abs(qy);
       const double Rx = ism_offset(qx, sx, rx, Lx), Ry = ism_offset(qy, sy, ry, Ly);
       col.rho2 = Rx * Rx + Ry * Ry;
-      if ((K < 0 || k_xy <= K) && col.rho2 < hi2) {
-        dead = false;
-        col.ln_xy = ism_log_gain(qx, job.ln_beta, job.beta_zero, dead) + ism_log_gain(qy, job.ln_beta + 2, job.beta_zero + 2, dead);
-        const int Kz = K < 0 ? Qz : min(Qz, K - k_xy);
+      if ((order < 0 || k_xy <= order) && col.rho2 < hi2) {
+        alive_xy = v.alive(0, qx) & v.alive(1, qy);
+        const int Kz = order < 0 ? Qz : min(Qz, order - k_xy);
         const double z_max = sqrt(hi2 - col.rho2);
         // image qz lies in (qz Lz, (qz + 1) Lz): one cell of margin on either side
         col.a1 = ism_clamp(floor((rz - z_max) / Lz) - 1.0, -Kz, Kz);
@@ -212,15 +257,12 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
       }
     }
     int count = 0;
-    if (!dead) {
-      double d, tau;
+    if (alive_xy) {
+      double Rz, d, tau;
       int t0;
       for (int run = 0; run < 2; ++run)
-        for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz) {
-          bool gone = false;
-          ism_log_gain(qz, job.ln_beta + 4, job.beta_zero + 4, gone);
-          if (!gone && touches(col, qz, d, tau, t0)) ++count;
-        }
+        for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz)
+          if ((alive_xy & v.alive(2, qz)) && touches(col, qz, Rz, d, tau, t0)) ++count;
     }
     // 2. exclusive prefix sum of the counts: suffix sums by shuffles, the total (lane 0's) through LDS
     int suffix = count;
@@ -232,68 +274,101 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
     if (lane == 0) wave_total[parity] = suffix;
     __syncthreads();
     const int total = wave_total[parity], offset = total - suffix;
-    // 3. + 4. the list, a window of ISM_LIST at a time
-    for (int w0 = 0; w0 < total; w0 += ISM_LIST) {
-      if (count > 0 && offset < w0 + ISM_LIST && offset + count > w0) {
-        int pos = offset;
+    // 3. + 4. the list, a window of LIST at a time
+    for (int w0 = 0; w0 < total; w0 += LIST) {
+      if (count > 0 && offset < w0 + LIST && offset + count > w0) {
+        IsmImage im;
+        im.qx = (int)(ci / ny) - Qx, im.qy = (int)(ci % ny) - Qy;
+        // the column's Rx, Ry again (not kept across the gather: registers)
+        im.Rx = ism_offset(im.qx, sx, rx, Lx), im.Ry = ism_offset(im.qy, sy, ry, Ly);
+        int at = offset;
         for (int run = 0; run < 2; ++run)
           for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz) {
-            bool gone = false;
-            const double ln_z = ism_log_gain(qz, job.ln_beta + 4, job.beta_zero + 4, gone);
-            double d, tau;
-            int t0;
-            if (gone || !touches(col, qz, d, tau, t0)) continue;
-            if (pos >= w0 && pos < w0 + ISM_LIST) {
-              IsmEntry e;
-              double sp, cp;
-              e.t0 = t0;
-              e.reserved = 0;
-              e.f = tau - (double)t0;
-              e.a = exp(col.ln_xy + ln_z) / (4.0 * M_PI * d);
-              sincospi(e.f, &sp, &cp);
-              e.g = -0.5 * e.a * sp / M_PI;
-              sincospi(2.0 * e.f / (double)ISM_TAPS, &e.s81, &e.c81);
-              list[pos - w0] = e;
-            }
-            ++pos;
+            im.qz = qz;
+            im.alive = alive_xy & v.alive(2, qz);
+            if (!im.alive || !touches(col, qz, im.Rz, im.d, im.tau, im.t0)) continue;
+            if (at >= w0 && at < w0 + LIST) v.fill(list[at - w0], im);
+            ++at;
           }
       }
       __syncthreads();
-      const int n_list = min(ISM_LIST, total - w0);
+      const int n_list = min(LIST, total - w0);
       for (int i = 0; i < n_list; ++i) {
         const int j0 = t - list[i].t0;   // of the lane's first sample; the others are 64 apart, so at most two are in reach
         if (j0 > ISM_HALF || j0 + (ISM_PER_LANE - 1) * ISM_THREADS < -ISM_HALF) continue;
-        const IsmEntry e = list[i];
+        const typename V::Entry e = list[i];
 #pragma unroll
         for (int s = 0; s < ISM_PER_LANE; ++s) {
           const int j = j0 + s * ISM_THREADS;
-          if (j < -ISM_HALF || j > ISM_HALF || t + s * ISM_THREADS >= y_end) continue;
+          if (j < -ISM_HALF || j > ISM_HALF || t + s * ISM_THREADS >= s_end) continue;
           const double u = (double)j - e.f;
           if (!(fabs(u) < 0.5 * (double)ISM_TAPS)) continue;
-          if (u == 0.0) {
-            acc[s] += e.a;
-          } else {
+          double shape = e.a;   // the tap of the image without its gains, formed once for the NG of them
+          if (u != 0.0) {
             const double window = 1.0 + (win_c[j + ISM_HALF] * e.c81 + win_s[j + ISM_HALF] * e.s81);
-            acc[s] += ((j & 1) ? -e.g : e.g) * window / u;
+            shape = ((j & 1) ? -e.g : e.g) * window / u;
+          }
+          if constexpr (NG == 0) {
+            acc[s][0] += shape;
+          } else {
+#pragma unroll
+            for (int k = 0; k < NG; ++k) acc[s][k] += shape * e.gain[k];
           }
         }
       }
       __syncthreads();
     }
   }
+}
+
+// the walls of a job with one column of reflection coefficients (IsmJob::ln_beta, beta_zero): one bit, one amplitude
+struct IsmWalls {
+  const IsmJob &job;
+  __device__ __forceinline__ unsigned alive(int axis, int q) const { return ism_alive(q, job.beta_zero + 2 * axis) ? 1u : 0u; }
+  __device__ __forceinline__ double amplitude(const IsmImage &im) const {
+    const double ln_xy = ism_log_gain(im.qx, job.ln_beta) + ism_log_gain(im.qy, job.ln_beta + 2), ln_z = ism_log_gain(im.qz, job.ln_beta + 4);
+    return exp(ln_xy + ln_z) / (4.0 * M_PI * im.d);
+  }
+};
+
+// the omnidirectional variant: no gains, 48-byte entries
+struct IsmOmni : IsmWalls {
+  static constexpr int NG = 0, LIST = ISM_LIST;
+  using Entry = IsmEntry;
+  __device__ __forceinline__ void fill(Entry &e, const IsmImage &im) const { ism_fill_shape(e, im, amplitude(im)); }
+};
+
+template <bool TAIL>
+__global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
+  __shared__ IsmEntry list[ISM_LIST];
+  __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];
+  __shared__ int wave_total[2];
+  const int tid = threadIdx.x;
+  const int tile = (int)(blockIdx.x % (unsigned)job.n_tiles);
+  const int64_t pair = blockIdx.x / (unsigned)job.n_tiles;   // c * N + n
+  const int n = (int)(pair % job.n_sources), cap = (int)(pair / job.n_sources);
+  const int t_lo = tile * ISM_TILE, t = t_lo + tid;
+  // the image sum is needed below y_end only: past the fade the row is the tail's
+  const int y_end = TAIL ? job.tail.y_end : job.ir_len;
+  const int t_hi = min(t_lo + ISM_TILE, y_end) - 1;
+  float *row = job.out + pair * (int64_t)job.pitch;
+  if (t_lo >= job.ir_len) {   // a tile of pad samples only
+    for (int s = 0; s < ISM_PER_LANE; ++s)
+      if (t + s * ISM_THREADS < job.pitch) row[t + s * ISM_THREADS] = 0.f;
+    return;
+  }
+  double acc[ISM_PER_LANE][1] = {};
+  ism_gather(job, IsmOmni{{job}}, n, cap, t_lo, t_hi, y_end, list, win_c, win_s, wave_total, acc);
 #pragma unroll
   for (int s = 0; s < ISM_PER_LANE; ++s) {
     const int ts = t + s * ISM_THREADS;
     if (ts >= job.pitch) continue;
-    double v = acc[s];
+    double v = acc[s][0];
     if constexpr (TAIL) {
       if (ts > job.tail.mix && ts < job.ir_len) {   // at or below M: w_e = 1, w_l = 0, the image sum as it is
-        const double x = ((double)ts - (double)job.tail.mix) / (double)job.tail.fade;
-        double w_e = 0.0, w_l = 1.0;
-        if (x < 1.0) sincospi(0.5 * x, &w_l, &w_e);
-        const float4 g4 = ism_tail_normal4(job.tail, ts >> 2, n, cap);
-        const float g = (ts & 2) ? ((ts & 1) ? g4.w : g4.z) : ((ts & 1) ? g4.y : g4.x);
-        v = w_e * v + w_l * ism_envelope(job.tail.ln_env, ts) * (double)g;
+        double w_e, w_l;
+        ism_fade(job.tail, ts, w_e, w_l);
+        v = w_e * v + w_l * ism_envelope(job.tail.ln_env, ts) * (double)ism_tail_normal(job.tail, ts, n, cap);
       }
     }
     row[ts] = ts < job.ir_len ? (float)v : 0.f;
@@ -384,6 +459,11 @@ inline void launch_ism_shoebox(const IsmJob &job, hipStream_t stream) {
   hipLaunchKernelGGL(k_ism_shoebox<false>, dim3((unsigned)groups), dim3(ISM_THREADS), 0, stream, job);
 }
 
+// the sample at which the image sum of a row with a tail ends: min(ir_len, M + F), for any mix and fade >= 0 (no overflow)
+inline int32_t ism_tail_y_end(int64_t mix, int64_t fade, int32_t ir_len) {
+  return mix < ir_len && fade < ir_len && mix + fade < ir_len ? (int32_t)(mix + fade) : ir_len;
+}
+
 // al_ism_shoebox_tail's further arguments into a job ism_prepare has filled: the tail, the split, the two grids
 inline int ism_tail_prepare(int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env,
                             int32_t n_knots, IsmJob *job) {
@@ -402,7 +482,7 @@ inline int ism_tail_prepare(int64_t mix, int64_t fade, uint64_t seed, int64_t so
   tail.mix = mix < cap ? mix : cap;   // a mix past the row is a mix at its end (and M + F cannot overflow)
   tail.fade = fade;
   tail.split = (int32_t)cap;
-  tail.y_end = fade < job->ir_len && tail.mix + fade < job->ir_len ? (int32_t)(tail.mix + fade) : job->ir_len;
+  tail.y_end = ism_tail_y_end(tail.mix, fade, job->ir_len);
   if (fade < cap && tail.mix + fade < cap) tail.split = (int32_t)((tail.mix + fade + ISM_TILE - 1) / ISM_TILE * ISM_TILE);
   tail.tail_blocks = tail.split < job->pitch ? (job->pitch - tail.split + ISM_TAIL_SPAN - 1) / ISM_TAIL_SPAN : 0;
   tail.seed_lo = (uint32_t)seed;
@@ -426,8 +506,7 @@ inline void launch_ism_shoebox_tail(const IsmJob &job, hipStream_t stream) {
 // P receiver positions with K <= 4 channels each and a pattern table pat[P][K][4] = (w, vx, vy, vz); row c = p K + k of the output
 // is the image sum of position p with every amplitude multiplied by w + v . R / |R|.  The K channels of a position share every
 // image, its delay and its 81 taps, so
-//   k_ism_shoebox_dir<K, TAIL>  one workgroup of one wave per (position, source, tile) serves all K rows: the lattice walk, the
-//     count, the prefix sum and the LDS list of k_ism_shoebox happen once (the same walk, the same canonical order, the same shell),
+//   k_ism_shoebox_dir<K, TAIL>  one workgroup of one wave per (position, source, tile) serves all K rows: ism_gather runs once,
 //     a list entry carries the K gains beside what is common, and a lane forms the tap's shape once per (image, sample) and adds it
 //     into K float64 accumulators: a channel costs a multiply-add per tap.  The list window is ISM_DIR_LIST = 96 entries of
 //     48 + 8 K bytes (rounded to 16), which keeps the workgroup's LDS at 7448 B (K <= 2) or 8984 B (K >= 3): the register count,
@@ -449,13 +528,30 @@ struct alignas(16) IsmDirEntry {
   double gain[K];             // w + v . R / d of each channel
 };
 
+// the directional variant: K pattern gains beside the omnidirectional image
+template <int K>
+struct IsmDir : IsmWalls {
+  static constexpr int NG = K, LIST = ISM_DIR_LIST;
+  using Entry = IsmDirEntry<K>;
+  const double *pat;   // the position's K patterns; uniform over the wave: scalar loads, no vector register holds a pattern
+  __device__ __forceinline__ void fill(Entry &e, const IsmImage &im) const {
+    // the gains go to the list before the common part is formed: neither is live while the other is computed
+    {
+      const double ux = im.Rx / im.d, uy = im.Ry / im.d, uz = im.Rz / im.d;   // the direction the image arrives from
+#pragma unroll
+      for (int k = 0; k < K; ++k) e.gain[k] = pat[4 * k] + (pat[4 * k + 1] * ux + pat[4 * k + 2] * uy + pat[4 * k + 3] * uz);
+    }
+    ism_fill_shape(e, im, amplitude(im));
+  }
+};
+
 template <int K, bool TAIL>
 __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox_dir(IsmDirJob dj) {
   __shared__ IsmDirEntry<K> list[ISM_DIR_LIST];
-  __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];   // cos, sin(2 pi j / 81), j = -40 .. 40
+  __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];
   __shared__ int wave_total[2];
   const IsmJob &job = dj.base;
-  const int tid = threadIdx.x, lane = tid;
+  const int tid = threadIdx.x;
   const int tile = (int)(blockIdx.x % (unsigned)job.n_tiles);
   const int64_t pair = blockIdx.x / (unsigned)job.n_tiles;   // p * N + n
   const int n = (int)(pair % job.n_sources), pos = (int)(pair / job.n_sources);
@@ -470,152 +566,8 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox_dir(IsmDirJob dj) {
         if (t + s * ISM_THREADS < job.pitch) row[k * row_stride + t + s * ISM_THREADS] = 0.f;
     return;
   }
-  for (int i = tid; i < ISM_TAPS; i += ISM_THREADS) sincospi(2.0 * (double)(i - ISM_HALF) / (double)ISM_TAPS, &win_s[i], &win_c[i]);
-  const double *pat = dj.patterns + (int64_t)pos * (4 * K);   // uniform over the wave: scalar loads, no vector register holds a pattern
-
-  const double sx = job.sources[3 * n], sy = job.sources[3 * n + 1], sz = job.sources[3 * n + 2];
-  const double rx = job.capsules[3 * pos], ry = job.capsules[3 * pos + 1], rz = job.capsules[3 * pos + 2];
-  const double Lx = job.L[0], Ly = job.L[1], Lz = job.L[2];
-  // the shell of this tile, a sample wider than the taps reach on either side
-  const double d_hi = (double)(t_hi + ISM_HALF + 2) * job.c / job.fs, d_lo = (double)(t_lo - ISM_HALF - 2) * job.c / job.fs;
-  const double hi2 = d_hi * d_hi, lo2 = d_lo > 0.0 ? d_lo * d_lo : 0.0;
-  const int order = job.max_order;
-  int Qx = ism_clamp(floor(d_hi / Lx) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH), Qy = ism_clamp(floor(d_hi / Ly) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH),
-      Qz = ism_clamp(floor(d_hi / Lz) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH);
-  if (order >= 0) {
-    Qx = min(Qx, order);
-    Qy = min(Qy, order);
-    Qz = min(Qz, order);
-  }
-  const int64_t ny = 2 * (int64_t)Qy + 1, n_columns = (2 * (int64_t)Qx + 1) * ny;
-
-  // does image qz of column `col` touch the tile?  Rz, t0, tau and d of the image either way
-  auto touches = [&](const IsmColumn &col, int qz, double &Rz, double &d, double &tau, int &t0) {
-    Rz = ism_offset(qz, sz, rz, Lz);
-    d = sqrt(col.rho2 + Rz * Rz);
-    tau = d * job.fs / job.c;
-    if (!(tau < 2.0e9) || !(d > 0.0)) return false;
-    t0 = (int)rint(tau);
-    return t0 + ISM_HALF >= t_lo && t0 - ISM_HALF <= t_hi;
-  };
-
   double acc[ISM_PER_LANE][K] = {};
-  int parity = 0;
-  for (int64_t base = 0; base < n_columns; base += ISM_THREADS, parity ^= 1) {
-    // 1. this lane's column
-    const int64_t ci = base + tid;
-    IsmColumn col;
-    col.a1 = col.a2 = 0;
-    col.b1 = col.b2 = -1;
-    bool dead = true;
-    if (ci < n_columns) {
-      const int qx = (int)(ci / ny) - Qx, qy = (int)(ci % ny) - Qy;
-      const int k_xy = abs(qx) + abs(qy);
-      const double Rx = ism_offset(qx, sx, rx, Lx), Ry = ism_offset(qy, sy, ry, Ly);
-      col.rho2 = Rx * Rx + Ry * Ry;
-      if ((order < 0 || k_xy <= order) && col.rho2 < hi2) {
-        dead = false;
-        col.ln_xy = ism_log_gain(qx, job.ln_beta, job.beta_zero, dead) + ism_log_gain(qy, job.ln_beta + 2, job.beta_zero + 2, dead);
-        const int Kz = order < 0 ? Qz : min(Qz, order - k_xy);
-        const double z_max = sqrt(hi2 - col.rho2);
-        // image qz lies in (qz Lz, (qz + 1) Lz): one cell of margin on either side
-        col.a1 = ism_clamp(floor((rz - z_max) / Lz) - 1.0, -Kz, Kz);
-        const int top = ism_clamp(floor((rz + z_max) / Lz) + 1.0, -Kz, Kz);
-        col.b1 = top;   // one run, unless the inner sphere cuts it in two
-        if (lo2 > col.rho2) {   // the cells wholly inside the inner sphere are left out
-          const double z_min = sqrt(lo2 - col.rho2);
-          const double ea = ceil((rz - z_min) / Lz) + 1.0, eb = floor((rz + z_min) / Lz) - 2.0;
-          if (ea <= eb) {
-            col.b1 = ism_clamp(ea - 1.0, -Kz - 1, Kz);
-            col.a2 = ism_clamp(eb + 1.0, -Kz, Kz + 1);
-            col.b2 = top;
-          }
-        }
-      }
-    }
-    int count = 0;
-    if (!dead) {
-      double Rz, d, tau;
-      int t0;
-      for (int run = 0; run < 2; ++run)
-        for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz) {
-          bool gone = false;
-          ism_log_gain(qz, job.ln_beta + 4, job.beta_zero + 4, gone);
-          if (!gone && touches(col, qz, Rz, d, tau, t0)) ++count;
-        }
-    }
-    // 2. exclusive prefix sum of the counts: suffix sums by shuffles, the total (lane 0's) through LDS
-    int suffix = count;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int other = __shfl_down(suffix, off, 64);
-      if (lane + off < 64) suffix += other;
-    }
-    if (lane == 0) wave_total[parity] = suffix;
-    __syncthreads();
-    const int total = wave_total[parity], offset = total - suffix;
-    // 3. + 4. the list, a window of ISM_DIR_LIST at a time
-    for (int w0 = 0; w0 < total; w0 += ISM_DIR_LIST) {
-      if (count > 0 && offset < w0 + ISM_DIR_LIST && offset + count > w0) {
-        // the column's Rx, Ry again (not kept across the gather: registers)
-        const double Rx = ism_offset((int)(ci / ny) - Qx, sx, rx, Lx), Ry = ism_offset((int)(ci % ny) - Qy, sy, ry, Ly);
-        int at = offset;
-        for (int run = 0; run < 2; ++run)
-          for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz) {
-            bool gone = false;
-            const double ln_z = ism_log_gain(qz, job.ln_beta + 4, job.beta_zero + 4, gone);
-            double Rz, d, tau;
-            int t0;
-            if (gone || !touches(col, qz, Rz, d, tau, t0)) continue;
-            if (at >= w0 && at < w0 + ISM_DIR_LIST) {
-              // the gains go to the list before the common part is formed: neither is live while the other is computed
-              IsmDirEntry<K> &e = list[at - w0];
-              {
-                const double ux = Rx / d, uy = Ry / d, uz = Rz / d;   // the direction the image arrives from
-#pragma unroll
-                for (int k = 0; k < K; ++k) e.gain[k] = pat[4 * k] + (pat[4 * k + 1] * ux + pat[4 * k + 2] * uy + pat[4 * k + 3] * uz);
-              }
-              double sp, cp, s81, c81;
-              const double f = tau - (double)t0, a = exp(col.ln_xy + ln_z) / (4.0 * M_PI * d);
-              sincospi(f, &sp, &cp);
-              sincospi(2.0 * f / (double)ISM_TAPS, &s81, &c81);
-              e.t0 = t0;
-              e.reserved = 0;
-              e.f = f;
-              e.a = a;
-              e.g = -0.5 * a * sp / M_PI;
-              e.s81 = s81;
-              e.c81 = c81;
-            }
-            ++at;
-          }
-      }
-      __syncthreads();
-      const int n_list = min(ISM_DIR_LIST, total - w0);
-      for (int i = 0; i < n_list; ++i) {
-        const int j0 = t - list[i].t0;   // of the lane's first sample; the others are 64 apart, so at most two are in reach
-        if (j0 > ISM_HALF || j0 + (ISM_PER_LANE - 1) * ISM_THREADS < -ISM_HALF) continue;
-        const IsmDirEntry<K> e = list[i];
-#pragma unroll
-        for (int s = 0; s < ISM_PER_LANE; ++s) {
-          const int j = j0 + s * ISM_THREADS;
-          if (j < -ISM_HALF || j > ISM_HALF || t + s * ISM_THREADS >= y_end) continue;
-          const double u = (double)j - e.f;
-          if (!(fabs(u) < 0.5 * (double)ISM_TAPS)) continue;
-          if (u == 0.0) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) acc[s][k] += e.a * e.gain[k];
-          } else {   // the omnidirectional tap, once for the K channels
-            const double window = 1.0 + (win_c[j + ISM_HALF] * e.c81 + win_s[j + ISM_HALF] * e.s81);
-            const double shape = ((j & 1) ? -e.g : e.g) * window / u;
-#pragma unroll
-            for (int k = 0; k < K; ++k) acc[s][k] += shape * e.gain[k];
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  ism_gather(job, IsmDir<K>{{job}, dj.patterns + (int64_t)pos * (4 * K)}, n, pos, t_lo, t_hi, y_end, list, win_c, win_s, wave_total, acc);
 #pragma unroll
   for (int s = 0; s < ISM_PER_LANE; ++s) {
     const int ts = t + s * ISM_THREADS;
@@ -625,9 +577,7 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox_dir(IsmDirJob dj) {
     if constexpr (TAIL) {
       if (ts > job.tail.mix && ts < job.ir_len) {   // at or below M: w_e = 1, w_l = 0, the image sum as it is
         mixed = true;
-        const double x = ((double)ts - (double)job.tail.mix) / (double)job.tail.fade;
-        w_e = 0.0, w_l = 1.0;
-        if (x < 1.0) sincospi(0.5 * x, &w_l, &w_e);
+        ism_fade(job.tail, ts, w_e, w_l);
       }
     }
 #pragma unroll
@@ -636,9 +586,7 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox_dir(IsmDirJob dj) {
       if constexpr (TAIL) {
         if (mixed) {
           const int c = pos * K + k;   // the row: its own noise stream and its own knot table
-          const float4 g4 = ism_tail_normal4(job.tail, ts >> 2, n, c);
-          const float g = (ts & 2) ? ((ts & 1) ? g4.w : g4.z) : ((ts & 1) ? g4.y : g4.x);
-          v = w_e * v + w_l * ism_envelope(job.tail.ln_env + (int64_t)c * job.tail.env_stride, ts) * (double)g;
+          v = w_e * v + w_l * ism_envelope(job.tail.ln_env + (int64_t)c * job.tail.env_stride, ts) * (double)ism_tail_normal(job.tail, ts, n, c);
         }
       }
       row[k * row_stride + ts] = ts < job.ir_len ? (float)v : 0.f;

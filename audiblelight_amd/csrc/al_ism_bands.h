@@ -5,8 +5,8 @@
 //   y(t) = sum_b sum_{j = -half .. half} phi_b[j] y_b[t - j],   float64, b ascending, then j ascending,
 // rounded to float32 once.  Two kernels share a row through a caller-provided float64 workspace [pair in pass][B][W],
 // W = y_end + 2 half rounded up to ISM_TILE, whose index w holds sample s = w - half:
-//   k_ism_bands<NB>  the gather of k_ism_shoebox_dir over the shifted axis: one workgroup of ONE WAVE per (pair, tile of W), the same
-//     lattice walk, the same canonical order (qx, qy, qz), the same shell.  A list entry carries NB <= 4 BAND GAINS
+//   k_ism_bands<NB>  ism_gather (al_ism.h: its walk, its canonical order) over the shifted axis, one workgroup of ONE WAVE per
+//     (pair, tile of W).  A list entry carries NB <= 4 BAND GAINS
 //     exp(sum k ln beta_b) in place of the pattern gains (logarithms taken on the host; a wall of beta_b == 0 in the path makes gain b
 //     exactly 0, which adds +-0 to that band's sum: the bits of leaving the image out; an image dead in every band of the group is
 //     left out of the list), a lane forms the tap's shape once per (image, sample) and adds it into NB float64 accumulators.  B > 4
@@ -72,40 +72,44 @@ struct alignas(16) IsmPsi {
   double x, y;   // psi_k[j], psi_{k+1}[j]: one 16-byte LDS read per tap
 };
 
-// reflections of image q of an axis by its wall at 0 and its wall at L
-__device__ __forceinline__ void ism_counts(int q, int &k0, int &k1) {
-  int m, p;
-  ism_mp(q, m, p);
-  k0 = abs(m - p);
-  k1 = abs(m);
-}
-// the bands of [band0, band0 + NB) in which image q of axis `axis` is alive (no wall of beta == 0 hit), as a bit mask
+// the band variant: the gains of the NB bands [band0, band0 + NB) beside the image between rigid walls
 template <int NB>
-__device__ __forceinline__ unsigned ism_band_alive(const IsmBandJob &bj, int axis, int q) {
-  int k0, k1;
-  ism_counts(q, k0, k1);
-  unsigned alive = 0;
+struct IsmBands {
+  static constexpr int NG = NB, LIST = ISM_DIR_LIST;
+  using Entry = IsmDirEntry<NB>;
+  const IsmBandJob &bj;
+  // the bands of the group in which image q of the axis is alive (no wall of beta_b == 0 hit)
+  __device__ __forceinline__ unsigned alive(int axis, int q) const {
+    unsigned mask = 0;
 #pragma unroll
-  for (int k = 0; k < NB; ++k) {
-    const int32_t *zero = bj.beta_zero[bj.band0 + k] + 2 * axis;
-    if (!((k0 > 0 && zero[0]) || (k1 > 0 && zero[1]))) alive |= 1u << k;
+    for (int k = 0; k < NB; ++k)
+      if (ism_alive(q, bj.beta_zero[bj.band0 + k] + 2 * axis)) mask |= 1u << k;
+    return mask;
   }
-  return alive;
-}
+  __device__ __forceinline__ void fill(Entry &e, const IsmImage &im) const {
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {   // prod beta_b^k, the logarithms summed as al_ism.h sums them: (x + y) + z
+      const double *lb = bj.ln_beta[bj.band0 + k];
+      const double ln_xy = ism_log_gain(im.qx, lb) + ism_log_gain(im.qy, lb + 2), ln_z = ism_log_gain(im.qz, lb + 4);
+      e.gain[k] = ((im.alive >> k) & 1u) ? exp(ln_xy + ln_z) : 0.0;
+    }
+    ism_fill_shape(e, im, 1.0 / (4.0 * M_PI * im.d));   // a, g of the image between rigid walls
+  }
+};
 
 template <int NB>
 __global__ __launch_bounds__(ISM_THREADS) void k_ism_bands(IsmBandJob bj) {
   __shared__ IsmDirEntry<NB> list[ISM_DIR_LIST];
-  __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];   // cos, sin(2 pi j / 81), j = -40 .. 40
+  __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];
   __shared__ int wave_total[2];
   const IsmJob &job = bj.base;
-  const int tid = threadIdx.x, lane = tid;
+  const int tid = threadIdx.x;
   const int tile = (int)(blockIdx.x % (unsigned)bj.n_ws_tiles);
   const int64_t local = blockIdx.x / (unsigned)bj.n_ws_tiles, pair = bj.pair0 + local;   // c * N + n
   const int n = (int)(pair % job.n_sources), cap = (int)(pair / job.n_sources);
   // the tile in workspace words w and in samples s = w - half
   const int w_lo = tile * ISM_TILE, w = w_lo + tid;
-  const int s_lo = w_lo - bj.half, t = s_lo + tid;
+  const int s_lo = w_lo - bj.half;
   const int s_end = bj.y_end + bj.half;                // the band sums are formed for s < s_end
   const int t_hi = min(s_lo + ISM_TILE, s_end) - 1;
   double *rows = bj.workspace + (local * bj.n_bands + bj.band0) * (int64_t)bj.W;   // band band0 of the pair; band k is k * W on
@@ -114,150 +118,8 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_bands(IsmBandJob bj) {
       for (int s = 0; s < ISM_PER_LANE; ++s) rows[(int64_t)k * bj.W + w + s * ISM_THREADS] = 0.0;
     return;
   }
-  for (int i = tid; i < ISM_TAPS; i += ISM_THREADS) sincospi(2.0 * (double)(i - ISM_HALF) / (double)ISM_TAPS, &win_s[i], &win_c[i]);
-
-  const double sx = job.sources[3 * n], sy = job.sources[3 * n + 1], sz = job.sources[3 * n + 2];
-  const double rx = job.capsules[3 * cap], ry = job.capsules[3 * cap + 1], rz = job.capsules[3 * cap + 2];
-  const double Lx = job.L[0], Ly = job.L[1], Lz = job.L[2];
-  // the shell of this tile, a sample wider than the taps reach on either side
-  const double d_hi = (double)(t_hi + ISM_HALF + 2) * job.c / job.fs, d_lo = (double)(s_lo - ISM_HALF - 2) * job.c / job.fs;
-  const double hi2 = d_hi * d_hi, lo2 = d_lo > 0.0 ? d_lo * d_lo : 0.0;
-  const int order = job.max_order;
-  int Qx = ism_clamp(floor(d_hi / Lx) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH), Qy = ism_clamp(floor(d_hi / Ly) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH),
-      Qz = ism_clamp(floor(d_hi / Lz) + 1.0, 0, (int)ISM_MAX_HALF_WIDTH);
-  if (order >= 0) {
-    Qx = min(Qx, order);
-    Qy = min(Qy, order);
-    Qz = min(Qz, order);
-  }
-  const int64_t ny = 2 * (int64_t)Qy + 1, n_columns = (2 * (int64_t)Qx + 1) * ny;
-
-  // does image qz of column `col` touch the tile?  t0, tau and d of the image either way
-  auto touches = [&](const IsmColumn &col, int qz, double &d, double &tau, int &t0) {
-    const double Rz = ism_offset(qz, sz, rz, Lz);
-    d = sqrt(col.rho2 + Rz * Rz);
-    tau = d * job.fs / job.c;
-    if (!(tau < 2.0e9) || !(d > 0.0)) return false;
-    t0 = (int)rint(tau);
-    return t0 + ISM_HALF >= s_lo && t0 - ISM_HALF <= t_hi;
-  };
-
   double acc[ISM_PER_LANE][NB] = {};
-  int parity = 0;
-  for (int64_t base = 0; base < n_columns; base += ISM_THREADS, parity ^= 1) {
-    // 1. this lane's column
-    const int64_t ci = base + tid;
-    IsmColumn col;
-    col.a1 = col.a2 = 0;
-    col.b1 = col.b2 = -1;
-    unsigned alive_xy = 0;   // the bands of the group in which the column is alive
-    if (ci < n_columns) {
-      const int qx = (int)(ci / ny) - Qx, qy = (int)(ci % ny) - Qy;
-      const int k_xy = abs(qx) + abs(qy);
-      const double Rx = ism_offset(qx, sx, rx, Lx), Ry = ism_offset(qy, sy, ry, Ly);
-      col.rho2 = Rx * Rx + Ry * Ry;
-      if ((order < 0 || k_xy <= order) && col.rho2 < hi2) {
-        alive_xy = ism_band_alive<NB>(bj, 0, qx) & ism_band_alive<NB>(bj, 1, qy);
-        const int Kz = order < 0 ? Qz : min(Qz, order - k_xy);
-        const double z_max = sqrt(hi2 - col.rho2);
-        // image qz lies in (qz Lz, (qz + 1) Lz): one cell of margin on either side
-        col.a1 = ism_clamp(floor((rz - z_max) / Lz) - 1.0, -Kz, Kz);
-        const int top = ism_clamp(floor((rz + z_max) / Lz) + 1.0, -Kz, Kz);
-        col.b1 = top;   // one run, unless the inner sphere cuts it in two
-        if (lo2 > col.rho2) {   // the cells wholly inside the inner sphere are left out
-          const double z_min = sqrt(lo2 - col.rho2);
-          const double ea = ceil((rz - z_min) / Lz) + 1.0, eb = floor((rz + z_min) / Lz) - 2.0;
-          if (ea <= eb) {
-            col.b1 = ism_clamp(ea - 1.0, -Kz - 1, Kz);
-            col.a2 = ism_clamp(eb + 1.0, -Kz, Kz + 1);
-            col.b2 = top;
-          }
-        }
-      }
-    }
-    int count = 0;
-    if (alive_xy) {
-      double d, tau;
-      int t0;
-      for (int run = 0; run < 2; ++run)
-        for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz)
-          if ((alive_xy & ism_band_alive<NB>(bj, 2, qz)) && touches(col, qz, d, tau, t0)) ++count;
-    }
-    // 2. exclusive prefix sum of the counts: suffix sums by shuffles, the total (lane 0's) through LDS
-    int suffix = count;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int other = __shfl_down(suffix, off, 64);
-      if (lane + off < 64) suffix += other;
-    }
-    if (lane == 0) wave_total[parity] = suffix;
-    __syncthreads();
-    const int total = wave_total[parity], offset = total - suffix;
-    // 3. + 4. the list, a window of ISM_DIR_LIST at a time
-    for (int w0 = 0; w0 < total; w0 += ISM_DIR_LIST) {
-      if (count > 0 && offset < w0 + ISM_DIR_LIST && offset + count > w0) {
-        int kx0, kx1, ky0, ky1;
-        ism_counts((int)(ci / ny) - Qx, kx0, kx1);
-        ism_counts((int)(ci % ny) - Qy, ky0, ky1);
-        int at = offset;
-        for (int run = 0; run < 2; ++run)
-          for (int qz = run ? col.a2 : col.a1, end = run ? col.b2 : col.b1; qz <= end; ++qz) {
-            const unsigned alive = alive_xy & ism_band_alive<NB>(bj, 2, qz);
-            double d, tau;
-            int t0;
-            if (!alive || !touches(col, qz, d, tau, t0)) continue;
-            if (at >= w0 && at < w0 + ISM_DIR_LIST) {
-              IsmDirEntry<NB> &e = list[at - w0];
-              int kz0, kz1;
-              ism_counts(qz, kz0, kz1);
-#pragma unroll
-              for (int k = 0; k < NB; ++k) {   // prod beta_b^k, the logarithms summed as al_ism.h sums them: (x + y) + z
-                const double *lb = bj.ln_beta[bj.band0 + k];
-                const double ln_xy = ((double)kx0 * lb[0] + (double)kx1 * lb[1]) + ((double)ky0 * lb[2] + (double)ky1 * lb[3]);
-                const double ln_z = (double)kz0 * lb[4] + (double)kz1 * lb[5];
-                e.gain[k] = ((alive >> k) & 1u) ? exp(ln_xy + ln_z) : 0.0;
-              }
-              double sp, cp, s81, c81;
-              const double f = tau - (double)t0, a = 1.0 / (4.0 * M_PI * d);   // a, g of the image between rigid walls
-              sincospi(f, &sp, &cp);
-              sincospi(2.0 * f / (double)ISM_TAPS, &s81, &c81);
-              e.t0 = t0;
-              e.reserved = 0;
-              e.f = f;
-              e.a = a;
-              e.g = -0.5 * a * sp / M_PI;
-              e.s81 = s81;
-              e.c81 = c81;
-            }
-            ++at;
-          }
-      }
-      __syncthreads();
-      const int n_list = min(ISM_DIR_LIST, total - w0);
-      for (int i = 0; i < n_list; ++i) {
-        const int j0 = t - list[i].t0;   // of the lane's first sample; the others are 64 apart, so at most two are in reach
-        if (j0 > ISM_HALF || j0 + (ISM_PER_LANE - 1) * ISM_THREADS < -ISM_HALF) continue;
-        const IsmDirEntry<NB> e = list[i];
-#pragma unroll
-        for (int s = 0; s < ISM_PER_LANE; ++s) {
-          const int j = j0 + s * ISM_THREADS;
-          if (j < -ISM_HALF || j > ISM_HALF || t + s * ISM_THREADS >= s_end) continue;
-          const double u = (double)j - e.f;
-          if (!(fabs(u) < 0.5 * (double)ISM_TAPS)) continue;
-          if (u == 0.0) {
-#pragma unroll
-            for (int k = 0; k < NB; ++k) acc[s][k] += e.a * e.gain[k];
-          } else {   // the tap between rigid walls, once for the NB bands
-            const double window = 1.0 + (win_c[j + ISM_HALF] * e.c81 + win_s[j + ISM_HALF] * e.s81);
-            const double shape = ((j & 1) ? -e.g : e.g) * window / u;
-#pragma unroll
-            for (int k = 0; k < NB; ++k) acc[s][k] += shape * e.gain[k];
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  ism_gather(job, IsmBands<NB>{bj}, n, cap, s_lo, t_hi, s_end, list, win_c, win_s, wave_total, acc);
 #pragma unroll
   for (int s = 0; s < ISM_PER_LANE; ++s)   // w + s * ISM_THREADS < W: the tile lies inside the row
 #pragma unroll
@@ -266,9 +128,7 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_bands(IsmBandJob bj) {
 
 // draw s of row (cap, n); zero outside [0, ir_len)
 __device__ __forceinline__ float ism_band_draw(const IsmJob &job, int s, int n, int cap) {
-  if (s < 0 || s >= job.ir_len) return 0.f;
-  const float4 g4 = ism_tail_normal4(job.tail, s >> 2, n, cap);
-  return (s & 2) ? ((s & 1) ? g4.w : g4.z) : ((s & 1) ? g4.y : g4.x);
+  return s < 0 || s >= job.ir_len ? 0.f : ism_tail_normal(job.tail, s, n, cap);
 }
 
 // out[t] = float32(sum_b sum_j phi_b[j] y_b[t - j]); grid: n_out_tiles workgroups of ONE WAVE per pair of the pass, a lane owning
@@ -449,8 +309,22 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_band_tail(IsmBandJob bj) {
   }
 }
 
-// W of a row: y_end + 2 half rounded up to the tile
-inline int64_t ism_bands_width(int64_t y_end, int64_t half) { return (y_end + 2 * half + ISM_TILE - 1) / ISM_TILE * ISM_TILE; }
+// THE LAYOUT of a job (n_bands, half and base.n_tiles set) whose band sums end at y_end, in a workspace of workspace_bytes: W of a row
+// (y_end + 2 half rounded up to the tile), the two tile counts, and the pairs per pass: what the workspace holds, and no grid above
+// 2^31 - 1 workgroups.  Returns the bytes a pair takes; a workspace below that holds no pair (pairs_per_pass == 0)
+inline int64_t ism_bands_layout(IsmBandJob *bj, int32_t y_end, int64_t workspace_bytes) {
+  const int64_t W = ((int64_t)y_end + 2 * (int64_t)bj->half + ISM_TILE - 1) / ISM_TILE * ISM_TILE;
+  const int64_t per_pair = (int64_t)bj->n_bands * W * (int64_t)sizeof(double);
+  bj->y_end = y_end;
+  bj->W = (int32_t)W;
+  bj->n_ws_tiles = (int32_t)(W / ISM_TILE);
+  bj->n_out_tiles = bj->base.n_tiles;   // with a tail: the tiles below the split
+  const int64_t most_tiles = bj->n_ws_tiles > bj->n_out_tiles ? bj->n_ws_tiles : bj->n_out_tiles;
+  int64_t per_pass = workspace_bytes < per_pair ? 0 : workspace_bytes / per_pair;
+  if (per_pass > 0x7fffffff / most_tiles) per_pass = 0x7fffffff / most_tiles;
+  bj->pairs_per_pass = per_pass;
+  return per_pair;
+}
 
 // al_ism_shoebox_bands_workspace_bytes: bytes per pair, or AL_E_BADARG.  mix < 0: no tail (y_end = ir_len)
 inline int64_t ism_bands_workspace_bytes(int32_t n_bands, int32_t half, int32_t ir_len, int64_t mix, int64_t fade) {
@@ -458,9 +332,11 @@ inline int64_t ism_bands_workspace_bytes(int32_t n_bands, int32_t half, int32_t 
   if (half < 1 || half > ISM_BAND_MAX_HALF) return fail(AL_E_BADARG, "al_ism_shoebox_bands: half must be in 1 .. 4096");
   if (ir_len < 1) return fail(AL_E_BADARG, "al_ism_shoebox_bands: ir_len must be >= 1");
   if (mix >= 0 && fade < 1) return fail(AL_E_BADARG, "al_ism_shoebox_bands: fade must be >= 1");
-  int64_t y_end = ir_len;
-  if (mix >= 0 && mix < ir_len && fade < ir_len && mix + fade < ir_len) y_end = mix + fade;
-  return (int64_t)n_bands * ism_bands_width(y_end, half) * (int64_t)sizeof(double);
+  IsmBandJob bj;
+  bj.n_bands = n_bands;
+  bj.half = half;
+  bj.base.n_tiles = 1;
+  return ism_bands_layout(&bj, mix < 0 ? ir_len : ism_tail_y_end(mix, fade, ir_len), 0);
 }
 
 // al_ism_shoebox_bands's arguments as the kernels' job: 0 with *bj filled, or the error of the first bad argument
@@ -486,26 +362,16 @@ inline int ism_bands_prepare(const double *sources, int32_t n_sources, const dou
   for (int i = 0; i < 3; ++i)   // the band sums reach `half` past the row
     if (!(c * ((double)ir_len + (double)half + 42.0) / fs / L[i] + 2.0 <= ISM_MAX_HALF_WIDTH))
       return fail(AL_E_BADARG, "al_ism_shoebox_bands: c (ir_len + half + 42) / fs spans more than 2^20 mirror cells of the room");
-  const int64_t W = ism_bands_width(ir_len, half), per_pair = (int64_t)n_bands * W * (int64_t)sizeof(double);
   if (!workspace || ((uintptr_t)workspace & 15) != 0) return fail(AL_E_BADARG, "al_ism_shoebox_bands: workspace must be 16-byte aligned and not null");
-  if (!with_tail && workspace_bytes < per_pair)   // with a tail: ism_bands_tail_prepare, against the shorter row
-    return fail(AL_E_BADARG, "al_ism_shoebox_bands: workspace smaller than al_ism_shoebox_bands_workspace_bytes (one pair)");
   bj->filters = filters;
   bj->workspace = (double *)workspace;
   bj->n_bands = n_bands;
   bj->half = half;
-  bj->y_end = ir_len;
-  bj->W = (int32_t)W;
-  bj->n_ws_tiles = (int32_t)(W / ISM_TILE);
-  bj->n_out_tiles = bj->base.n_tiles;
   bj->band0 = 0;
   bj->pair0 = 0;
   bj->band_tail_blocks = 0;
-  // pairs per pass: what the workspace holds, and no grid above 2^31 - 1 workgroups
-  const int64_t most_tiles = bj->n_ws_tiles > bj->n_out_tiles ? bj->n_ws_tiles : bj->n_out_tiles;
-  int64_t per_pass = workspace_bytes / per_pair;
-  if (per_pass > 0x7fffffff / most_tiles) per_pass = 0x7fffffff / most_tiles;
-  bj->pairs_per_pass = per_pass > 0 ? per_pass : 1;
+  if (workspace_bytes < ism_bands_layout(bj, ir_len, workspace_bytes) && !with_tail)   // with a tail: ism_bands_tail_prepare, against the shorter row
+    return fail(AL_E_BADARG, "al_ism_shoebox_bands: workspace smaller than al_ism_shoebox_bands_workspace_bytes (one pair)");
   return AL_OK;
 }
 
@@ -519,16 +385,8 @@ inline int ism_bands_tail_prepare(int64_t mix, int64_t fade, uint64_t seed, int6
     return fail(AL_E_BADARG, "al_ism_shoebox_bands_tail: pitch must be at most 2^31 - 4097");
   IsmTail &tail = bj->base.tail;
   tail.env_stride = (uint32_t)n_knots;   // from band b to band b + 1
-  bj->y_end = tail.y_end;
-  const int64_t W = ism_bands_width(bj->y_end, bj->half), per_pair = (int64_t)bj->n_bands * W * (int64_t)sizeof(double);
-  if (workspace_bytes < per_pair) return fail(AL_E_BADARG, "al_ism_shoebox_bands: workspace smaller than al_ism_shoebox_bands_workspace_bytes (one pair)");
-  bj->W = (int32_t)W;
-  bj->n_ws_tiles = (int32_t)(W / ISM_TILE);
-  bj->n_out_tiles = bj->base.n_tiles;   // the tiles below the split
-  const int64_t most_tiles = bj->n_ws_tiles > bj->n_out_tiles ? bj->n_ws_tiles : bj->n_out_tiles;
-  int64_t per_pass = workspace_bytes / per_pair;
-  if (per_pass > 0x7fffffff / most_tiles) per_pass = 0x7fffffff / most_tiles;
-  bj->pairs_per_pass = per_pass;
+  if (workspace_bytes < ism_bands_layout(bj, tail.y_end, workspace_bytes))
+    return fail(AL_E_BADARG, "al_ism_shoebox_bands: workspace smaller than al_ism_shoebox_bands_workspace_bytes (one pair)");
   bj->band_tail_blocks = tail.split < bj->base.pitch ? (bj->base.pitch - tail.split + ISM_BT_SPAN - 1) / ISM_BT_SPAN : 0;
   if ((int64_t)bj->band_tail_blocks * bj->base.n_sources * bj->base.n_capsules > 0x7fffffff)
     return fail(AL_E_BADARG, "al_ism_shoebox_bands_tail: more than 2^31 - 1 workgroups (spans of 1024 samples x pairs): split the call");

@@ -447,75 +447,54 @@ def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sa
     (``al_ism_shoebox_bands_tail``; every coefficient > 0).  Not yet together with ``patterns`` (ValueError)."""
     room, betas, sources, capsules, ir_len, fs, c, order = check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c,
                                                                           max_order, tail, patterns, bands)
+    if bands is not None and (isinstance(workspace_cap, (bool, np.bool_)) or not isinstance(workspace_cap, (int, np.integer))
+                              or workspace_cap < 0):
+        raise ValueError("workspace_cap must be an integer >= 0 (bytes)")
+    if patterns is not None:
+        patterns = check_patterns(patterns, len(capsules))
+    n, n_cap, pitch = len(sources), len(capsules), pitch_of(ir_len)
+    n_rows = n_cap * (1 if patterns is None else patterns.shape[1])
+    if tail is not None:
+        for name, v, count in (("source_id0", source_id0, n), ("capsule_id0", capsule_id0, n_rows)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0 or int(v) + count > 1 << 32:
+                raise ValueError(f"{name} must be an integer >= 0 with {name} + count <= 2^32")
+    mem, lib = renderer.mem, renderer.lib
+    mix, fade = (-1, 0) if tail is None else tail_samples(tail, room, fs, c)
+    # the entry and its arguments: head, (pattern | band) middle, lengths, [tail], [workspace], out, stream
+    entry = "al_ism_shoebox"
+    middle = walls = (room.ctypes.data_as(ct.POINTER(ct.c_double)), betas.ctypes.data_as(ct.POINTER(ct.c_double)))
+    tail_block = workspace_pair = ()
+    ln_env = None       # with a tail: one knot table per row, per distinct pattern or per band column
     if bands is not None:
-        if isinstance(workspace_cap, (bool, np.bool_)) or not isinstance(workspace_cap, (int, np.integer)) or workspace_cap < 0:
-            raise ValueError("workspace_cap must be an integer >= 0 (bytes)")
-        mem, lib = renderer.mem, renderer.lib
-        n, n_cap, pitch, n_bands, half = len(sources), len(capsules), pitch_of(ir_len), betas.shape[1], int(bands.half)
-        mix, fade = (-1, 0) if tail is None else tail_samples(tail, room, fs, c)
-        if tail is not None:
-            for name, v, count in (("source_id0", source_id0, n), ("capsule_id0", capsule_id0, n_cap)):
-                if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0 or int(v) + count > 1 << 32:
-                    raise ValueError(f"{name} must be an integer >= 0 with {name} + count <= 2^32")
+        n_bands, half = betas.shape[1], int(bands.half)
         per_pair = lib.call("al_ism_shoebox_bands_workspace_bytes", n_bands, half, ir_len, mix, fade)
         if per_pair <= 0:
             raise ValueError(f"al_ism_shoebox_bands_workspace_bytes refused {n_bands} bands, half = {half}, ir_len = {ir_len}")
         pairs_per_pass = max(1, min(n * n_cap, int(workspace_cap) // per_pair))
         workspace = mem.empty(pairs_per_pass * per_pair // 8, dtype=np.float64)
-        phi_dev = mem.upload(band_filters(bands.centres, fs, half).reshape(-1))
-        src_dev, cap_dev = mem.upload(sources.reshape(-1)), mem.upload(capsules.reshape(-1))
-        out = mem.empty(n_cap * n * pitch)
+        table_dev = mem.upload(band_filters(bands.centres, fs, half).reshape(-1))
+        entry, middle = entry + "_bands", walls + (n_bands, mem.ptr(table_dev), half)
+        workspace_pair = (mem.ptr(workspace), pairs_per_pass * per_pair)
         if tail is not None:
             ln_env = np.stack([tail_envelope(room, betas[:, b], ir_len, fs, mix, c, tail.rt60) for b in range(n_bands)])
-            env_dev = mem.upload(ln_env.reshape(-1))
-            lib.call("al_ism_shoebox_bands_tail", mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, room.ctypes.data_as(ct.POINTER(ct.c_double)),
-                     betas.ctypes.data_as(ct.POINTER(ct.c_double)), n_bands, mem.ptr(phi_dev), half, c, fs, order, ir_len, pitch, mix, fade,
-                     int(tail.seed), int(source_id0), int(capsule_id0), mem.ptr(env_dev), ln_env.shape[1], mem.ptr(workspace),
-                     pairs_per_pass * per_pair, mem.ptr(out), mem.stream())
-            return out, (n * pitch, pitch), ir_len
-        lib.call("al_ism_shoebox_bands", mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, room.ctypes.data_as(ct.POINTER(ct.c_double)),
-                 betas.ctypes.data_as(ct.POINTER(ct.c_double)), n_bands, mem.ptr(phi_dev), half, c, fs, order, ir_len, pitch,
-                 mem.ptr(workspace), pairs_per_pass * per_pair, mem.ptr(out), mem.stream())
-        return out, (n * pitch, pitch), ir_len
-    if patterns is not None:
-        patterns = check_patterns(patterns, len(capsules))
-    n_rows = len(capsules) * (1 if patterns is None else patterns.shape[1])
-    if tail is not None:
-        for name, v, count in (("source_id0", source_id0, len(sources)), ("capsule_id0", capsule_id0, n_rows)):
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0 or int(v) + count > 1 << 32:
-                raise ValueError(f"{name} must be an integer >= 0 with {name} + count <= 2^32")
-    mem, lib = renderer.mem, renderer.lib
-    n, n_cap, pitch = len(sources), len(capsules), pitch_of(ir_len)
-    src_dev, cap_dev = mem.upload(sources.reshape(-1)), mem.upload(capsules.reshape(-1))
-    out = mem.empty(n_rows * n * pitch)
-    if patterns is not None:
-        pat_dev, n_channels = mem.upload(patterns.reshape(-1)), patterns.shape[1]
-        L, B = room.ctypes.data_as(ct.POINTER(ct.c_double)), betas.ctypes.data_as(ct.POINTER(ct.c_double))
+    elif patterns is not None:
+        table_dev = mem.upload(patterns.reshape(-1))
+        entry, middle = entry + "_dir", (mem.ptr(table_dev), patterns.shape[1]) + walls
         if tail is not None:
-            mix, fade = tail_samples(tail, room, fs, c)
-            tables = {}     # one knot table per distinct pattern, one row of the upload per channel
+            tables = {}
             for pattern in patterns.reshape(-1, 4):
                 if pattern.tobytes() not in tables:
                     tables[pattern.tobytes()] = tail_envelope(room, betas, ir_len, fs, mix, c, tail.rt60, pattern)
             ln_env = np.stack([tables[pattern.tobytes()] for pattern in patterns.reshape(-1, 4)])
-            env_dev = mem.upload(ln_env.reshape(-1))
-            lib.call("al_ism_shoebox_dir_tail", mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, mem.ptr(pat_dev), n_channels, L, B, c, fs,
-                     order, ir_len, pitch, mix, fade, int(tail.seed), int(source_id0), int(capsule_id0), mem.ptr(env_dev),
-                     ln_env.shape[1], mem.ptr(out), mem.stream())
-        else:
-            lib.call("al_ism_shoebox_dir", mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, mem.ptr(pat_dev), n_channels, L, B, c, fs, order,
-                     ir_len, pitch, mem.ptr(out), mem.stream())
-        return out, (n * pitch, pitch), ir_len
+    elif tail is not None:
+        ln_env = tail_envelope(room, betas, ir_len, fs, mix, c, tail.rt60)[None]
     if tail is not None:
-        mix, fade = tail_samples(tail, room, fs, c)
-        ln_env = tail_envelope(room, betas, ir_len, fs, mix, c, tail.rt60)
-        env_dev = mem.upload(ln_env)
-        lib.call("al_ism_shoebox_tail", mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, room.ctypes.data_as(ct.POINTER(ct.c_double)),
-                 betas.ctypes.data_as(ct.POINTER(ct.c_double)), c, fs, order, ir_len, pitch, mix, fade, int(tail.seed), int(source_id0),
-                 int(capsule_id0), mem.ptr(env_dev), len(ln_env), mem.ptr(out), mem.stream())
-        return out, (n * pitch, pitch), ir_len
-    lib.call("al_ism_shoebox", mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, room.ctypes.data_as(ct.POINTER(ct.c_double)),
-             betas.ctypes.data_as(ct.POINTER(ct.c_double)), c, fs, order, ir_len, pitch, mem.ptr(out), mem.stream())
+        env_dev = mem.upload(ln_env.reshape(-1))
+        entry, tail_block = entry + "_tail", (mix, fade, int(tail.seed), int(source_id0), int(capsule_id0), mem.ptr(env_dev), ln_env.shape[1])
+    src_dev, cap_dev = mem.upload(sources.reshape(-1)), mem.upload(capsules.reshape(-1))
+    out = mem.empty(n_rows * n * pitch)
+    lib.call(entry, mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, *middle, c, fs, order, ir_len, pitch, *tail_block, *workspace_pair,
+             mem.ptr(out), mem.stream())
     return out, (n * pitch, pitch), ir_len
 
 

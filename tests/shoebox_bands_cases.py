@@ -334,6 +334,18 @@ def run_close_capsule(r):
     assert int(np.argmax(np.abs(rows[0, 0]))) == 0 and rows[0, 0, 0] > 1.0 / (4 * np.pi * 0.01) * 0.5
 
 
+def run_crowded_tile(r):
+    """shoebox_cases.run_crowded_tile's room, row and pair with two bands: more than 2000 images (the broadband oracle's count;
+    band 0 has no wall at 0 and keeps every one of them), so the gather's last tiles go through several windows of its 96-entry
+    LDS list."""
+    room, ir_len = (2.0, 1.6, 1.2), 600
+    s, m = np.array([0.7, 0.5, 0.4]), np.array([1.4, 1.1, 0.8])
+    rows, _ = check_parity(r, room, BETA_8[:, :2], centres_of(2, FS), 16, s, m, ir_len, FS, what="crowded tile")
+    assert np.abs(rows).max() > 0 and np.all(BETA_8[:, 0] > 0)
+    _, _, used = sc.oracle(room, (0.9, 0.95, 0.85, 0.9, 0.97, 0.8), s, m, ir_len, FS)
+    assert used[0, 0] > 2000, used
+
+
 # ----------------------------------------------------------------------------- 2. ties to the broadband oracle and entry
 def run_equal_columns(r):
     """Equal band columns: sum_b phi_b = delta, so the row is the broadband row of shoebox_cases' oracle (an oracle this module's

@@ -36,6 +36,10 @@ def test_close_capsule(gpu):
     cases.run_close_capsule(gpu)
 
 
+def test_crowded_tile(gpu):
+    cases.run_crowded_tile(gpu)
+
+
 def test_equal_columns_are_the_broadband_oracle(gpu):
     cases.run_equal_columns(gpu)
 

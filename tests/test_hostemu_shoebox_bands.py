@@ -41,6 +41,10 @@ def test_emu_close_capsule(emu):
     cases.run_close_capsule(emu)
 
 
+def test_emu_crowded_tile(emu):
+    cases.run_crowded_tile(emu)
+
+
 def test_emu_equal_columns_are_the_broadband_oracle(emu):
     cases.run_equal_columns(emu)
 
