@@ -309,13 +309,16 @@ class ShoeboxIRState:
     ``bands``: a ``shoebox.ShoeboxBands`` (or its dictionary) gives the walls a reflection coefficient per band (DESIGN.md "Shoebox
     IRs: frequency-dependent walls"): ``betas`` then has shape (6, B), or ``materials`` names six walls (or one name for all) in
     ``material_table`` (``shoebox.load_materials``), read at the band centres.  The names are kept with the betas in ``to_dict``;
-    ``from_dict`` needs no material file."""
+    ``from_dict`` needs no material file.
+    ``air``: the air's amplitude attenuation in Np/m (``shoebox.air_absorption``), one number, or one per band with ``bands``;
+    ``add_emitters(patterns=...)`` gives emitters a first-order pattern each (DESIGN.md "Shoebox IRs: directional sources and
+    air").  Without either the state generates what it generated before, bit for bit."""
 
     name = "SHOEBOX"
 
     def __init__(self, room, betas=None, rt60: Optional[float] = None, ir_len: int = 4096, sample_rate: int = config.SAMPLE_RATE,
                  c: float = 343.0, max_order: Optional[int] = None, renderer=None, metadata: Optional[dict] = None, tail=None,
-                 bands=None, materials=None, material_table=None):
+                 bands=None, materials=None, material_table=None, air=None):
         from . import shoebox
 
         self.bands = shoebox.ShoeboxBands.from_dict(bands) if isinstance(bands, dict) else bands
@@ -345,13 +348,17 @@ class ShoeboxIRState:
         self.metadata = dict(metadata or {})
         self.microphones: "OrderedDict[str, MicArray]" = OrderedDict()
         self.emitters: "OrderedDict[str, np.ndarray]" = OrderedDict()
+        self._emitter_patterns: "OrderedDict[str, np.ndarray]" = OrderedDict()      # (n, 4) of the aliases that have patterns
         self._capsules: "OrderedDict[str, np.ndarray]" = OrderedDict()      # receiver positions (P, 3) of each microphone
         self._patterns: "OrderedDict[str, Optional[np.ndarray]]" = OrderedDict()     # None (omni) or (P, K, 4)
         self._irs = None
         # refuse bad room parameters here, not at the first simulate()
         inside = 0.5 * self.room[None, :]
         shoebox.check_arguments(self.room, self.betas, inside, inside + 0.25 * self.room[None, :], self.ir_len, self.sample_rate,
-                                self.c, self.max_order, self.tail, None, self.bands)
+                                self.c, self.max_order, self.tail, None, self.bands, None, air)
+        self.air = None      # a number, or with bands an array (B,)
+        if air is not None:
+            self.air = float(shoebox.check_air(air)[0]) if self.bands is None else shoebox.check_air(air, self.betas.shape[1])
 
     def add_microphone(self, alias: str, capsule_positions, patterns=None, capsule_names=None) -> MicArray:
         """``capsule_positions`` (C, 3).  ``patterns`` (C, 4): one first-order pattern ``(w, vx, vy, vz)`` per capsule in room axes
@@ -403,14 +410,19 @@ class ShoeboxIRState:
         self._irs = None
         return self.microphones[alias]
 
-    def add_emitters(self, positions, alias: Optional[str] = None) -> str:
-        """One IR column per row of ``positions`` (n, 3), appended in event order.  Returns the alias the rows are filed under."""
+    def add_emitters(self, positions, alias: Optional[str] = None, patterns=None) -> str:
+        """One IR column per row of ``positions`` (n, 3), appended in event order.  ``patterns`` (4,) or (n, 4): a first-order
+        pattern ``(w, vx, vy, vz)`` per emitter in room axes (``shoebox.first_order``, ``cardioid``); None: omnidirectional.
+        Returns the alias the rows are filed under."""
         from . import shoebox
 
         alias = alias if alias is not None else f"emitters{len(self.emitters):03d}"
         if alias in self.emitters:
             raise KeyError(f"Emitters with alias {alias} already exist")
-        self.emitters[alias] = shoebox._points(np.atleast_2d(np.asarray(positions, dtype=np.float64)), self.room, f"emitters {alias}")
+        points = shoebox._points(np.atleast_2d(np.asarray(positions, dtype=np.float64)), self.room, f"emitters {alias}")
+        if patterns is not None:
+            self._emitter_patterns[alias] = shoebox.check_source_patterns(patterns, len(points))
+        self.emitters[alias] = points
         self._irs = None
         return alias
 
@@ -421,6 +433,16 @@ class ShoeboxIRState:
     @property
     def emitter_positions(self) -> np.ndarray:
         return np.concatenate(list(self.emitters.values()), axis=0) if self.emitters else np.zeros((0, 3))
+
+    @property
+    def emitter_patterns(self) -> Optional[np.ndarray]:
+        """(N, 4) in the order of ``emitter_positions`` (omni rows for the aliases without patterns), or None when no emitter has one."""
+        from . import shoebox
+
+        if not self._emitter_patterns:
+            return None
+        return np.concatenate([self._emitter_patterns.get(alias, np.tile(shoebox.omni(), (len(points), 1)))
+                               for alias, points in self.emitters.items()], axis=0)
 
     def simulate(self) -> None:
         from . import shoebox, synthesize
@@ -436,7 +458,7 @@ class ShoeboxIRState:
         for alias, capsules in self._capsules.items():
             buf, strides, _ = shoebox.shoebox_irs_device(r, self.room, self.betas, sources, capsules, self.ir_len, self.sample_rate,
                                                          self.c, self.max_order, self.tail, 0, capsule_id0, self._patterns[alias],
-                                                         self.bands)
+                                                         self.bands, source_patterns=self.emitter_patterns, air=self.air)
             n_channels = self.microphones[alias].n_capsules
             irs[alias] = shoebox.DeviceIRTensor(r, buf, strides, (n_channels, len(sources), self.ir_len))
             capsule_id0 += n_channels
@@ -463,6 +485,10 @@ class ShoeboxIRState:
             d["shoebox"]["bands"] = self.bands.to_dict()
             if self.materials is not None:
                 d["shoebox"]["materials"] = list(self.materials)
+        if self.air is not None:
+            d["shoebox"]["air"] = self.air if self.bands is None else self.air.tolist()
+        if self._emitter_patterns:      # beside the emitters, whose entry keeps its form
+            d["shoebox"]["emitter_patterns"] = {k: v.tolist() for k, v in self._emitter_patterns.items()}
         d.update({k: v for k, v in self.metadata.items() if k not in d})
         return d
 
@@ -482,7 +508,7 @@ class ShoeboxIRState:
         keep = {k: v for k, v in state_d.items() if k not in ("backend", "sample_rate", "emitters", "microphones", "shoebox")}
         state = cls(box["room"], betas=box["betas"], ir_len=box["ir_len"], sample_rate=state_d.get("sample_rate") or config.SAMPLE_RATE,
                     c=box.get("c", 343.0), max_order=box.get("max_order"), renderer=renderer, metadata=keep, tail=box.get("tail"),
-                    bands=box.get("bands"))
+                    bands=box.get("bands"), air=box.get("air"))
         state.rt60 = box.get("rt60")
         state.materials = None if box.get("materials") is None else [str(v) for v in box["materials"]]
         for alias, md in state_d["microphones"].items():
@@ -495,8 +521,9 @@ class ShoeboxIRState:
                 patterns = patterns.reshape(len(positions), -1, 4)
             mic = state._add_receivers(alias, positions, patterns, md.get("capsule_names"), {})
             mic.metadata.update({k: v for k, v in md.items() if k not in ("n_capsules",)})
+        emitter_patterns = box.get("emitter_patterns") or {}
         for alias, rows in state_d["emitters"].items():
-            state.add_emitters(rows, alias)
+            state.add_emitters(rows, alias, emitter_patterns.get(alias))
         return state
 
 

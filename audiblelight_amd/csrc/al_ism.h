@@ -42,6 +42,18 @@
 //     gives zeros and not 0 * inf); the quad's later three samples are e(t) times powers of exp((ln_env[k + 1] - ln_env[k]) / 256),
 //     two exp per quad instead of four (a few float64 ulp from the definition, ten orders below the draw's tolerance).
 // Every output sample is written exactly once per call by exactly one of the two kernels; out is never read.
+//
+// THE SOURCE SIDE (al_ism_shoebox_src; DESIGN.md "Shoebox IRs: directional sources and air").  Source n may carry a first-order pattern
+// spat[n] = (w, vx, vy, vz) in room axes and the call an air coefficient m >= 0 in Np/m: the amplitude of an image becomes
+// a gs exp(-m d), gs = w + v . e, where e is the direction in which the ray LEAVES the real source: e_i = -(-1)^{q_i} R_i / d, since
+// each of the |q_i| reflections on axis i flips component i and the direct path leaves along -R / d.  The kernels with SRC set take
+// the source-aware variants (IsmOmniSrc, IsmDirSrc<K>; IsmBandsSrc<NB> in al_ism_bands.h), which differ from the plain ones in
+// `fill` alone: gs from the parities of im.qx / qy / qz and R / d (one division: w + (v . (sigma R)) / d), through a pointer that is
+// uniform over the wave (n comes from blockIdx), and -m d added to the exponent of the wall gain: no further exp.  Where an entry
+// carries gains, gs is written to the entry's `a` and read back behind a compiler barrier (ism_park), so that it is not live while
+// the exp is evaluated.  The omni pattern (or a null table) and m = 0 give gs = 1 + 0 / d = 1 and exp(x - 0) = exp(x): the bits of
+// the plain kernels.  With a tail every (row, source) pair reads a knot table of its own
+// (IsmTail::env_src_stride).  The instantiations without SRC are the kernels as they were.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -74,6 +86,7 @@ struct IsmTail {
   int32_t tail_blocks;    // workgroups of k_ism_tail per row
   uint32_t seed_lo, seed_hi, source_id0, capsule_id0;
   uint32_t env_stride;    // knots between the tables of two rows c (al_ism_shoebox_dir_tail: n_knots); 0: one table serves every row
+  uint32_t env_src_stride;   // knots between the tables of two sources n (al_ism_shoebox_src: n_knots); 0: one table serves every source
 };
 
 struct IsmJob {
@@ -84,6 +97,8 @@ struct IsmJob {
   int32_t beta_zero[6];
   double c, fs;
   IsmTail tail;
+  const double *source_patterns;   // (N, 4), device; null: omni sources.  Read by the SRC kernels only
+  double air;                      // m of al_ism_shoebox_src, Np/m
 };
 
 struct alignas(16) IsmEntry {
@@ -338,7 +353,46 @@ struct IsmOmni : IsmWalls {
   __device__ __forceinline__ void fill(Entry &e, const IsmImage &im) const { ism_fill_shape(e, im, amplitude(im)); }
 };
 
-template <bool TAIL>
+// the source of a workgroup: its pattern (null: omni) behind a pointer that is uniform over the wave, so it lives in scalar registers
+struct IsmSource {
+  const double *spat;
+  // gs = w + v . e, e_i = -(-1)^{q_i} R_i / d: the direction in which the image's ray leaves the real source
+  __device__ __forceinline__ double gain(const IsmImage &im) const {
+    if (!spat) return 1.0;
+    const double sx = (im.qx & 1) ? im.Rx : -im.Rx, sy = (im.qy & 1) ? im.Ry : -im.Ry, sz = (im.qz & 1) ? im.Rz : -im.Rz;   // e d
+    return spat[0] + (spat[1] * sx + spat[2] * sy + spat[3] * sz) / im.d;   // one division, not three
+  }
+  // the same from u = R / d, where a variant has formed it already
+  __device__ __forceinline__ double gain(const IsmImage &im, double ux, double uy, double uz) const {
+    if (!spat) return 1.0;
+    return spat[0] + (spat[1] * ((im.qx & 1) ? ux : -ux) + spat[2] * ((im.qy & 1) ? uy : -uy) + spat[3] * ((im.qz & 1) ? uz : -uz));
+  }
+};
+__device__ __forceinline__ IsmSource ism_source(const IsmJob &job, int n) {
+  return IsmSource{job.source_patterns ? job.source_patterns + 4 * (int64_t)n : nullptr};
+}
+// IsmWalls::amplitude through air of coefficient m: exp(sum k ln beta - m d) / (4 pi d)
+__device__ __forceinline__ double ism_air_amplitude(const IsmJob &job, const IsmImage &im) {
+  const double ln_xy = ism_log_gain(im.qx, job.ln_beta) + ism_log_gain(im.qy, job.ln_beta + 2), ln_z = ism_log_gain(im.qz, job.ln_beta + 4);
+  return exp((ln_xy + ln_z) - job.air * im.d) / (4.0 * M_PI * im.d);
+}
+// the list entry keeps a value that was written to it out of the registers until it is read back (a compiler barrier, no instruction)
+__device__ __forceinline__ void ism_park() { asm volatile("" ::: "memory"); }
+
+// IsmOmni with a source pattern and air
+struct IsmOmniSrc : IsmWalls {
+  static constexpr int NG = 0, LIST = ISM_LIST;
+  using Entry = IsmEntry;
+  IsmSource src;
+  __device__ __forceinline__ void fill(Entry &e, const IsmImage &im) const { ism_fill_shape(e, im, ism_air_amplitude(job, im) * src.gain(im)); }
+};
+
+// the knot table of row c and source n (both strides 0: the one table of al_ism_shoebox_tail)
+__device__ __forceinline__ const double *ism_tail_table(const IsmTail &tail, int c, int n) {
+  return tail.ln_env + ((int64_t)c * tail.env_stride + (int64_t)n * tail.env_src_stride);
+}
+
+template <bool TAIL, bool SRC = false>
 __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
   __shared__ IsmEntry list[ISM_LIST];
   __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];
@@ -358,7 +412,10 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
     return;
   }
   double acc[ISM_PER_LANE][1] = {};
-  ism_gather(job, IsmOmni{{job}}, n, cap, t_lo, t_hi, y_end, list, win_c, win_s, wave_total, acc);
+  if constexpr (SRC)
+    ism_gather(job, IsmOmniSrc{{job}, ism_source(job, n)}, n, cap, t_lo, t_hi, y_end, list, win_c, win_s, wave_total, acc);
+  else
+    ism_gather(job, IsmOmni{{job}}, n, cap, t_lo, t_hi, y_end, list, win_c, win_s, wave_total, acc);
 #pragma unroll
   for (int s = 0; s < ISM_PER_LANE; ++s) {
     const int ts = t + s * ISM_THREADS;
@@ -368,7 +425,8 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
       if (ts > job.tail.mix && ts < job.ir_len) {   // at or below M: w_e = 1, w_l = 0, the image sum as it is
         double w_e, w_l;
         ism_fade(job.tail, ts, w_e, w_l);
-        v = w_e * v + w_l * ism_envelope(job.tail.ln_env, ts) * (double)ism_tail_normal(job.tail, ts, n, cap);
+        const double *ln_env = SRC ? ism_tail_table(job.tail, cap, n) : job.tail.ln_env;   // SRC: a table per pair
+        v = w_e * v + w_l * ism_envelope(ln_env, ts) * (double)ism_tail_normal(job.tail, ts, n, cap);
       }
     }
     row[ts] = ts < job.ir_len ? (float)v : 0.f;
@@ -391,7 +449,7 @@ __global__ __launch_bounds__(ISM_TAIL_THREADS) void k_ism_tail(IsmJob job) {
     if (t < job.ir_len) {
       const float4 g = ism_tail_normal4(job.tail, t >> 2, n, cap);
       const int k = t / ISM_TILE, r = t % ISM_TILE;   // r + 3 < ISM_TILE: the quad lies in one knot interval
-      const double *ln_env = job.tail.ln_env + (int64_t)cap * job.tail.env_stride;   // the row's own table
+      const double *ln_env = ism_tail_table(job.tail, cap, n);   // the row's own table, the source's with al_ism_shoebox_src
       const double a = ln_env[k], b = ln_env[k + 1];
       const double inv = 1.0 / (double)ISM_TILE, p = (double)r * inv, step = (b - a) * inv;
       const double e0 = exp(r == 0 ? a : (1.0 - p) * a + p * b);
@@ -451,6 +509,8 @@ inline int ism_prepare(const double *sources, int32_t n_sources, const double *c
   job->c = c;
   job->fs = fs;
   job->tail = IsmTail{};
+  job->source_patterns = nullptr;
+  job->air = 0.0;
   return AL_OK;
 }
 
@@ -514,6 +574,11 @@ inline void launch_ism_shoebox_tail(const IsmJob &job, hipStream_t stream) {
 //   k_ism_tail  as it is, over the P K rows, each row reading its own knot table (IsmTail::env_stride).
 constexpr int ISM_MAX_CHANNELS = 4;
 constexpr int ISM_DIR_LIST = 96;
+#ifdef __HIP__   // hipcc; a host compiler does not know the attribute
+#define ISM_WAVES_PER_SIMD(n) __attribute__((amdgpu_waves_per_eu(n)))
+#else
+#define ISM_WAVES_PER_SIMD(n)
+#endif
 
 struct IsmDirJob {
   IsmJob base;              // n_capsules: the P K ROWS (what k_ism_tail and the id ranges count); capsules: the P positions
@@ -545,8 +610,28 @@ struct IsmDir : IsmWalls {
   }
 };
 
-template <int K, bool TAIL>
-__global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox_dir(IsmDirJob dj) {
+// IsmDir with a source pattern and air: the receiver's K gains as they are, the source's in the common amplitude
+template <int K>
+struct IsmDirSrc : IsmDir<K> {
+  using Entry = IsmDirEntry<K>;
+  IsmSource src;
+  __device__ __forceinline__ void fill(Entry &e, const IsmImage &im) const {
+    {
+      const double ux = im.Rx / im.d, uy = im.Ry / im.d, uz = im.Rz / im.d;
+#pragma unroll
+      for (int k = 0; k < K; ++k)   // IsmDir's expression: its bits
+        e.gain[k] = this->pat[4 * k] + (this->pat[4 * k + 1] * ux + this->pat[4 * k + 2] * uy + this->pat[4 * k + 3] * uz);
+      e.a = src.gain(im, ux, uy, uz);   // parked in the list and read back below: not live while the wall gain's exp is evaluated
+    }
+    ism_park();
+    ism_fill_shape(e, im, ism_air_amplitude(this->job, im) * e.a);
+  }
+};
+
+// (waves per SIMD: with SRC and K = 4 hipcc lands a few registers past the 128 of four waves and then stops trying, 166 VGPRs; asked
+// for four it finds 128 without scratch.  1 is the default: the other instantiations are compiled as before.)
+template <int K, bool TAIL, bool SRC = false>
+__global__ __launch_bounds__(ISM_THREADS) ISM_WAVES_PER_SIMD(SRC && K == 4 ? 4 : 1) void k_ism_shoebox_dir(IsmDirJob dj) {
   __shared__ IsmDirEntry<K> list[ISM_DIR_LIST];
   __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];
   __shared__ int wave_total[2];
@@ -567,7 +652,11 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox_dir(IsmDirJob dj) {
     return;
   }
   double acc[ISM_PER_LANE][K] = {};
-  ism_gather(job, IsmDir<K>{{job}, dj.patterns + (int64_t)pos * (4 * K)}, n, pos, t_lo, t_hi, y_end, list, win_c, win_s, wave_total, acc);
+  if constexpr (SRC)
+    ism_gather(job, IsmDirSrc<K>{{{job}, dj.patterns + (int64_t)pos * (4 * K)}, ism_source(job, n)}, n, pos, t_lo, t_hi, y_end, list, win_c,
+               win_s, wave_total, acc);
+  else
+    ism_gather(job, IsmDir<K>{{job}, dj.patterns + (int64_t)pos * (4 * K)}, n, pos, t_lo, t_hi, y_end, list, win_c, win_s, wave_total, acc);
 #pragma unroll
   for (int s = 0; s < ISM_PER_LANE; ++s) {
     const int ts = t + s * ISM_THREADS;
@@ -586,7 +675,8 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox_dir(IsmDirJob dj) {
       if constexpr (TAIL) {
         if (mixed) {
           const int c = pos * K + k;   // the row: its own noise stream and its own knot table
-          v = w_e * v + w_l * ism_envelope(job.tail.ln_env + (int64_t)c * job.tail.env_stride, ts) * (double)ism_tail_normal(job.tail, ts, n, c);
+          const double *ln_env = SRC ? ism_tail_table(job.tail, c, n) : job.tail.ln_env + (int64_t)c * job.tail.env_stride;
+          v = w_e * v + w_l * ism_envelope(ln_env, ts) * (double)ism_tail_normal(job.tail, ts, n, c);
         }
       }
       row[k * row_stride + ts] = ts < job.ir_len ? (float)v : 0.f;
@@ -617,14 +707,14 @@ inline int ism_dir_tail_prepare(int64_t mix, int64_t fade, uint64_t seed, int64_
   return AL_OK;
 }
 
-template <bool TAIL>
+template <bool TAIL, bool SRC = false>
 inline void launch_ism_dir_images(const IsmDirJob &dj, hipStream_t stream) {
   const dim3 grid((unsigned)((int64_t)dj.base.n_tiles * dj.base.n_sources * dj.n_positions)), block(ISM_THREADS);
   switch (dj.n_channels) {
-    case 1: hipLaunchKernelGGL((k_ism_shoebox_dir<1, TAIL>), grid, block, 0, stream, dj); break;
-    case 2: hipLaunchKernelGGL((k_ism_shoebox_dir<2, TAIL>), grid, block, 0, stream, dj); break;
-    case 3: hipLaunchKernelGGL((k_ism_shoebox_dir<3, TAIL>), grid, block, 0, stream, dj); break;
-    default: hipLaunchKernelGGL((k_ism_shoebox_dir<4, TAIL>), grid, block, 0, stream, dj); break;
+    case 1: hipLaunchKernelGGL((k_ism_shoebox_dir<1, TAIL, SRC>), grid, block, 0, stream, dj); break;
+    case 2: hipLaunchKernelGGL((k_ism_shoebox_dir<2, TAIL, SRC>), grid, block, 0, stream, dj); break;
+    case 3: hipLaunchKernelGGL((k_ism_shoebox_dir<3, TAIL, SRC>), grid, block, 0, stream, dj); break;
+    default: hipLaunchKernelGGL((k_ism_shoebox_dir<4, TAIL, SRC>), grid, block, 0, stream, dj); break;
   }
 }
 
@@ -636,6 +726,59 @@ inline void launch_ism_shoebox_dir_tail(const IsmDirJob &dj, hipStream_t stream)
   if (job.tail.tail_blocks > 0)
     hipLaunchKernelGGL(k_ism_tail, dim3((unsigned)((int64_t)job.tail.tail_blocks * job.n_sources * job.n_capsules)), dim3(ISM_TAIL_THREADS),
                        0, stream, job);
+}
+
+// SOURCE PATTERNS AND AIR (al_ism_shoebox_src).  The source side of a job that ism_prepare (or ism_dir_prepare) has filled
+inline int ism_source_prepare(const double *source_patterns, double air, IsmJob *job) {
+  if (!isfinite(air) || !(air >= 0.0)) return fail(AL_E_BADARG, "al_ism_shoebox_src: air must be finite and >= 0 (Np/m)");
+  job->source_patterns = source_patterns;
+  job->air = air;
+  return AL_OK;
+}
+
+// al_ism_shoebox_src's arguments as a directional job; patterns == nullptr (with n_channels == 1): omni capsules, dj->patterns null.
+// mix < 0: no tail, and the tail's arguments are not looked at.  ln_env: (rows, N, n_knots)
+inline int ism_src_prepare(const double *sources, int32_t n_sources, const double *source_patterns, const double *receivers,
+                           int32_t n_receivers, const double *patterns, int32_t n_channels, const double *L, const double *beta,
+                           double air, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade,
+                           uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, float *out,
+                           IsmDirJob *dj) {
+  if (!patterns) {
+    if (n_channels != 1) return fail(AL_E_BADARG, "al_ism_shoebox_src: a null pattern table (omni capsules) takes n_channels == 1");
+    if (int rc = ism_prepare(sources, n_sources, receivers, n_receivers, L, beta, c, fs, max_order, ir_len, pitch, out, &dj->base)) return rc;
+    dj->patterns = nullptr;
+    dj->n_positions = n_receivers;
+    dj->n_channels = 1;
+  } else if (int rc = ism_dir_prepare(sources, n_sources, receivers, n_receivers, patterns, n_channels, L, beta, c, fs, max_order, ir_len,
+                                      pitch, out, dj)) {
+    return rc;
+  }
+  if (int rc = ism_source_prepare(source_patterns, air, &dj->base)) return rc;
+  if (mix >= 0) {
+    if (int rc = ism_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, &dj->base)) return rc;
+    dj->base.tail.env_src_stride = (uint32_t)n_knots;
+    if ((int64_t)n_knots * n_sources > 0xffffffffll) return fail(AL_E_BADARG, "al_ism_shoebox_src: n_knots x n_sources must be below 2^32");
+    dj->base.tail.env_stride = (uint32_t)((int64_t)n_knots * n_sources);
+  }
+  return AL_OK;
+}
+
+inline void launch_ism_shoebox_src(const IsmDirJob &dj, bool with_tail, hipStream_t stream) {
+  const IsmJob &job = dj.base;
+  const int64_t pairs = (int64_t)job.n_sources * job.n_capsules;
+  if (!dj.patterns) {
+    const dim3 grid((unsigned)(job.n_tiles * pairs)), block(ISM_THREADS);
+    if (with_tail)
+      hipLaunchKernelGGL((k_ism_shoebox<true, true>), grid, block, 0, stream, job);
+    else
+      hipLaunchKernelGGL((k_ism_shoebox<false, true>), grid, block, 0, stream, job);
+  } else if (with_tail) {
+    launch_ism_dir_images<true, true>(dj, stream);
+  } else {
+    launch_ism_dir_images<false, true>(dj, stream);
+  }
+  if (with_tail && job.tail.tail_blocks > 0)
+    hipLaunchKernelGGL(k_ism_tail, dim3((unsigned)(job.tail.tail_blocks * pairs)), dim3(ISM_TAIL_THREADS), 0, stream, job);
 }
 
 }  // namespace al

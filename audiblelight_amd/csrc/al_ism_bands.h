@@ -37,6 +37,10 @@
 // The entry walks the pairs in PASSES of workspace_bytes / bytes_per_pair pairs, gather then combine, in order on the one stream: the
 // workspace is reused in stream order, nothing is allocated and nothing synchronises.  A row's bits do not depend on the pass it is
 // generated in: both kernels index the workspace by the pair's place in its pass only to find their own rows.
+// SOURCE PATTERNS AND AIR WITH BANDS (al_ism_shoebox_bands_src; al_ism.h "THE SOURCE SIDE").  k_ism_bands<NB, true> takes IsmBandsSrc<NB>:
+// the source gain gs goes into the rigid-wall amplitude 1 / (4 pi d), and band b's gain becomes exp(sum k ln beta_b - m_b d) with
+// its own air coefficient m_b (IsmBandJob::air).  With a tail the knot tables are (N, B, n_knots): a table per (source, band),
+// found through IsmTail::env_src_stride by k_ism_band_combine<true> and k_ism_band_tail.
 #pragma once
 #include "al_ism.h"
 
@@ -66,6 +70,7 @@ struct IsmBandJob {
   int32_t band0;                     // first band of this launch of k_ism_bands
   int64_t pair0;                     // first pair of the pass
   int64_t pairs_per_pass;
+  double air[ISM_MAX_BANDS];         // m_b of al_ism_shoebox_bands_src, Np/m (read by k_ism_bands<NB, true> only)
 };
 
 struct alignas(16) IsmPsi {
@@ -97,7 +102,26 @@ struct IsmBands {
   }
 };
 
+// IsmBands with a source pattern and an air coefficient per band
 template <int NB>
+struct IsmBandsSrc : IsmBands<NB> {
+  using Entry = IsmDirEntry<NB>;
+  IsmSource src;
+  __device__ __forceinline__ void fill(Entry &e, const IsmImage &im) const {
+    const IsmBandJob &bj = this->bj;
+    e.a = src.gain(im);   // parked in the list and read back below: not live while the NB exp are evaluated
+    ism_park();
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      const double *lb = bj.ln_beta[bj.band0 + k];
+      const double ln_xy = ism_log_gain(im.qx, lb) + ism_log_gain(im.qy, lb + 2), ln_z = ism_log_gain(im.qz, lb + 4);
+      e.gain[k] = ((im.alive >> k) & 1u) ? exp((ln_xy + ln_z) - bj.air[bj.band0 + k] * im.d) : 0.0;
+    }
+    ism_fill_shape(e, im, 1.0 / (4.0 * M_PI * im.d) * e.a);
+  }
+};
+
+template <int NB, bool SRC = false>
 __global__ __launch_bounds__(ISM_THREADS) void k_ism_bands(IsmBandJob bj) {
   __shared__ IsmDirEntry<NB> list[ISM_DIR_LIST];
   __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];
@@ -119,7 +143,10 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_bands(IsmBandJob bj) {
     return;
   }
   double acc[ISM_PER_LANE][NB] = {};
-  ism_gather(job, IsmBands<NB>{bj}, n, cap, s_lo, t_hi, s_end, list, win_c, win_s, wave_total, acc);
+  if constexpr (SRC)
+    ism_gather(job, IsmBandsSrc<NB>{{bj}, ism_source(job, n)}, n, cap, s_lo, t_hi, s_end, list, win_c, win_s, wave_total, acc);
+  else
+    ism_gather(job, IsmBands<NB>{bj}, n, cap, s_lo, t_hi, s_end, list, win_c, win_s, wave_total, acc);
 #pragma unroll
   for (int s = 0; s < ISM_PER_LANE; ++s)   // w + s * ISM_THREADS < W: the tile lies inside the row
 #pragma unroll
@@ -191,7 +218,7 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_band_combine(IsmBandJob bj)
     }
     if constexpr (TAIL) {
       if (noisy) {
-        const double *ln_env = job.tail.ln_env + (int64_t)b * job.tail.env_stride;
+        const double *ln_env = ism_tail_table(job.tail, b, n);   // band b's table, the source's with al_ism_shoebox_bands_src
 #pragma unroll
         for (int s = 0; s < ISM_PER_LANE; ++s) {
           const int ts = t + s * ISM_THREADS;
@@ -253,10 +280,11 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_band_tail(IsmBandJob bj) {
     }
   }
   // psi of one knot into half `which` of the double2 table
+  const double *ln_env = ism_tail_table(job.tail, 0, n);   // band 0's table, the source's with al_ism_shoebox_bands_src
   auto form = [&](int knot, int which) {
     double e[ISM_MAX_BANDS];   // unrolled to the full count: registers, no indexed array
 #pragma unroll
-    for (int b = 0; b < ISM_MAX_BANDS; ++b) e[b] = b < bj.n_bands ? exp(job.tail.ln_env[(int64_t)b * job.tail.env_stride + knot]) : 0.0;
+    for (int b = 0; b < ISM_MAX_BANDS; ++b) e[b] = b < bj.n_bands ? exp(ln_env[(int64_t)b * job.tail.env_stride + knot]) : 0.0;
     for (int m = lane; m < n_taps; m += ISM_THREADS) {
       double v = 0.0;
 #pragma unroll
@@ -370,6 +398,7 @@ inline int ism_bands_prepare(const double *sources, int32_t n_sources, const dou
   bj->band0 = 0;
   bj->pair0 = 0;
   bj->band_tail_blocks = 0;
+  for (int b = 0; b < ISM_MAX_BANDS; ++b) bj->air[b] = 0.0;
   if (workspace_bytes < ism_bands_layout(bj, ir_len, workspace_bytes) && !with_tail)   // with a tail: ism_bands_tail_prepare, against the shorter row
     return fail(AL_E_BADARG, "al_ism_shoebox_bands: workspace smaller than al_ism_shoebox_bands_workspace_bytes (one pair)");
   return AL_OK;
@@ -393,12 +422,12 @@ inline int ism_bands_tail_prepare(int64_t mix, int64_t fade, uint64_t seed, int6
   return AL_OK;
 }
 
-template <int NB>
+template <int NB, bool SRC>
 inline void launch_ism_bands_group(const IsmBandJob &bj, int64_t pairs, hipStream_t stream) {
-  hipLaunchKernelGGL((k_ism_bands<NB>), dim3((unsigned)(pairs * bj.n_ws_tiles)), dim3(ISM_THREADS), 0, stream, bj);
+  hipLaunchKernelGGL((k_ism_bands<NB, SRC>), dim3((unsigned)(pairs * bj.n_ws_tiles)), dim3(ISM_THREADS), 0, stream, bj);
 }
 
-template <bool TAIL>
+template <bool TAIL, bool SRC = false>
 inline void launch_ism_bands_passes(const IsmBandJob &job, hipStream_t stream) {
   const int64_t pairs = (int64_t)job.base.n_sources * job.base.n_capsules;
   IsmBandJob bj = job;
@@ -408,10 +437,10 @@ inline void launch_ism_bands_passes(const IsmBandJob &job, hipStream_t stream) {
     for (int band0 = 0; band0 < job.n_bands; band0 += ISM_BAND_GROUP) {
       bj.band0 = band0;
       switch (job.n_bands - band0 < ISM_BAND_GROUP ? job.n_bands - band0 : ISM_BAND_GROUP) {
-        case 1: launch_ism_bands_group<1>(bj, in_pass, stream); break;
-        case 2: launch_ism_bands_group<2>(bj, in_pass, stream); break;
-        case 3: launch_ism_bands_group<3>(bj, in_pass, stream); break;
-        default: launch_ism_bands_group<4>(bj, in_pass, stream); break;
+        case 1: launch_ism_bands_group<1, SRC>(bj, in_pass, stream); break;
+        case 2: launch_ism_bands_group<2, SRC>(bj, in_pass, stream); break;
+        case 3: launch_ism_bands_group<3, SRC>(bj, in_pass, stream); break;
+        default: launch_ism_bands_group<4, SRC>(bj, in_pass, stream); break;
       }
     }
     bj.band0 = 0;
@@ -421,8 +450,8 @@ inline void launch_ism_bands_passes(const IsmBandJob &job, hipStream_t stream) {
 
 inline void launch_ism_shoebox_bands(const IsmBandJob &job, hipStream_t stream) { launch_ism_bands_passes<false>(job, stream); }
 
-inline void launch_ism_shoebox_bands_tail(const IsmBandJob &job, hipStream_t stream) {
-  launch_ism_bands_passes<true>(job, stream);
+// the samples past the split of every row of a job with a tail
+inline void launch_ism_band_tail(const IsmBandJob &job, hipStream_t stream) {
   if (job.band_tail_blocks > 0) {
     const dim3 grid((unsigned)((int64_t)job.band_tail_blocks * job.base.n_sources * job.base.n_capsules)), block(ISM_THREADS);
     if (job.half <= 256)
@@ -431,6 +460,33 @@ inline void launch_ism_shoebox_bands_tail(const IsmBandJob &job, hipStream_t str
       hipLaunchKernelGGL(k_ism_band_tail<512>, grid, block, 0, stream, job);
     else
       hipLaunchKernelGGL(k_ism_band_tail<1024>, grid, block, 0, stream, job);
+  }
+}
+
+inline void launch_ism_shoebox_bands_tail(const IsmBandJob &job, hipStream_t stream) {
+  launch_ism_bands_passes<true>(job, stream);
+  launch_ism_band_tail(job, stream);
+}
+
+// al_ism_shoebox_bands_src's further arguments into a job ism_bands_prepare (and, with mix >= 0, ism_bands_tail_prepare) has filled:
+// the source patterns, the air coefficient of every band, a knot table per (source, band)
+inline int ism_bands_source_prepare(const double *source_patterns, const double *air, bool with_tail, IsmBandJob *bj) {
+  if (!air) return fail(AL_E_BADARG, "al_ism_shoebox_bands_src: null air table");
+  for (int b = 0; b < bj->n_bands; ++b) {
+    if (int rc = ism_source_prepare(source_patterns, air[b], &bj->base)) return rc;
+    bj->air[b] = air[b];
+  }
+  bj->base.air = 0.0;   // the bands carry their own
+  if (with_tail) bj->base.tail.env_src_stride = bj->base.tail.env_stride * (uint32_t)bj->n_bands;   // (N, B, n_knots): at most 8 x 2^23 knots
+  return AL_OK;
+}
+
+inline void launch_ism_shoebox_bands_src(const IsmBandJob &job, bool with_tail, hipStream_t stream) {
+  if (with_tail) {
+    launch_ism_bands_passes<true, true>(job, stream);
+    launch_ism_band_tail(job, stream);
+  } else {
+    launch_ism_bands_passes<false, true>(job, stream);
   }
 }
 

@@ -680,6 +680,36 @@ int al_ism_shoebox_bands_tail(const double *sources, int32_t n_sources, const do
   return check_launch("k_ism_band_tail");
 }
 
+// ---- the same with directional sources and air absorption: DESIGN.md "Shoebox IRs: directional sources and air"
+int al_ism_shoebox_src(const double *sources, int32_t n_sources, const double *source_patterns, const double *receivers,
+                       int32_t n_receivers, const double *patterns, int32_t n_channels, const double *L, const double *beta, double air,
+                       double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade, uint64_t seed,
+                       int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, float *out, al_stream_t stream) {
+  al::IsmDirJob job;
+  if (int rc = al::ism_src_prepare(sources, n_sources, source_patterns, receivers, n_receivers, patterns, n_channels, L, beta, air, c, fs,
+                                   max_order, ir_len, pitch, mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, out, &job))
+    return rc;
+  al::launch_ism_shoebox_src(job, mix >= 0, (hipStream_t)stream);
+  return check_launch("k_ism_shoebox_src");
+}
+
+int al_ism_shoebox_bands_src(const double *sources, int32_t n_sources, const double *source_patterns, const double *capsules,
+                             int32_t n_capsules, const double *L, const double *beta, int32_t n_bands, const double *filters,
+                             int32_t half, const double *air, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch,
+                             int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env,
+                             int32_t n_knots, void *workspace, int64_t workspace_bytes, float *out, al_stream_t stream) {
+  al::IsmBandJob job;
+  const bool with_tail = mix >= 0;
+  if (int rc = al::ism_bands_prepare(sources, n_sources, capsules, n_capsules, L, beta, n_bands, filters, half, c, fs, max_order, ir_len,
+                                     pitch, workspace, workspace_bytes, out, &job, with_tail))
+    return rc;
+  if (with_tail)
+    if (int rc = al::ism_bands_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, workspace_bytes, &job)) return rc;
+  if (int rc = al::ism_bands_source_prepare(source_patterns, air, with_tail, &job)) return rc;
+  al::launch_ism_shoebox_bands_src(job, with_tail, (hipStream_t)stream);
+  return check_launch("k_ism_bands_src");
+}
+
 int al_resample_poly(const float *x, int32_t rows, int64_t n_in, const float *taps, int32_t half_len, int32_t up, int32_t down,
                      float *out, int64_t n_out, int64_t out_pitch, al_stream_t stream) {
   if (!x || !taps || !out || rows <= 0 || rows > 65535 || n_in <= 0 || half_len < 0 || up <= 0 || down <= 0 || n_out <= 0 ||

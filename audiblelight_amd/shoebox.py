@@ -4,12 +4,16 @@
 born in HBM in the layout ``Renderer.prepare(plan, clips, irs, ir_strides)`` reads and never crosses PCIe.  ``DeviceIRTensor`` wraps
 it as a lazy array: the render path takes its buffer (``result()``), a host consumer downloads it once.  Point capsules,
 omnidirectional or with first-order patterns (``patterns=``: ``omni``, ``first_order``, ``cardioid``, ``foa_patterns``; the channels
-of a point share one image search, ``al_ism_shoebox_dir``), no air absorption.  Walls are one broadband coefficient each, or, with
+of a point share one image search, ``al_ism_shoebox_dir``).  Walls are one broadband coefficient each, or, with
 ``bands=`` (a ``ShoeboxBands``), a column of coefficients per octave band, from a material table if wanted (``load_materials``,
 ``material_betas``, ``al_ism_shoebox_bands``; DESIGN.md "Shoebox IRs: frequency-dependent walls").  Without ``max_order`` the cost grows as
 ``ir_len**3 / (Lx * Ly * Lz)`` per (capsule, source) pair; with a ``ShoeboxTail`` the exact image sum ends a fade after the mixing
 time and the row continues as seeded Gaussian noise under an envelope that matches the image field in level and decay
 (``al_ism_shoebox_tail``, ``tail_envelope``; DESIGN.md "Shoebox IRs: the diffuse tail"), so a row of seconds costs a write of its bytes.
+Sources are omnidirectional, or carry a first-order pattern each (``source_patterns=``, the same ``(w, vx, vy, vz)`` as a capsule's,
+applied to the direction in which the image's ray leaves the source), and the air may absorb (``air=`` in Np/m, one coefficient or one
+per band; ``air_absorption`` gives ISO 9613-1's): ``al_ism_shoebox_src``, ``al_ism_shoebox_bands_src``; DESIGN.md "Shoebox IRs:
+directional sources and air".
 """
 from __future__ import annotations
 
@@ -202,6 +206,81 @@ def check_patterns(patterns, n_positions: int) -> np.ndarray:
     return patterns
 
 
+def check_source_patterns(source_patterns, n_sources: int) -> np.ndarray:
+    """The source patterns of ``shoebox_irs_device`` as float64 ``(n_sources, 4)``: one pattern ``(4,)`` for every source or a row
+    per source, finite, none all zero (ValueError)."""
+    try:
+        source_patterns = np.asarray(source_patterns, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("source_patterns must be an array of shape (4,) or (sources, 4)")
+    if source_patterns.shape == (4,):
+        source_patterns = np.tile(source_patterns, (n_sources, 1))
+    if source_patterns.shape != (n_sources, 4):
+        raise ValueError(f"source_patterns must have shape (4,) or ({n_sources} sources, 4), not {source_patterns.shape}")
+    if not np.all(np.isfinite(source_patterns)):
+        raise ValueError("source_patterns must be finite")
+    if np.any(np.all(source_patterns == 0.0, axis=1)):
+        raise ValueError("a source's pattern must not be all zero")
+    return np.ascontiguousarray(source_patterns)
+
+
+def check_air(air, n_bands: Optional[int] = None) -> np.ndarray:
+    """The air coefficients of ``shoebox_irs_device`` in Np/m as a float64 array: ``(1,)`` without bands (``n_bands`` None), else
+    ``(n_bands,)`` from a number or a vector of that length; finite and >= 0 (ValueError)."""
+    try:
+        air = np.asarray(air, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("air must be a number (Np/m), or one per band")
+    if n_bands is None:
+        if air.ndim != 0:
+            raise ValueError("without bands air is one number (Np/m)")
+        air = air.reshape(1)
+    elif air.ndim == 0:
+        air = np.full(n_bands, float(air))
+    elif air.shape != (n_bands,):
+        raise ValueError(f"with {n_bands} bands air is one number or has shape ({n_bands},), not {air.shape}")
+    if not np.all(np.isfinite(air)) or np.any(air < 0.0):
+        raise ValueError("air must be finite and >= 0 (Np/m)")
+    return np.ascontiguousarray(air)
+
+
+def air_absorption(freqs, temperature_c: float = 20.0, humidity: float = 50.0, pressure_pa: float = 101325.0) -> np.ndarray:
+    """The amplitude attenuation of air in Np/m at the frequencies ``freqs`` (Hz) by ISO 9613-1, at ``temperature_c`` degrees
+    Celsius, ``humidity`` per cent relative humidity and ``pressure_pa`` pascal: what ``air=`` of ``shoebox_irs_device`` takes.
+
+    With ``T = temperature_c + 273.15``, ``T0 = 293.15``, ``T01 = 273.16``, ``pr = 101325`` and ``pa = pressure_pa``:
+    ``psat / pr = 10^(-6.8346 (T01 / T)^1.261 + 4.6151)``, ``h = humidity (psat / pr) / (pa / pr)``,
+    ``frO = (pa / pr) (24 + 4.04e4 h (0.02 + h) / (0.391 + h))``,
+    ``frN = (pa / pr) (T / T0)^(-1/2) (9 + 280 h exp(-4.170 ((T / T0)^(-1/3) - 1)))``,
+    ``alpha = 8.686 f^2 (1.84e-11 (pr / pa) (T / T0)^(1/2) + (T / T0)^(-5/2) (0.01275 exp(-2239.1 / T) / (frO + f^2 / frO)
+    + 0.1068 exp(-3352 / T) / (frN + f^2 / frN)))`` in dB/m and ``m = alpha ln(10) / 20``.
+
+    A band of ``ShoeboxBands`` holds everything between its neighbours' centres, and the TOP band everything above its centre:
+    the attenuation grows about as ``f^2``, so a coefficient read at the top band's centre understates what that band loses."""
+    try:
+        f = np.asarray(freqs, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("freqs must be numbers (Hz)")
+    if not np.all(np.isfinite(f)) or np.any(f < 0.0):
+        raise ValueError("freqs must be finite and >= 0 (Hz)")
+    for name, v in (("temperature_c", temperature_c), ("humidity", humidity), ("pressure_pa", pressure_pa)):
+        if not (isinstance(v, _REAL) and not isinstance(v, bool) and np.isfinite(v)):
+            raise ValueError(f"{name} must be a finite number")
+    T = float(temperature_c) + 273.15
+    if not (T > 0.0 and 0.0 <= humidity <= 100.0 and pressure_pa > 0.0):
+        raise ValueError("temperature above absolute zero, humidity in 0 .. 100 per cent, pressure > 0")
+    T0, T01, pr = 293.15, 273.16, 101325.0
+    pa_r, Tr = float(pressure_pa) / pr, T / T0
+    psat_r = 10.0 ** (-6.8346 * (T01 / T) ** 1.261 + 4.6151)
+    h = float(humidity) * psat_r / pa_r
+    frO = pa_r * (24.0 + 4.04e4 * h * (0.02 + h) / (0.391 + h))
+    frN = pa_r * Tr ** -0.5 * (9.0 + 280.0 * h * np.exp(-4.170 * (Tr ** (-1.0 / 3.0) - 1.0)))
+    f2 = f * f
+    alpha_db = 8.686 * f2 * (1.84e-11 / pa_r * np.sqrt(Tr) + Tr ** -2.5 * (0.01275 * np.exp(-2239.1 / T) / (frO + f2 / frO)
+                                                                         + 0.1068 * np.exp(-3352.0 / T) / (frN + f2 / frN)))
+    return alpha_db * (np.log(10.0) / 20.0)
+
+
 def _centres(centres, sample_rate: float) -> np.ndarray:
     try:
         centres = np.asarray(centres, dtype=np.float64)
@@ -317,9 +396,20 @@ def check_bands(bands, betas, sample_rate: float) -> np.ndarray:
     return betas
 
 
-def tail_energy_law(room, betas, sample_rate: float, c: float = SPEED_OF_SOUND, pattern=None):
+def _direction_weight(pattern, mu, phi, s):
+    """ln of the octant average's weight of a first-order pattern at the quadrature nodes: ``w^2 + vx^2 s^2 cos^2 phi + vy^2 s^2
+    sin^2 phi + vz^2 mu^2`` (the omni pattern: ln 1 = 0)."""
+    pw, vx, vy, vz = _pattern(pattern)
+    weight = (pw * pw + (vx * vx * np.cos(phi)[None, :] ** 2 + vy * vy * np.sin(phi)[None, :] ** 2) * (s * s)[:, None]
+              + vz * vz * (mu * mu)[:, None])
+    with np.errstate(divide="ignore"):
+        return np.log(weight)
+
+
+def tail_energy_law(room, betas, sample_rate: float, c: float = SPEED_OF_SOUND, pattern=None, source_pattern=None, air: float = 0.0):
     """``tau -> ln(sigma^2 D(tau))``, ``tau`` in seconds: the expected squared sample of the image-source field (``tail_envelope``
-    states the law and the quadrature rule), seen through ``pattern`` (None: omni)."""
+    states the law and the quadrature rule), seen through ``pattern`` (None: omni), sent through ``source_pattern`` (None: omni)
+    and through air of ``air`` Np/m."""
     room = _room(room)
     betas = np.ascontiguousarray(betas, dtype=np.float64)
     if betas.shape != (6,) or not np.all(np.isfinite(betas)) or np.any(betas <= 0.0) or np.any(betas > 1.0):
@@ -336,22 +426,23 @@ def tail_energy_law(room, betas, sample_rate: float, c: float = SPEED_OF_SOUND, 
     rate = (lam[0] * np.cos(phi)[None, :] + lam[1] * np.sin(phi)[None, :]) * s[:, None] + lam[2] * mu[:, None]     # (mu, phi)
     ln_w = np.log(w_mu[:, None] * w_phi[None, :]) + np.log(2.0 / np.pi)
     if pattern is not None:     # the direction weight of a first-order pattern, inside the log-sum (omni: ln 1 = 0, today's bits)
-        pw, vx, vy, vz = _pattern(pattern)
-        weight = (pw * pw + (vx * vx * np.cos(phi)[None, :] ** 2 + vy * vy * np.sin(phi)[None, :] ** 2) * (s * s)[:, None]
-                  + vz * vz * (mu * mu)[:, None])
-        with np.errstate(divide="ignore"):
-            ln_w = ln_w + np.log(weight)
+        ln_w = ln_w + _direction_weight(pattern, mu, phi, s)
+    if source_pattern is not None:     # the source's weight multiplies the receiver's: the same quadratic form (tail_envelope)
+        ln_w = ln_w + _direction_weight(source_pattern, mu, phi, s)
+    if not (isinstance(air, _REAL) and not isinstance(air, bool) and np.isfinite(air) and air >= 0.0):
+        raise ValueError("air must be a finite number >= 0 (Np/m)")
+    air = float(air)
 
     def ln_energy(tau: float) -> float:
         e = ln_w - c * float(tau) * rate
         top = e.max()
-        return float(ln_sigma2 + top + np.log(np.exp(e - top).sum()))
+        return float(ln_sigma2 + top + np.log(np.exp(e - top).sum())) - 2.0 * air * c * float(tau)
 
     return ln_energy
 
 
 def tail_envelope(room, betas, ir_len: int, sample_rate: float, mix: int, c: float = SPEED_OF_SOUND,
-                  rt60: Optional[float] = None, pattern=None) -> np.ndarray:
+                  rt60: Optional[float] = None, pattern=None, source_pattern=None, air: float = 0.0) -> np.ndarray:
     """The float64 table ``ln_env`` of ``n_knots_of(ir_len)`` log-amplitude knots of the tail, knot ``k`` at sample ``256 k``: THE
     TABLE THIS RETURNS IS THE DEFINITION the kernel is held to.
 
@@ -375,8 +466,16 @@ def tail_envelope(room, betas, ir_len: int, sample_rate: float, mix: int, c: flo
     ``pattern = (w, vx, vy, vz)`` (a channel of a directional receiver; None: omni): the image field is symmetric under a sign flip
     of each axis, so the cross terms of ``(w + v . n)^2`` average out and the integrand carries the weight
     ``w^2 + vx^2 s^2 cos^2 phi + vy^2 s^2 sin^2 phi + vz^2 mu^2``, inside the same rule; ``rt60`` level-matches with the weighted
-    law.  The omni pattern gives the bits of None."""
-    ln_energy = tail_energy_law(room, betas, sample_rate, c, pattern)
+    law.  The omni pattern gives the bits of None.
+
+    ``source_pattern = (w, vx, vy, vz)`` (None: omni): the ray of an image in direction ``u`` left the source along ``e``,
+    ``e_i = -sigma_i u_i`` with ``sigma_i`` the parity sign of the image on axis ``i``.  To the order the law works at the parity is
+    independent of the sign of ``u_i``, so ``E[gs^2 gr^2] = E[gs^2] E[gr^2]`` with every cross term gone: the integrand's weight is
+    the PRODUCT of the two quadratic forms, the source's over the same ``(s cos phi, s sin phi, mu)``.  ``air = m`` in Np/m: an image at
+    ``d = c tau`` has lost ``exp(-2 m c tau)`` of its energy, which leaves the integral: ``ln_env[k] -= m c 256 k / fs`` with
+    ``rt60`` None.  With ``rt60`` the level is matched at the mixing sample with both factors in and the requested exponential is
+    kept as it is: a measured reverberation time already contains the air.  None / omni / 0 give today's bits."""
+    ln_energy = tail_energy_law(room, betas, sample_rate, c, pattern, source_pattern, air)
     if int(ir_len) != ir_len or ir_len < 1 or int(mix) != mix or mix < 0:
         raise ValueError("ir_len must be an integer >= 1 and mix an integer >= 0")
     if rt60 is not None and not (np.isfinite(rt60) and rt60 > 0.0):
@@ -389,9 +488,10 @@ def tail_envelope(room, betas, ir_len: int, sample_rate: float, mix: int, c: flo
 
 
 def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED_OF_SOUND, max_order=None, tail=None, patterns=None,
-                    bands=None):
+                    bands=None, source_patterns=None, air=None):
     """The host-side validation of ``shoebox_irs_device`` (ValueError); returns the arguments as the call takes them (the pattern
-    table through ``check_patterns``).  With ``bands`` (a ``ShoeboxBands``) ``betas`` is ``(6, B)``."""
+    table through ``check_patterns``, the source patterns through ``check_source_patterns``, the air through ``check_air``).  With
+    ``bands`` (a ``ShoeboxBands``) ``betas`` is ``(6, B)``."""
     room = _room(room)
     if bands is not None:
         if not (np.isfinite(sample_rate) and sample_rate > 0.0):
@@ -416,6 +516,10 @@ def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED
         _check_tail(tail, betas)
     if patterns is not None:
         check_patterns(patterns, len(capsules))
+    if source_patterns is not None:
+        check_source_patterns(source_patterns, len(sources))
+    if air is not None:
+        check_air(air, None if bands is None else betas.shape[1])
     gap = np.sqrt(((capsules[:, None, :] - sources[None, :, :]) ** 2).sum(axis=2))
     if gap.min() < MIN_DISTANCE:
         raise ValueError(f"every source must be at least {MIN_DISTANCE} m from every capsule (closest: {gap.min():.4g} m)")
@@ -425,7 +529,7 @@ def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED
 def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sample_rate: float, c: float = SPEED_OF_SOUND,
                        max_order: Optional[int] = None, tail: Optional[ShoeboxTail] = None, source_id0: int = 0,
                        capsule_id0: int = 0, patterns=None, bands: Optional[ShoeboxBands] = None,
-                       workspace_cap: int = BAND_WORKSPACE_CAP):
+                       workspace_cap: int = BAND_WORKSPACE_CAP, source_patterns=None, air=None):
     """The IRs of ``sources`` (N, 3) at ``capsules`` (C, 3) in the room ``(Lx, Ly, Lz)`` with wall reflection coefficients
     ``betas = (x0, x1, y0, y1, z0, z1)``: ``(device buffer, (stride_c, stride_n), ir_len)`` as ``ingest.pack_ragged_irs`` returns
     it, enqueued on the renderer's stream.  The two coordinate tables are all that is uploaded.  With ``tail`` (a ``ShoeboxTail``)
@@ -444,9 +548,16 @@ def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sa
     uploaded (``band_filters``) and a float64 workspace for the band sums is allocated for the call: what all pairs need, at most
     ``workspace_cap`` bytes and at least one pair's; the entry walks the pairs in passes of what it holds, and the rows' bits do
     not depend on it.  With ``tail`` every band decays under its own envelope, ``tail_envelope`` of its column of ``betas``
-    (``al_ism_shoebox_bands_tail``; every coefficient > 0).  Not yet together with ``patterns`` (ValueError)."""
+    (``al_ism_shoebox_bands_tail``; every coefficient > 0).  Not yet together with ``patterns`` (ValueError).
+
+    ``source_patterns`` ``(4,)`` or ``(N, 4)``: a first-order pattern ``(w, vx, vy, vz)`` per source in room axes (``omni``,
+    ``first_order``, ``cardioid``), applied to the direction in which an image's ray leaves the source.  ``air``: amplitude
+    attenuation in Np/m (``air_absorption``), one number, or ``(B,)`` with bands.  With either the call goes to
+    ``al_ism_shoebox_src`` or ``al_ism_shoebox_bands_src`` (DESIGN.md "Shoebox IRs: directional sources and air"), and a tail takes
+    an envelope per distinct (receiver pattern, source pattern) or (source pattern, band); with both None the calls above, bit
+    for bit."""
     room, betas, sources, capsules, ir_len, fs, c, order = check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c,
-                                                                          max_order, tail, patterns, bands)
+                                                                          max_order, tail, patterns, bands, source_patterns, air)
     if bands is not None and (isinstance(workspace_cap, (bool, np.bool_)) or not isinstance(workspace_cap, (int, np.integer))
                               or workspace_cap < 0):
         raise ValueError("workspace_cap must be an integer >= 0 (bytes)")
@@ -460,6 +571,9 @@ def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sa
                 raise ValueError(f"{name} must be an integer >= 0 with {name} + count <= 2^32")
     mem, lib = renderer.mem, renderer.lib
     mix, fade = (-1, 0) if tail is None else tail_samples(tail, room, fs, c)
+    if source_patterns is not None or air is not None:
+        return _shoebox_irs_source(renderer, room, betas, sources, capsules, ir_len, fs, c, order, tail, mix, fade, int(source_id0),
+                                   int(capsule_id0), patterns, bands, workspace_cap, source_patterns, air)
     # the entry and its arguments: head, (pattern | band) middle, lengths, [tail], [workspace], out, stream
     entry = "al_ism_shoebox"
     middle = walls = (room.ctypes.data_as(ct.POINTER(ct.c_double)), betas.ctypes.data_as(ct.POINTER(ct.c_double)))
@@ -495,6 +609,67 @@ def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sa
     out = mem.empty(n_rows * n * pitch)
     lib.call(entry, mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, *middle, c, fs, order, ir_len, pitch, *tail_block, *workspace_pair,
              mem.ptr(out), mem.stream())
+    return out, (n * pitch, pitch), ir_len
+
+
+def _shoebox_irs_source(renderer, room, betas, sources, capsules, ir_len, fs, c, order, tail, mix, fade, source_id0, capsule_id0,
+                        patterns, bands, workspace_cap, source_patterns, air):
+    """``shoebox_irs_device`` with source patterns or air (arguments checked): the one call of ``al_ism_shoebox_src`` or
+    ``al_ism_shoebox_bands_src``."""
+    mem, lib = renderer.mem, renderer.lib
+    n, n_cap, pitch = len(sources), len(capsules), pitch_of(ir_len)
+    K = 1 if patterns is None else patterns.shape[1]
+    n_rows = n_cap * K
+    spat = None if source_patterns is None else check_source_patterns(source_patterns, n)
+    air = check_air(0.0 if air is None else air, None if bands is None else betas.shape[1])
+    keep = [mem.upload(sources.reshape(-1)), mem.upload(capsules.reshape(-1))]      # device tables, alive until the call is enqueued
+    spat_ptr = 0
+    if spat is not None:
+        keep.append(mem.upload(spat.reshape(-1)))
+        spat_ptr = mem.ptr(keep[-1])
+    source_keys = [b""] * n if spat is None else [row.tobytes() for row in spat]
+    source_of = (lambda key: None) if spat is None else (lambda key: np.frombuffer(key, dtype=np.float64))
+    walls = (room.ctypes.data_as(ct.POINTER(ct.c_double)), betas.ctypes.data_as(ct.POINTER(ct.c_double)))
+    env_ptr, n_knots, seed = 0, 0, 0
+    tables = {}      # one quadrature per distinct (receiver pattern, source pattern) or (source pattern, band)
+    out = mem.empty(n_rows * n * pitch)
+    if bands is not None:
+        n_bands, half = betas.shape[1], int(bands.half)
+        per_pair = lib.call("al_ism_shoebox_bands_workspace_bytes", n_bands, half, ir_len, mix, fade)
+        if per_pair <= 0:
+            raise ValueError(f"al_ism_shoebox_bands_workspace_bytes refused {n_bands} bands, half = {half}, ir_len = {ir_len}")
+        pairs_per_pass = max(1, min(n * n_cap, int(workspace_cap) // per_pair))
+        workspace = mem.empty(pairs_per_pass * per_pair // 8, dtype=np.float64)
+        keep.append(mem.upload(band_filters(bands.centres, fs, half).reshape(-1)))
+        filters_ptr = mem.ptr(keep[-1])
+        if tail is not None:
+            for key in source_keys:
+                for b in range(n_bands):
+                    if (key, b) not in tables:
+                        tables[key, b] = tail_envelope(room, betas[:, b], ir_len, fs, mix, c, tail.rt60, None, source_of(key), float(air[b]))
+            ln_env = np.stack([np.stack([tables[key, b] for b in range(n_bands)]) for key in source_keys])      # (N, B, n_knots)
+            keep.append(mem.upload(ln_env.reshape(-1)))
+            env_ptr, n_knots, seed = mem.ptr(keep[-1]), ln_env.shape[2], int(tail.seed)
+        lib.call("al_ism_shoebox_bands_src", mem.ptr(keep[0]), n, spat_ptr, mem.ptr(keep[1]), n_cap, *walls, n_bands, filters_ptr, half,
+                 air.ctypes.data_as(ct.POINTER(ct.c_double)), c, fs, order, ir_len, pitch, mix, fade, seed, source_id0, capsule_id0, env_ptr,
+                 n_knots, mem.ptr(workspace), pairs_per_pass * per_pair, mem.ptr(out), mem.stream())
+        return out, (n * pitch, pitch), ir_len
+    pat_ptr = 0
+    if patterns is not None:
+        keep.append(mem.upload(patterns.reshape(-1)))
+        pat_ptr = mem.ptr(keep[-1])
+    if tail is not None:
+        rows = [None] * n_rows if patterns is None else list(patterns.reshape(-1, 4))
+        for row in rows:
+            for key in source_keys:
+                pair = (b"" if row is None else row.tobytes(), key)
+                if pair not in tables:
+                    tables[pair] = tail_envelope(room, betas, ir_len, fs, mix, c, tail.rt60, row, source_of(key), float(air[0]))
+        ln_env = np.stack([np.stack([tables[b"" if row is None else row.tobytes(), key] for key in source_keys]) for row in rows])
+        keep.append(mem.upload(ln_env.reshape(-1)))                                                         # (rows, N, n_knots)
+        env_ptr, n_knots, seed = mem.ptr(keep[-1]), ln_env.shape[2], int(tail.seed)
+    lib.call("al_ism_shoebox_src", mem.ptr(keep[0]), n, spat_ptr, mem.ptr(keep[1]), n_cap, pat_ptr, K, *walls, float(air[0]), c, fs, order,
+             ir_len, pitch, mix, fade, seed, source_id0, capsule_id0, env_ptr, n_knots, mem.ptr(out), mem.stream())
     return out, (n * pitch, pitch), ir_len
 
 

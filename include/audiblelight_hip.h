@@ -703,6 +703,35 @@ int al_ism_shoebox_bands_tail(const double *sources, int32_t n_sources, const do
                               int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, void *workspace,
                               int64_t workspace_bytes, float *out, al_stream_t stream);
 
+/* The same rows with DIRECTIONAL SOURCES and AIR ABSORPTION (DESIGN.md "Shoebox IRs: directional sources and air").  One entry for
+ * omnidirectional and directional receivers, with and without a tail:
+ *   source_patterns: float64 DEVICE table (n_sources, 4) of finite (w, vx, vy, vz) in room axes, or NULL (omni sources);
+ *   patterns: as al_ism_shoebox_dir, or NULL with n_channels == 1 for omnidirectional capsules (the rows of al_ism_shoebox);
+ *   air: amplitude attenuation m >= 0 in Np/m;
+ *   mix < 0: no tail, and fade, seed, the ids, ln_env and n_knots are ignored; mix >= 0: the tail of al_ism_shoebox_tail, with ln_env a
+ *   DEVICE table (n_receivers * n_channels, n_sources, n_knots): the pair of row c and source n reads table c * n_sources + n.
+ * For the image (qx, qy, qz) = 2 m - p with offset R, d = |R| and u = R / d, the ray leaves the real source in the direction e,
+ * e_i = -(-1)^{q_i} u_i (a reflection on an axis-i wall flips component i; the direct path leaves along -u).  The image's amplitude in
+ * row c is  a (w_s + v_s . e) exp(-m d) (w_c + v_c . u): a of al_ism_shoebox, the last factor 1 for an omni capsule.  Tap shape, reach,
+ * order rule, beta = 0 rule and summation order are unchanged.  With omni sources (NULL, or rows (1, 0, 0, 0)) and air == 0 the
+ * output has the bits of al_ism_shoebox, al_ism_shoebox_dir and, given the same table for every source, of their _tail entries.
+ * AL_E_BADARG: everything those four refuse; air negative or not finite; patterns == NULL with n_channels != 1;
+ * n_knots * n_sources >= 2^32.  The launches of the entry it stands for; no allocation, no synchronisation, no atomics. */
+int al_ism_shoebox_src(const double *sources, int32_t n_sources, const double *source_patterns, const double *receivers,
+                       int32_t n_receivers, const double *patterns, int32_t n_channels, const double *L, const double *beta, double air,
+                       double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade, uint64_t seed,
+                       int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, float *out, al_stream_t stream);
+/* al_ism_shoebox_bands (mix < 0) or al_ism_shoebox_bands_tail (mix >= 0) with source_patterns as above and air a HOST array of n_bands
+ * coefficients m_b: the image sum y_b of band b carries (w_s + v_s . e) exp(-m_b d) per image.  With a tail ln_env is a DEVICE table
+ * (n_sources, n_bands, n_knots): source n's band b reads table n * n_bands + b.  The workspace is sized by
+ * al_ism_shoebox_bands_workspace_bytes.  AL_E_BADARG: everything the two band entries refuse; a null air; an air[b] negative or not
+ * finite. */
+int al_ism_shoebox_bands_src(const double *sources, int32_t n_sources, const double *source_patterns, const double *capsules,
+                             int32_t n_capsules, const double *L, const double *beta, int32_t n_bands, const double *filters,
+                             int32_t half, const double *air, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch,
+                             int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env,
+                             int32_t n_knots, void *workspace, int64_t workspace_bytes, float *out, al_stream_t stream);
+
 /* dst[t] = src[t mod m] for t < n: np.pad(..., mode="wrap") of Augmentation.process. */
 int al_wrap_copy(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream);
 
