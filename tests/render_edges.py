@@ -106,25 +106,37 @@ def run_twiddles(r, log2_block):
 
 
 # ----------------------------------------------------------------------------- batch construction
-def make_plan(specs, C, Lir, log2_block, guards=False, odd=False):
+def make_plan(specs, C, Lir, log2_block, guards=False, odd=False, base=0):
     """plan_batch + optional guard bands: every event's (C, len) block moves to its own place in ``spatial`` with G sentinel
     floats before and after it (al_event.out_off rewritten in the plan's ``events`` table, spatial_floats enlarged before
-    ``prepare``); ``odd`` starts every other block at an odd float offset, so both synth_store_block pair paths run."""
+    ``prepare``); ``odd`` starts every other block at an odd float offset, so both synth_store_block pair paths run.  ``base``
+    (with guards) moves the whole guarded region that many floats into ``spatial``: the floats below it are never touched, the
+    checks below read [base, spatial_floats) only (tests/wide_offset_cases.py puts it next to 2^31)."""
     pl = planning.plan_batch(specs, C, Lir, SR, log2_block=log2_block)
     if guards:
-        off = G
+        off = base + G
         for i, ev in enumerate(pl.events):
             if odd and (i % 2 == 0) != (off % 2 == 1):
                 off += 1
             pl.events["out_off"][i] = off
             off += C * int(ev["len"]) + G
         pl.spatial_floats = off + G
+        pl.spatial_base = int(base)
     return pl
 
 
+def spatial_base(pl):
+    return getattr(pl, "spatial_base", 0)
+
+
 def sentinel_spatial(r, batch):
-    """Replace the batch's ``spatial`` by a buffer filled with the sentinel pattern (every chunk descriptor repointed)."""
-    n = batch.plan.spatial_floats
+    """Replace the batch's ``spatial`` by a buffer filled with the sentinel pattern (every chunk descriptor repointed).  With a
+    plan moved to ``base``, the batch's own buffer is kept and only [base, spatial_floats) is filled."""
+    n, base = batch.plan.spatial_floats, spatial_base(batch.plan)
+    if base:
+        buf = batch.bufs["spatial"]
+        put(r, buf[base:], np.resize(SENTINEL, 4 * (n - base)).view(np.float32))
+        return buf
     buf = r.mem.upload(np.resize(SENTINEL, 4 * n).view(np.float32))
     batch.bufs["spatial"] = buf
     for desc in batch.descs:
@@ -133,14 +145,16 @@ def sentinel_spatial(r, batch):
 
 
 def check_guards(r, batch):
-    """Every float of ``spatial`` outside the events' (C, len) blocks still holds the sentinel; returns the whole buffer."""
+    """Every float of ``spatial`` outside the events' (C, len) blocks still holds the sentinel; returns the buffer from
+    ``spatial_base(plan)`` on (the whole buffer unless the plan was moved)."""
     pl = batch.plan
-    sp = download(r, batch.bufs["spatial"], pl.spatial_floats)
-    inside = np.zeros(pl.spatial_floats, dtype=bool)
+    base = spatial_base(pl)
+    sp = download(r, batch.bufs["spatial"][base: pl.spatial_floats])
+    inside = np.zeros(pl.spatial_floats - base, dtype=bool)
     for ev in pl.events:
-        inside[int(ev["out_off"]): int(ev["out_off"]) + pl.n_capsules * int(ev["len"])] = True
+        inside[int(ev["out_off"]) - base: int(ev["out_off"]) - base + pl.n_capsules * int(ev["len"])] = True
     outside = bits(sp[~inside]) != bits(np.full(1, SENTINEL_F32))[0]
-    assert not outside.any(), f"{int(outside.sum())} floats outside the event blocks overwritten (first at {int(np.flatnonzero(~inside)[np.argmax(outside)])})"
+    assert not outside.any(), f"{int(outside.sum())} floats outside the event blocks overwritten (first at {base + int(np.flatnonzero(~inside)[np.argmax(outside)])})"
     return sp
 
 
@@ -237,12 +251,12 @@ def check_render(r, batch, clips, irs, family, partials=True):
     res = batch.result()
     sp = check_guards(r, batch)
     gains = download(r, batch.bufs["emitter_gain"], max(pl.n_emitters, 1)).astype(np.float64)
-    part = download(r, batch.bufs["partials"], 4 * pl.n_partials).reshape(-1, 4) if partials else None
+    base = spatial_base(pl)
     outs = []
     for i in range(len(pl.events)):
         ev = pl.events[i]
         n, valid = int(ev["len"]), int(ev["valid_len"])
-        got = sp[int(ev["out_off"]): int(ev["out_off"]) + C * n].reshape(C, n)
+        got = sp[int(ev["out_off"]) - base: int(ev["out_off"]) - base + C * n].reshape(C, n)
         want, scale, term = render64(pl, i, clips[i], irs, gains)
         assert np.isfinite(got).all(), (family, i)
         if valid < n:       # pad_or_truncate_audio's zeros: +0.0, bit for bit
@@ -265,7 +279,8 @@ def check_render(r, batch, clips, irs, family, partials=True):
             record(f"render {family} silent (err / bound)", float(np.max(np.abs(got) / render_bound(B, pl.n_partitions, scale)[:, None])), 1.0)
         if partials:
             K = int(ev["n_blocks"])
-            pp = part[int(ev["part_base"]): int(ev["part_base"]) + C * K].reshape(C, K, 4)
+            pb = int(ev["part_base"])      # this event's entries alone: part_base may lie anywhere in a large buffer
+            pp = download(r, batch.bufs["partials"][4 * pb: 4 * (pb + C * K)]).reshape(C, K, 4)
             x = np.abs(np.pad(got.astype(np.float64), ((0, 0), (0, K * B - n))).reshape(C, K, B))
             np.testing.assert_array_equal(pp[..., 1], x.max(axis=2).astype(np.float32), err_msg=f"{family} partial max, event {i}")
             s64 = x.sum(axis=2)

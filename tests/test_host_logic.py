@@ -654,6 +654,53 @@ def test_c_planner_mixdown_and_weights_equal_the_numpy_planner():
         np.testing.assert_array_equal(planning.generate_interpolation_matrix(t, sr, 128), orc.crossfade_weights(t, sr, 128))
 
 
+def test_c_planner_past_2_31_equals_the_numpy_planner():
+    """Plans whose spatial_floats or audio_floats -- and with them the last events' out_off / audio_off and the mixdown's slot_src
+    -- pass 2^31 and 2^32: every table field for field against tests/plan_reference.py, every chunk of al_plan_chunk too.  A few
+    long events reach the boundary; a short moving event comes last, so that its offsets lie past it."""
+    from hypothesis import assume, given, settings, strategies as st
+
+    from tests import plan_reference as ref
+
+    @settings(max_examples=40, deadline=None)
+    @given(st.sampled_from(["spatial", "audio"]), st.sampled_from([1 << 31, 1 << 32]), st.integers(3, 7), st.integers(1, 64),
+           st.integers(0, 5000), st.sampled_from([13, 14]), st.integers(1, 3))
+    def check(which, target, n_ev, C, extra, lb, chunk):
+        sr = 48000.0
+        C = C if which == "spatial" else 1 + C % 2
+        per = target // (n_ev * (C if which == "spatial" else 1)) + 1 + extra
+        assume(per + 13 * n_ev < (1 << 31) - (1 << 15))
+        specs = [dict(n_samples=per + 13 * i, n_emitters=1, snr=10.0, emitter0=i) for i in range(n_ev)]
+        specs.append(dict(n_samples=5000 + extra, n_emitters=3, snr=7.0, emitter0=n_ev, is_moving=True, duration=(5000 + extra) / sr))
+        specs.append(dict(n_samples=1234, n_emitters=0, snr=3.0, emitter0=n_ev + 3))
+        a = planning.plan_batch([planning.EventSpec(**k) for k in specs], C, 3000, sr, log2_block=lb)
+        b = ref.plan_batch([ref.EventSpec(**k) for k in specs], C, 3000, sr, log2_block=lb)
+        assert (a.spatial_floats if which == "spatial" else a.audio_floats) > target
+        off = a.events["out_off" if which == "spatial" else "audio_off"]
+        assert off.dtype == np.int64 and int(off[-1]) > target and int(off[-2]) > target and (np.diff(off) > 0).all()
+        for name in a.events.dtype.names:
+            assert np.array_equal(a.events[name], b.events[name]), name
+        for name in a.streams.dtype.names:
+            assert np.array_equal(a.streams[name], b.streams[name]), name
+        assert np.array_equal(a.wtab, b.wtab) and np.array_equal(a.audio_offsets, b.audio_offsets)
+        assert (a.audio_floats, a.spatial_floats, a.xspec_blocks, a.yspec_blocks, a.n_partials, a.n_emitters) == \
+               (b.audio_floats, b.spatial_floats, b.xspec_blocks, b.yspec_blocks, b.n_partials, b.n_emitters)
+        assert a.workspace_bytes() == b.workspace_bytes() and a.chunks(chunk) == b.chunks(chunk) and len(a.chunks(chunk)) > 1
+        n = len(specs)
+        starts = [0.25 * i for i in range(n)]
+        lens = [int(x) for x in a.events["len"]]
+        ends = [s + min(ln, 200000) / sr for s, ln in zip(starts, lens)]
+        ma = planning.plan_mixdown(starts, ends, lens, [C] * n, a.events["out_off"], list(range(n)), 6.0, sr, C)
+        mb = ref.plan_mixdown(starts, ends, lens, [C] * n, b.events["out_off"], list(range(n)), 6.0, sr, C)
+        for f in ("tile_ptr", "tile_events", "slot_src", "slot_len", "slot_start", "slot_count", "slot_rows", "slot_event"):
+            assert np.array_equal(getattr(ma, f), getattr(mb, f)), f
+        assert ma.slot_src.dtype == np.int64 and np.array_equal(ma.slot_src, a.events["out_off"][ma.slot_event])
+        if which == "spatial":
+            assert int(ma.slot_src.max()) > target
+
+    check()
+
+
 def test_c_planner_refuses_what_the_reference_refuses():
     with pytest.raises(ValueError, match="Moving Event has only one emitter!"):
         planning.plan_batch([planning.EventSpec(10, 1, 1.0, is_moving=True)], 1, 10, 8000)
