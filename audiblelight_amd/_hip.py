@@ -224,6 +224,11 @@ SYMBOLS = {
                                         _P, ct.c_int32, ct.POINTER(ct.c_double), ct.c_double, ct.c_double, ct.c_int32, ct.c_int32,
                                         ct.c_int32, ct.c_int64, ct.c_int64, ct.c_uint64, ct.c_int64, ct.c_int64, _P, ct.c_int32, _P,
                                         ct.c_int64, _P, _S]),
+    "al_ism_shoebox_sphere_workspace_bytes": (ct.c_int64, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int64, ct.c_int64]),
+    "al_ism_shoebox_sphere": (ct.c_int, [_P, ct.c_int32, _P, ct.POINTER(ct.c_double), _P, ct.c_int32, ct.POINTER(ct.c_double),
+                                     ct.POINTER(ct.c_double), ct.c_double, _P, ct.c_int32, ct.c_int32, _P, ct.c_double, ct.c_double,
+                                     ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int64, ct.c_int64, ct.c_uint64, ct.c_int64, ct.c_int64, _P,
+                                     ct.c_int32, _P, ct.c_int64, _P, _S]),
     "al_noise_workspace_floats": (ct.c_int64, [ct.c_int32, ct.c_int64]),
     "al_noise_irfft": (ct.c_int, [_P, _P, _P, ct.c_int32, ct.c_int64, ct.c_float, _P, _P, _S]),
     "al_noise_irfft_seeded": (ct.c_int, [ct.c_uint64, _P, ct.c_int32, ct.c_int64, ct.c_float, _P, _P, _S]),

@@ -312,7 +312,9 @@ class ShoeboxIRState:
     ``from_dict`` needs no material file.
     ``air``: the air's amplitude attenuation in Np/m (``shoebox.air_absorption``), one number, or one per band with ``bands``;
     ``add_emitters(patterns=...)`` gives emitters a first-order pattern each (DESIGN.md "Shoebox IRs: directional sources and
-    air").  Without either the state generates what it generated before, bit for bit."""
+    air").  Without either the state generates what it generated before, bit for bit.
+    ``add_sphere_microphone`` puts capsules on a rigid sphere and ``add_binaural_listener`` two ears on a spherical head (DESIGN.md
+    "Shoebox IRs: rigid-sphere receivers"); the other microphones of the state are generated as before."""
 
     name = "SHOEBOX"
 
@@ -351,6 +353,7 @@ class ShoeboxIRState:
         self._emitter_patterns: "OrderedDict[str, np.ndarray]" = OrderedDict()      # (n, 4) of the aliases that have patterns
         self._capsules: "OrderedDict[str, np.ndarray]" = OrderedDict()      # receiver positions (P, 3) of each microphone
         self._patterns: "OrderedDict[str, Optional[np.ndarray]]" = OrderedDict()     # None (omni) or (P, K, 4)
+        self._spheres: "OrderedDict[str, dict]" = OrderedDict()      # the microphones on a rigid sphere: centre, radius, directions, ...
         self._irs = None
         # refuse bad room parameters here, not at the first simulate()
         inside = 0.5 * self.room[None, :]
@@ -384,6 +387,41 @@ class ShoeboxIRState:
             raise ValueError("an FOA listener is one point")
         return self._add_receivers(alias, point, patterns[None, :, :], list(order.lower()),
                                    dict(micarray_type="FOAListener", channel_layout_type="foa"))
+
+    def add_sphere_microphone(self, alias: str, centre, directions, radius: float = 0.042, n_orders: Optional[int] = None,
+                              half: Optional[int] = None, capsule_names=None) -> MicArray:
+        """Capsules on a RIGID SPHERE of ``radius`` metres at ``centre``, capsule c at the unit direction ``directions[c]`` (C, 3; room
+        axes, normalised here): an array whose body scatters (DESIGN.md "Shoebox IRs: rigid-sphere receivers").  The default radius
+        is that of the 4.2 cm arrays; no array geometry is shipped, the directions are the caller's.  ``n_orders`` and ``half``: as
+        ``shoebox.sphere_filters`` (None: from the radius and the sample rate).  The capsule coordinates written to the metadata
+        are ``centre + radius directions``."""
+        from . import shoebox
+
+        return self._add_sphere(alias, centre, shoebox.check_directions(directions), radius, n_orders, half, capsule_names, {})
+
+    def add_binaural_listener(self, alias: str, position, forward=(1.0, 0.0, 0.0), up=(0.0, 0.0, 1.0), radius: float = 0.0875,
+                              ear_angle_deg: float = 100.0) -> MicArray:
+        """A listener with a SPHERICAL HEAD of ``radius`` metres at ``position``: two channels, left then right, the ears at
+        ``+-ear_angle_deg`` from ``forward`` about ``up`` (``shoebox.binaural_directions``; the reference's ``binaural`` channel
+        layout).  Level and time differences come from the sphere's scattering; there is no pinna and no torso."""
+        from . import shoebox
+
+        ears = shoebox.check_directions(shoebox.binaural_directions(forward, up, ear_angle_deg))      # one policy for every path
+        return self._add_sphere(alias, position, ears, radius, None, None, ["left", "right"],
+                                dict(micarray_type="Binaural", channel_layout_type="binaural"))
+
+    def _add_sphere(self, alias: str, centre, directions: np.ndarray, radius, n_orders, half, capsule_names, metadata: dict) -> MicArray:
+        from . import shoebox
+
+        if self.bands is not None:
+            raise ValueError("bands together with a rigid sphere are not yet supported (B x n_orders rows per capsule)")
+        centre, radius = shoebox.check_sphere(self.room, centre, radius, self.emitter_positions)
+        _, _, _, n_orders, half, _ = shoebox._sphere_plan(radius, float(self.sample_rate), self.c, n_orders, half)
+        positions = centre[None, :] + radius * directions
+        sphere = dict(centre=centre.tolist(), radius=radius, n_orders=n_orders, half=half, directions=directions.tolist())
+        mic = self._add_receivers(alias, positions, None, capsule_names, dict(metadata, is_spherical=True, sphere=sphere))
+        self._spheres[alias] = dict(centre=centre, radius=radius, n_orders=n_orders, half=half, directions=directions)
+        return mic
 
     def _add_receivers(self, alias: str, positions: np.ndarray, patterns, capsule_names, metadata: dict) -> MicArray:
         """``positions`` (P, 3) with ``patterns`` None (omni, one channel each) or (P, K, 4): a microphone of P K channels."""
@@ -420,6 +458,8 @@ class ShoeboxIRState:
         if alias in self.emitters:
             raise KeyError(f"Emitters with alias {alias} already exist")
         points = shoebox._points(np.atleast_2d(np.asarray(positions, dtype=np.float64)), self.room, f"emitters {alias}")
+        for sphere in self._spheres.values():      # the plane-wave model: no emitter closer than 2 radius to a sphere's centre
+            shoebox.check_sphere(self.room, sphere["centre"], sphere["radius"], points)
         if patterns is not None:
             self._emitter_patterns[alias] = shoebox.check_source_patterns(patterns, len(points))
         self.emitters[alias] = points
@@ -456,9 +496,16 @@ class ShoeboxIRState:
         irs = OrderedDict()
         capsule_id0 = 0     # the tail's noise: channels are numbered through the microphones, emitters are one table already
         for alias, capsules in self._capsules.items():
-            buf, strides, _ = shoebox.shoebox_irs_device(r, self.room, self.betas, sources, capsules, self.ir_len, self.sample_rate,
-                                                         self.c, self.max_order, self.tail, 0, capsule_id0, self._patterns[alias],
-                                                         self.bands, source_patterns=self.emitter_patterns, air=self.air)
+            sphere = self._spheres.get(alias)
+            if sphere is not None:
+                buf, strides, _ = shoebox.shoebox_sphere_irs_device(r, self.room, self.betas, sources, sphere["centre"], sphere["directions"],
+                                                                    sphere["radius"], self.ir_len, self.sample_rate, self.c, self.max_order,
+                                                                    self.tail, 0, capsule_id0, sphere["n_orders"], sphere["half"],
+                                                                    source_patterns=self.emitter_patterns, air=self.air)
+            else:
+                buf, strides, _ = shoebox.shoebox_irs_device(r, self.room, self.betas, sources, capsules, self.ir_len, self.sample_rate,
+                                                             self.c, self.max_order, self.tail, 0, capsule_id0, self._patterns[alias],
+                                                             self.bands, source_patterns=self.emitter_patterns, air=self.air)
             n_channels = self.microphones[alias].n_capsules
             irs[alias] = shoebox.DeviceIRTensor(r, buf, strides, (n_channels, len(sources), self.ir_len))
             capsule_id0 += n_channels
@@ -513,6 +560,16 @@ class ShoeboxIRState:
         state.materials = None if box.get("materials") is None else [str(v) for v in box["materials"]]
         for alias, md in state_d["microphones"].items():
             positions = shoebox._points(md["coordinates_absolute"], state.room, f"capsules of {alias}")
+            sphere = md.get("sphere")
+            if sphere is not None:      # capsules on a rigid sphere: the directions as they were written (check_directions takes unit
+                # rows as they are, so their bits come back), else from the coordinates
+                directions = sphere.get("directions")
+                if directions is None:
+                    directions = positions - np.asarray(sphere["centre"], dtype=np.float64)[None, :]
+                mic = state._add_sphere(alias, sphere["centre"], shoebox.check_directions(directions), sphere["radius"],
+                                        sphere.get("n_orders"), sphere.get("half"), md.get("capsule_names"), {})
+                mic.metadata.update({k: v for k, v in md.items() if k not in ("n_capsules", "sphere", "coordinates_absolute")})
+                continue
             patterns = md.get("patterns")      # one row per channel; several channels share a coordinate row (an FOA listener)
             if patterns is not None:
                 patterns = np.asarray(patterns, dtype=np.float64)

@@ -31,6 +31,7 @@
 #include "al_ingest.h"
 #include "al_ism.h"
 #include "al_ism_bands.h"
+#include "al_ism_sphere.h"
 #include "al_levels.h"
 #include "al_mac.h"
 #include "al_mixdown.h"
@@ -708,6 +709,26 @@ int al_ism_shoebox_bands_src(const double *sources, int32_t n_sources, const dou
   if (int rc = al::ism_bands_source_prepare(source_patterns, air, with_tail, &job)) return rc;
   al::launch_ism_shoebox_bands_src(job, with_tail, (hipStream_t)stream);
   return check_launch("k_ism_bands_src");
+}
+
+// ---- capsules on a rigid sphere (arrays, a spherical head): DESIGN.md "Shoebox IRs: rigid-sphere receivers"
+int64_t al_ism_shoebox_sphere_workspace_bytes(int32_t n_orders, int32_t half, int32_t ir_len, int64_t mix, int64_t fade) {
+  return al::ism_sphere_workspace_bytes(n_orders, half, ir_len, mix, fade);
+}
+
+int al_ism_shoebox_sphere(const double *sources, int32_t n_sources, const double *source_patterns, const double *centre,
+                          const double *directions, int32_t n_capsules, const double *L, const double *beta, double air,
+                          const double *filters, int32_t n_orders, int32_t half, const double *diffuse, double c, double fs,
+                          int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0,
+                          int64_t capsule_id0, const double *ln_env, int32_t n_knots, void *workspace, int64_t workspace_bytes, float *out,
+                          al_stream_t stream) {
+  al::IsmSphereJob job;
+  if (int rc = al::ism_sphere_prepare(sources, n_sources, source_patterns, centre, directions, n_capsules, L, beta, air, filters, n_orders,
+                                      half, diffuse, c, fs, max_order, ir_len, pitch, mix, fade, seed, source_id0, capsule_id0, ln_env,
+                                      n_knots, workspace, workspace_bytes, out, &job))
+    return rc;
+  al::launch_ism_shoebox_sphere(job, mix >= 0, (hipStream_t)stream);
+  return check_launch("k_ism_sphere");
 }
 
 int al_resample_poly(const float *x, int32_t rows, int64_t n_in, const float *taps, int32_t half_len, int32_t up, int32_t down,

@@ -14,6 +14,8 @@ Sources are omnidirectional, or carry a first-order pattern each (``source_patte
 applied to the direction in which the image's ray leaves the source), and the air may absorb (``air=`` in Np/m, one coefficient or one
 per band; ``air_absorption`` gives ISO 9613-1's): ``al_ism_shoebox_src``, ``al_ism_shoebox_bands_src``; DESIGN.md "Shoebox IRs:
 directional sources and air".
+Capsules may sit on a rigid sphere, an array or a spherical head (``shoebox_sphere_irs_device``, ``sphere_filters``,
+``sphere_diffuse_filter``, ``binaural_directions``; ``al_ism_shoebox_sphere``, DESIGN.md "Shoebox IRs: rigid-sphere receivers").
 """
 from __future__ import annotations
 
@@ -670,6 +672,258 @@ def _shoebox_irs_source(renderer, room, betas, sources, capsules, ir_len, fs, c,
         env_ptr, n_knots, seed = mem.ptr(keep[-1]), ln_env.shape[2], int(tail.seed)
     lib.call("al_ism_shoebox_src", mem.ptr(keep[0]), n, spat_ptr, mem.ptr(keep[1]), n_cap, pat_ptr, K, *walls, float(air[0]), c, fs, order,
              ir_len, pitch, mix, fade, seed, source_id0, capsule_id0, env_ptr, n_knots, mem.ptr(out), mem.stream())
+    return out, (n * pitch, pitch), ir_len
+
+
+# ----------------------------------------------------------------------------- capsules on a rigid sphere
+MAX_SPHERE_ORDERS = 64     # Legendre orders of al_ism_shoebox_sphere
+MIN_SPHERE_ORDERS = 4      # the fewest sphere_filters takes when asked for a number
+MAX_SPHERE_HALF = 1024     # its cap on the half length of a radial filter
+SPHERE_PASS_EDGE = 0.8     # the pass edge f_p of the radial filters, as a fraction of the Nyquist frequency
+
+
+def spherical_hankel1(n_max: int, x) -> np.ndarray:
+    """``h_l(x)``, ``l = 0 .. n_max``, the spherical Hankel functions of the first kind at the positive reals ``x``: complex
+    ``(n_max + 1, len(x))``.  ``h_0 = -i e^{ix} / x``, ``h_1 = -e^{ix} (x + i) / x^2`` and upwards by
+    ``h_{l+1} = (2 l + 1) / x h_l - h_{l-1}``: the stable direction for this solution (it is dominated by ``y_l``, which grows
+    with ``l``).  An order that overflows float64 (a tiny ``x`` at a high order) comes out as inf or nan."""
+    x = np.asarray(x, dtype=np.float64)
+    h = np.zeros((int(n_max) + 1,) + x.shape, dtype=np.complex128)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        e = np.exp(1j * x)
+        h[0] = -1j * e / x
+        if n_max >= 1:
+            h[1] = -e * (x + 1j) / (x * x)
+        for l in range(1, int(n_max)):
+            h[l + 1] = (2 * l + 1) / x * h[l] - h[l - 1]
+    return h
+
+
+def wiscombe_length(x: float) -> int:
+    """``ceil(x + 4 x^(1/3) + 2) + 1``: the orders ``0 .. ceil(x + 4 x^(1/3) + 2)`` of Wiscombe's series length at size parameter ``x``."""
+    return int(np.ceil(x + 4.0 * x ** (1.0 / 3.0) + 2.0)) + 1
+
+
+def _sphere_plan(radius, sample_rate, c, n_orders, half):
+    """(radius, fs, c, n_orders, half, f_p) of ``sphere_filters`` (ValueError)."""
+    for name, v in (("radius", radius), ("sample_rate", sample_rate), ("c", c)):
+        if not (isinstance(v, _REAL) and not isinstance(v, bool) and np.isfinite(v) and v > 0.0):
+            raise ValueError(f"{name} must be a finite number > 0")
+    a, fs, c = float(radius), float(sample_rate), float(c)
+    if half is None:
+        half = max(64, 2 * int(np.ceil(4.0 * a * fs / c)))
+    if isinstance(half, (bool, np.bool_)) or not isinstance(half, (int, np.integer)) or not 1 <= int(half) <= MAX_SPHERE_HALF:
+        raise ValueError(f"half must be an integer in 1 .. {MAX_SPHERE_HALF}")
+    f_p = SPHERE_PASS_EDGE * 0.5 * fs
+    x_p = 2.0 * np.pi * f_p * a / c
+    if n_orders is None:
+        n_orders = min(wiscombe_length(x_p), MAX_SPHERE_ORDERS)
+    elif (isinstance(n_orders, (bool, np.bool_)) or not isinstance(n_orders, (int, np.integer))
+          or not MIN_SPHERE_ORDERS <= int(n_orders) <= MAX_SPHERE_ORDERS):
+        raise ValueError(f"n_orders must be None or an integer in {MIN_SPHERE_ORDERS} .. {MAX_SPHERE_ORDERS}")
+    n_orders = int(n_orders)
+    if wiscombe_length(x_p) > n_orders:     # the largest x whose series still fits: x + 4 x^(1/3) + 2 = n_orders - 1, by bisection
+        lo, hi = 0.0, x_p
+        for _ in range(200):
+            mid = 0.5 * (lo + hi)
+            lo, hi = (mid, hi) if mid + 4.0 * mid ** (1.0 / 3.0) + 2.0 <= n_orders - 1.0 else (lo, mid)
+        f_p = lo * c / (2.0 * np.pi * a)
+    return a, fs, c, n_orders, int(half), f_p
+
+
+def _sphere_spectra(a, fs, c, n_orders, half, f_p):
+    """``B`` complex ``(n_orders, Nf / 2 + 1)`` of ``sphere_filters`` on the grid ``f_k = k fs / (4 half)``, taper included."""
+    n_fft = 4 * half
+    f = np.arange(n_fft // 2 + 1, dtype=np.float64) * fs / n_fft
+    taper = np.where(f <= f_p, 1.0, np.where(f < 1.25 * f_p, np.cos(0.5 * np.pi * (f - f_p) / (0.25 * f_p)) ** 2, 0.0))
+    B = np.zeros((n_orders, len(f)), dtype=np.complex128)
+    B[0, 0] = 1.0
+    live = np.flatnonzero(taper[1:] > 0.0) + 1
+    x = 2.0 * np.pi * f[live] * a / c
+    h = spherical_hankel1(n_orders, x)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        for l in range(n_orders):
+            dh = (l / x) * h[l] - h[l + 1]
+            series = (2 * l + 1) * 1j * (-1j) ** l / (x * x * dh)
+            # an order whose Hankel function has left the float64 range contributes nothing at that frequency
+            B[l, live] = np.where(np.isfinite(dh.real) & np.isfinite(dh.imag), np.conj(series), 0.0) * taper[live]
+    return B
+
+
+def _sphere_window(half: int) -> np.ndarray:
+    """``w[|j|]``, ``|j| = 0 .. half``: 1 up to ``half // 2``, then a raised cosine that reaches zero at ``half + 1``."""
+    j = np.arange(half + 1, dtype=np.float64)
+    flat = half // 2
+    return np.where(j <= flat, 1.0, 0.5 * (1.0 + np.cos(np.pi * (j - flat) / (half + 1.0 - flat))))
+
+
+def sphere_filters(radius: float, sample_rate: float, c: float = SPEED_OF_SOUND, n_orders: Optional[int] = None,
+                   half: Optional[int] = None) -> np.ndarray:
+    """The float64 table ``b`` of shape ``(n_orders, 2 half + 1)``, ``b[l, half + j] = b_l[j]``, of the radial filters of a rigid
+    sphere of ``radius`` metres: THE TABLE THIS RETURNS IS THE DEFINITION ``al_ism_shoebox_sphere`` is handed.  A plane wave from the
+    unit direction ``u`` puts ``sum_l P_l(n . u) (b_l * x)`` at the surface point of direction ``n``, with ``x`` the wave at the
+    centre: time zero is the arrival at the centre, so the point facing the wave peaks at ``-radius fs / c`` samples.
+
+    Grid ``f_k = k fs / Nf``, ``Nf = 4 half``, ``x_k = 2 pi f_k radius / c``.  Pass edge ``f_p = 0.8 fs / 2``; taper ``T(f) = 1`` up to
+    ``f_p``, ``cos^2(pi / 2 (f - f_p) / (0.25 f_p))`` up to ``1.25 f_p`` (the Nyquist frequency for that ``f_p``) and 0 beyond.  For
+    ``k >= 1``, ``B_l(f_k) = conj((2 l + 1) i (-i)^l / (x^2 h_l'(x))) T(f_k)`` with ``h_l`` the spherical Hankel function of the first
+    kind (``spherical_hankel1``; the conjugate takes the textbook's ``e^{-i w t}`` to numpy's transform) and
+    ``h_l' = (l / x) h_l - h_{l+1}``; ``B_0(0) = 1``, ``B_{l >= 1}(0) = 0``.  ``b_l[j] = irfft(B_l, Nf)[j mod Nf] w[j]``, ``w = 1`` for
+    ``|j| <= half // 2`` and from there a raised cosine that reaches zero at ``|j| = half + 1``.
+
+    ``n_orders`` None: ``ceil(x_p + 4 x_p^(1/3) + 2) + 1`` with ``x_p = 2 pi f_p radius / c`` (Wiscombe's series length).  If that
+    exceeds 64, or ``n_orders`` (4 .. 64) is given and is smaller, THE PASS EDGE ``f_p`` IS LOWERED to the largest frequency whose
+    Wiscombe length still fits, and the taper with it: the array is then band-limited below ``1.25 f_p``.  ``half`` None:
+    ``max(64, 2 ceil(4 radius fs / c))``, 64 for a 4.2 cm array at 48 kHz, 98 for an 8.75 cm head."""
+    a, fs, c, n_orders, half, f_p = _sphere_plan(radius, sample_rate, c, n_orders, half)
+    n_fft = 4 * half
+    time = np.fft.irfft(_sphere_spectra(a, fs, c, n_orders, half, f_p), n_fft, axis=1)
+    j = np.arange(-half, half + 1)
+    return np.ascontiguousarray(time[:, j % n_fft] * _sphere_window(half)[np.abs(j)][None, :])
+
+
+def sphere_diffuse_filter(radius: float, sample_rate: float, c: float = SPEED_OF_SOUND, n_orders: Optional[int] = None,
+                          half: Optional[int] = None) -> np.ndarray:
+    """The float64 taps ``psi_d`` of shape ``(2 half + 1,)``, index ``j + half``, of the diffuse-field filter of a surface point of
+    the sphere of ``sphere_filters`` (same arguments, same grid, transform and window):
+    ``D(f_k) = sqrt(sum_l |B_l(f_k)|^2 / (2 l + 1))``, ``D(0) = 1``: the RMS response to plane waves from all directions, which
+    tends to sqrt(2) at high ``ka``.  Zero phase, and symmetric bit for bit."""
+    a, fs, c, n_orders, half, f_p = _sphere_plan(radius, sample_rate, c, n_orders, half)
+    B = _sphere_spectra(a, fs, c, n_orders, half, f_p)
+    D = np.sqrt((np.abs(B) ** 2 / (2.0 * np.arange(n_orders)[:, None] + 1.0)).sum(axis=0))
+    D[0] = 1.0
+    right = np.fft.irfft(D, 4 * half)[: half + 1] * _sphere_window(half)
+    return np.ascontiguousarray(np.concatenate([right[:0:-1], right]))
+
+
+UNIT_TOLERANCE = 16.0 * np.finfo(np.float64).eps     # |n|^2 within this of 1: a unit vector to rounding, taken as it is
+
+
+def check_directions(directions) -> np.ndarray:
+    """Capsule directions as float64 unit vectors ``(C >= 1, 3)``; a zero or non-finite direction is a ValueError.  A row that is of
+    unit length to rounding (``| |n|^2 - 1 | <= 16 eps``) is TAKEN AS IT IS, every other row is divided by its length, which leaves it
+    within that tolerance: the function is idempotent, so directions that went through it once (``binaural_directions``, a state's
+    metadata) keep their bits however often they pass again."""
+    try:
+        directions = np.array(directions, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("directions must be an array of shape (capsules, 3)")
+    if directions.ndim != 2 or directions.shape[1] != 3 or directions.shape[0] < 1:
+        raise ValueError("directions must have shape (capsules >= 1, 3)")
+    if not np.all(np.isfinite(directions)):
+        raise ValueError("directions must be finite")
+    largest = np.abs(directions).max(axis=1)
+    if np.any(largest == 0.0):
+        raise ValueError("a direction must not be the zero vector")
+    with np.errstate(over="ignore", under="ignore", divide="ignore", invalid="ignore"):
+        norm2 = (directions * directions).sum(axis=1)
+        unit = np.abs(norm2 - 1.0) <= UNIT_TOLERANCE
+        divided = directions / np.sqrt(norm2)[:, None]
+    extreme = ~np.isfinite(norm2) | (norm2 < 1e-280)      # a row whose square overflows or vanishes: scaled by its largest component first
+    scaled = directions / largest[:, None]
+    scaled = scaled / np.sqrt((scaled * scaled).sum(axis=1))[:, None]
+    return np.ascontiguousarray(np.where(unit[:, None], directions, np.where(extreme[:, None], scaled, divided)))
+
+
+def check_sphere(room, centre, radius, sources=None) -> Tuple[np.ndarray, float]:
+    """``(centre, radius)`` of a sphere that lies wholly inside the room, every source at least ``2 radius`` from its centre
+    (ValueError): closer than that the plane-wave model of the scattering has an error of order one."""
+    room = _room(room)
+    if not (isinstance(radius, _REAL) and not isinstance(radius, bool) and np.isfinite(radius) and radius > 0.0):
+        raise ValueError("radius must be a finite number > 0 (metres)")
+    radius = float(radius)
+    centre = np.asarray(centre, dtype=np.float64)
+    if centre.shape != (3,) or not np.all(np.isfinite(centre)):
+        raise ValueError("centre must be three finite numbers")
+    if np.any(centre - radius <= 0.0) or np.any(centre + radius >= room):
+        raise ValueError("the sphere must lie wholly inside the room")
+    if sources is not None and len(sources):
+        gap = np.sqrt(((np.asarray(sources, dtype=np.float64) - centre[None, :]) ** 2).sum(axis=1))
+        if gap.min() < 2.0 * radius:
+            raise ValueError(f"every source must be at least 2 radius = {2.0 * radius:.4g} m from the sphere's centre "
+                             f"(closest: {gap.min():.4g} m)")
+    return np.ascontiguousarray(centre), radius
+
+
+def binaural_directions(forward=(1.0, 0.0, 0.0), up=(0.0, 0.0, 1.0), ear_angle_deg: float = 100.0) -> np.ndarray:
+    """The two ear directions ``(2, 3)`` of a spherical head, left first: ``forward`` (made perpendicular to ``up``) turned by
+    ``+ear_angle_deg`` and ``-ear_angle_deg`` about ``up``, right-handed, so that with ``up`` towards +z and ``forward`` towards
+    +x the left ear points towards +y.  100 degrees puts the ears a little behind the interaural axis, as on a head."""
+    forward, up = np.asarray(forward, dtype=np.float64), np.asarray(up, dtype=np.float64)
+    if forward.shape != (3,) or up.shape != (3,) or not (np.all(np.isfinite(forward)) and np.all(np.isfinite(up))):
+        raise ValueError("forward and up must be three finite numbers each")
+    if not (isinstance(ear_angle_deg, _REAL) and not isinstance(ear_angle_deg, bool) and np.isfinite(ear_angle_deg)
+            and 0.0 < ear_angle_deg < 180.0):
+        raise ValueError("ear_angle_deg must be between 0 and 180 degrees")
+    if not np.any(up != 0.0):
+        raise ValueError("up must not be the zero vector")
+    up = up / np.sqrt((up * up).sum())
+    forward = forward - (forward @ up) * up
+    norm = np.sqrt((forward * forward).sum())
+    if not norm > 1e-12:
+        raise ValueError("forward must not be parallel to up")
+    forward = forward / norm
+    side = np.cross(up, forward)
+    angle = np.deg2rad(float(ear_angle_deg))
+    return np.stack([np.cos(angle) * forward + np.sin(angle) * side, np.cos(angle) * forward - np.sin(angle) * side])
+
+
+def shoebox_sphere_irs_device(renderer, room, betas, sources, centre, directions, radius: float, ir_len: int, sample_rate: float,
+                              c: float = SPEED_OF_SOUND, max_order: Optional[int] = None, tail: Optional[ShoeboxTail] = None,
+                              source_id0: int = 0, capsule_id0: int = 0, n_orders: Optional[int] = None, half: Optional[int] = None,
+                              workspace_cap: int = BAND_WORKSPACE_CAP, source_patterns=None, air=None):
+    """``shoebox_irs_device`` for the ``C`` capsules of unit directions ``directions`` (C, 3) on a RIGID SPHERE of ``radius`` metres
+    at ``centre``: a rigid-sphere array or the two ears of a spherical head (``binaural_directions``); ``al_ism_shoebox_sphere``,
+    DESIGN.md "Shoebox IRs: rigid-sphere receivers".  Returns what ``shoebox_irs_device`` returns, the rows in the order of
+    ``directions``.  Every image reaches the sphere as a plane wave (a far-field model: the sphere lies wholly inside the room and
+    every source is at least ``2 radius`` from its centre, ValueError) and is filtered per Legendre order by ``sphere_filters(radius,
+    sample_rate, c, n_orders, half)``, which is uploaded with a float64 workspace as the band call's.  ``betas``: six broadband
+    coefficients (not yet together with bands).  With ``tail`` the noise goes through ``sphere_diffuse_filter`` under the omni
+    envelope of each source; rows are independent draws.  ``source_patterns`` and ``air`` as in ``shoebox_irs_device``."""
+    room, betas, sources, _, ir_len, fs, c, order = check_arguments(room, betas, sources, np.atleast_2d(np.asarray(centre, dtype=np.float64)),
+                                                                    ir_len, sample_rate, c, max_order, tail, None, None, source_patterns, air)
+    centre, radius = check_sphere(room, centre, radius, sources)
+    directions = check_directions(directions)
+    if isinstance(workspace_cap, (bool, np.bool_)) or not isinstance(workspace_cap, (int, np.integer)) or workspace_cap < 0:
+        raise ValueError("workspace_cap must be an integer >= 0 (bytes)")
+    table = sphere_filters(radius, fs, c, n_orders, half)
+    n_orders, half = table.shape[0], (table.shape[1] - 1) // 2
+    n, n_cap, pitch = len(sources), len(directions), pitch_of(ir_len)
+    if tail is not None:
+        for name, v, count in (("source_id0", source_id0, n), ("capsule_id0", capsule_id0, n_cap)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0 or int(v) + count > 1 << 32:
+                raise ValueError(f"{name} must be an integer >= 0 with {name} + count <= 2^32")
+    mem, lib = renderer.mem, renderer.lib
+    mix, fade = (-1, 0) if tail is None else tail_samples(tail, room, fs, c)
+    spat = None if source_patterns is None else check_source_patterns(source_patterns, n)
+    air = float(check_air(0.0 if air is None else air)[0])
+    per_pair = lib.call("al_ism_shoebox_sphere_workspace_bytes", n_orders, half, ir_len, mix, fade)
+    if per_pair <= 0:
+        raise ValueError(f"al_ism_shoebox_sphere_workspace_bytes refused {n_orders} orders, half = {half}, ir_len = {ir_len}")
+    pairs_per_pass = max(1, min(n * n_cap, int(workspace_cap) // per_pair))
+    workspace = mem.empty(pairs_per_pass * per_pair // 8, dtype=np.float64)
+    keep = [mem.upload(sources.reshape(-1)), mem.upload(directions.reshape(-1)), mem.upload(table.reshape(-1))]
+    spat_ptr = diffuse_ptr = env_ptr = 0
+    n_knots = seed = 0
+    if spat is not None:
+        keep.append(mem.upload(spat.reshape(-1)))
+        spat_ptr = mem.ptr(keep[-1])
+    if tail is not None:
+        keep.append(mem.upload(sphere_diffuse_filter(radius, fs, c, n_orders, half)))
+        diffuse_ptr = mem.ptr(keep[-1])
+        tables = {}      # one quadrature per distinct source pattern: the omni law of tail_envelope
+        for key in ([b""] * n if spat is None else [row.tobytes() for row in spat]):
+            if key not in tables:
+                tables[key] = tail_envelope(room, betas, ir_len, fs, mix, c, tail.rt60, None,
+                                            None if spat is None else np.frombuffer(key, dtype=np.float64), air)
+        ln_env = np.stack([tables[b"" if spat is None else row.tobytes()] for row in (range(n) if spat is None else spat)])
+        keep.append(mem.upload(ln_env.reshape(-1)))
+        env_ptr, n_knots, seed = mem.ptr(keep[-1]), ln_env.shape[1], int(tail.seed)
+    out = mem.empty(n_cap * n * pitch)
+    lib.call("al_ism_shoebox_sphere", mem.ptr(keep[0]), n, spat_ptr, centre.ctypes.data_as(ct.POINTER(ct.c_double)), mem.ptr(keep[1]), n_cap,
+             room.ctypes.data_as(ct.POINTER(ct.c_double)), betas.ctypes.data_as(ct.POINTER(ct.c_double)), air, mem.ptr(keep[2]), n_orders, half,
+             diffuse_ptr, c, fs, order, ir_len, pitch, mix, fade, seed, int(source_id0), int(capsule_id0), env_ptr, n_knots,
+             mem.ptr(workspace), pairs_per_pass * per_pair, mem.ptr(out), mem.stream())
     return out, (n * pitch, pitch), ir_len
 
 

@@ -732,6 +732,37 @@ int al_ism_shoebox_bands_src(const double *sources, int32_t n_sources, const dou
                              int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env,
                              int32_t n_knots, void *workspace, int64_t workspace_bytes, float *out, al_stream_t stream);
 
+/* The rows of CAPSULES ON A RIGID SPHERE of centre `centre` (HOST, 3 numbers) with the unit directions `directions` (float64 DEVICE
+ * table (n_capsules, 3), room axes): a rigid-sphere array or the ears of a spherical head (DESIGN.md "Shoebox IRs: rigid-sphere
+ * receivers").  Images are taken relative to the centre: R = image - centre, d = |R|, u = R / d, tau = d fs / c, amplitude A as in
+ * al_ism_shoebox_src with omni capsules (source_patterns: DEVICE (n_sources, 4) or NULL; air in Np/m).  Each image reaches the sphere
+ * as a plane wave from u.  With mu = clamp(n_c . u, -1, 1) and the Legendre recurrence in float64, in this order,
+ *   P_0 = 1,  P_1 = mu,  P_{l+1} = ((2 l + 1) mu P_l - l P_{l-1}) / (l + 1),
+ *   y_l[s] = sum over the images of A P_l(mu) tap(s - tau)  at every integer s in [-half, y_end + half),  l = 0 .. n_orders - 1,
+ *   y(t)   = sum_l sum_{j = -half .. half} filters[l][j + half] y_l[t - j]   (float64, l ascending, then j ascending),
+ * out = float32(y(t)), pads +0.  filters: float64 DEVICE table (n_orders, 2 half + 1), the radial FIRs of the sphere
+ * (shoebox.sphere_filters; any table is taken: the radius lives in it alone).  Tap shape, reach, order rule, beta = 0 rule and the
+ * canonical image order are al_ism_shoebox's.  mix < 0: no tail (y_end = ir_len; fade, seed, the ids, ln_env, n_knots and diffuse are
+ * ignored).  mix >= 0: the tail of al_ism_shoebox_bands_tail with ONE band whose filter is `diffuse` (float64 DEVICE, 2 half + 1 taps:
+ * shoebox.sphere_diffuse_filter) and whose knots are ln_env, a DEVICE table (n_sources, n_knots): y_end = min(ir_len, M + F),
+ *   n(t) = ((1 - p) exp(ln_env[n][k]) + p exp(ln_env[n][k + 1])) sum_j diffuse[j + half] g(t - j),  out = float32(w_e y(t) + w_l n(t)),
+ * row (c, n) drawing as source source_id0 + n at capsule capsule_id0 + c.  With mix >= ir_len the output has the bits of mix < 0; omni
+ * source rows and air == 0 give the bits of NULL and 0.  A row's bits depend on the room, the pair, the direction, the tables, half
+ * and n_orders (and the seed and ids) alone, not on n_capsules, n_sources, the pitch or the workspace size.
+ * workspace: DEVICE, 16-byte aligned, workspace_bytes >= al_ism_shoebox_sphere_workspace_bytes(n_orders, half, ir_len, mix, fade) (one
+ * pair: n_orders float64 rows of y_end + 2 half samples rounded up to 256); the pairs are walked in passes of what it holds, per pass
+ * ceil(n_orders / 4) gathers and one combine, then one launch for the samples past the split.  No allocation, no synchronisation, no
+ * atomics.
+ * AL_E_BADARG: everything al_ism_shoebox_src (omni capsules) and the band entries refuse for the arguments they share; n_orders outside
+ * 1 .. 64; half outside 1 .. 1024; a null centre, filters or (with a tail) diffuse; a centre that is not finite; the workspace rules. */
+int64_t al_ism_shoebox_sphere_workspace_bytes(int32_t n_orders, int32_t half, int32_t ir_len, int64_t mix, int64_t fade);
+int al_ism_shoebox_sphere(const double *sources, int32_t n_sources, const double *source_patterns, const double *centre,
+                          const double *directions, int32_t n_capsules, const double *L, const double *beta, double air,
+                          const double *filters, int32_t n_orders, int32_t half, const double *diffuse, double c, double fs,
+                          int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0,
+                          int64_t capsule_id0, const double *ln_env, int32_t n_knots, void *workspace, int64_t workspace_bytes, float *out,
+                          al_stream_t stream);
+
 /* dst[t] = src[t mod m] for t < n: np.pad(..., mode="wrap") of Augmentation.process. */
 int al_wrap_copy(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream);
 
