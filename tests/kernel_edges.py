@@ -92,7 +92,7 @@ def assert_bits_equal(got, want, what=None):
     want = np.ascontiguousarray(want, dtype=got.dtype)
     assert got.shape == want.shape, (got.shape, want.shape, what)
     diff = np.flatnonzero(bits(got) != bits(want))
-    assert diff.size == 0, (what, f"{diff.size} elements differ, first at {int(diff[0])}: {got[diff[0]]!r} vs {want[diff[0]]!r}")
+    assert diff.size == 0, (what, f"{diff.size} elements differ, first at {int(diff[0])}: {got.flat[diff[0]]!r} vs {want.flat[diff[0]]!r}")
 
 
 def ulps(got, ref):
@@ -262,9 +262,10 @@ def run_frame_shuffle(r, n, frame_len, row_len, n_rows, shift=0, seed=4):
     assert_bits_equal(out.get(), np.resize(cat, n), ("frame_shuffle", n))
 
 
-def run_wrap_copy(r, m, n, shift=0, seed=5):
+def run_wrap_copy(r, m, n, shift=0, seed=5, guarded=None):
+    """``guarded``: another guarded-buffer class for the destination (tests/transfer_cases.py: page-locked host memory)."""
     x = signal(m, seed)
-    out = Guarded(r, n, shift=shift)
+    out = (guarded or Guarded)(r, n, shift=shift)
     src = dev(r, x)
     r.lib.call("al_wrap_copy", r.mem.ptr(src), m, out.ptr, n, r.mem.stream())
     assert_bits_equal(out.get(), np.resize(x, n), ("wrap_copy", m, n))
@@ -720,8 +721,9 @@ PCM_EDGES = np.array([0.0, -0.0, 1e-40, -1e-40, 0.5 / 32768, 1.5 / 32768, 2.5 / 
                       -32767.5 / 32768, -32768.0 / 32768, -32768.5 / 32768, -1.5, -np.inf], dtype=np.float32)
 
 
-def run_encode(r, n_capsules, n_samples, fmt, shift=0, seed=16):
-    """(C, T) -> (T, C) frames, bit-exact: float32 copies, PCM_16 = tests.conftest.pcm16 (libsndfile's clipping f2s)."""
+def run_encode(r, n_capsules, n_samples, fmt, shift=0, seed=16, guarded=None):
+    """(C, T) -> (T, C) frames, bit-exact: float32 copies, PCM_16 = tests.conftest.pcm16 (libsndfile's clipping f2s).
+    ``guarded``: another guarded-buffer class for the frames (tests/transfer_cases.py: page-locked host memory)."""
     rng = np.random.default_rng(seed)
     scene = rng.uniform(-1.05, 1.05, (n_capsules, n_samples)).astype(np.float32)
     flat = scene.reshape(-1)
@@ -729,7 +731,7 @@ def run_encode(r, n_capsules, n_samples, fmt, shift=0, seed=16):
     flat[:k] = PCM_EDGES[:k]
     flat[-k:] = PCM_EDGES[::-1][:k]
     dtype = np.int16 if fmt == _hip.FRAMES_PCM16 else np.float32
-    out = Guarded(r, n_capsules * n_samples, dtype=dtype, shift=shift)
+    out = (guarded or Guarded)(r, n_capsules * n_samples, dtype=dtype, shift=shift)
     d = dev(r, flat)
     r.lib.call("al_encode_frames", r.mem.ptr(d), n_capsules, n_samples, fmt, out.ptr, r.mem.stream())
     want = pcm16(scene.T) if fmt == _hip.FRAMES_PCM16 else scene.T

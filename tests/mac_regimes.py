@@ -179,9 +179,9 @@ def run_static_case(renderer, log2_block, code, k_mult, p_mult, C=3, E=2, seed=0
     return res
 
 
-def run_moving_case(renderer, log2_block, p_mult, n_irs, k_mult, expect_moving, C=2, E=2, seed=0, sr=48000):
-    """Moving events whose cross-fade windows are short against the block (sliding-window kernel) or, with
-    expect_moving == 0, too many partitions for it (tile kernel summing over streams)."""
+def moving_scene(log2_block, p_mult, n_irs, k_mult, C=2, E=2, seed=0, sr=48000):
+    """The scene of ``run_moving_case``: E moving events of about k_mult blocks over n_irs IRs of about p_mult partitions each.
+    Returns (clips, per-event IR tensors, specs, the microphone's (C, E * n_irs, Lir) tensor, the plan)."""
     B = 1 << log2_block
     rng = np.random.default_rng(7000 + 10 * log2_block + seed)
     La, Lir = int(round(k_mult * B)), int(round(p_mult * B))
@@ -196,6 +196,22 @@ def run_moving_case(renderer, log2_block, p_mult, n_irs, k_mult, expect_moving, 
         col += n_irs
     mic_ir = np.concatenate(irs, axis=1)
     pl = planning.plan_batch(specs, C, Lir, sr, log2_block=log2_block)
+    return clips, irs, specs, mic_ir, pl
+
+
+def check_moving_events(res, clips, irs, specs, sr=48000):
+    """Every row of every event of ``moving_scene`` against the oracle."""
+    for e in range(len(specs)):
+        want = orc.render_event(clips[e], irs[e].astype(np.float64), specs[e].snr, is_moving=True,
+                                duration=specs[e].duration, sr=sr)["spatial"]
+        check_event_rows(res, e, want)
+
+
+def run_moving_case(renderer, log2_block, p_mult, n_irs, k_mult, expect_moving, C=2, E=2, seed=0, sr=48000):
+    """Moving events whose cross-fade windows are short against the block (sliding-window kernel) or, with
+    expect_moving == 0, too many partitions for it (tile kernel summing over streams)."""
+    B = 1 << log2_block
+    clips, irs, specs, mic_ir, pl = moving_scene(log2_block, p_mult, n_irs, k_mult, C, E, seed, sr)
     batch = renderer.prepare(pl, clips, mic_ir)
     _, moving = mac_codes(renderer, batch)
     assert moving == expect_moving, moving
@@ -217,10 +233,7 @@ def run_moving_case(renderer, log2_block, p_mult, n_irs, k_mult, expect_moving, 
         untouched = np.isnan(h).all(axis=3)
         expected = np.arange(pl.n_partitions)[None, None, :] >= parts[:, None, None]
         assert np.array_equal(untouched, np.broadcast_to(expected, untouched.shape)) and not np.isnan(h[~untouched]).any()
-    for e in range(E):
-        want = orc.render_event(clips[e], irs[e].astype(np.float64), specs[e].snr, is_moving=True,
-                                duration=specs[e].duration, sr=sr)["spatial"]
-        check_event_rows(res, e, want)
+    check_moving_events(res, clips, irs, specs, sr)
     return res
 
 

@@ -513,6 +513,49 @@ def test_every_accumulate_instantiation_is_named_by_a_gpu_test():
     assert asserted <= have, sorted(asserted - have)
 
 
+def test_every_switch_that_selects_a_code_path_is_set_by_a_test():
+    """Every field of switches.Switches whose environment name (AL_ + the field's name in capitals) some module of the package
+    reads or documents must be named by a tests/*.py file: a switch is a code path that ships, and for most of them the switch is
+    the only way in."""
+    from dataclasses import fields
+
+    from audiblelight_amd import switches
+
+    def text_of(folder):
+        return {f: open(os.path.join(folder, f)).read() for f in sorted(os.listdir(folder)) if f.endswith(".py")}
+
+    package, tests = text_of(os.path.join(ROOT, "audiblelight_amd")), text_of(os.path.join(ROOT, "tests"))
+    names = ["AL_" + f.name.upper() for f in fields(switches.Switches)]
+    assert len(names) >= 13
+    for name in names:                                        # the naming rule itself: from_env reads exactly these
+        assert re.search(r'"%s"' % name, package["switches.py"]), f"{name}: Switches.from_env does not read it"
+    word = lambda name, text: re.search(r"\b%s\b" % name, text) is not None  # noqa: E731  (whole names: one switch's name is the start of another's)
+    unset = [name for name in names if any(word(name, t) for t in package.values()) and not any(word(name, t) for t in tests.values())]
+    assert not unset, f"switches no test sets: {unset}"
+
+
+def test_ambience_rng_switch_is_the_default_of_new_ambiences(monkeypatch):
+    """AL_AMBIENCE_RNG=device makes ``Ambience(...)`` draw on the GPU unless told otherwise (examples/render_dataset.py sets it);
+    an explicit ``rng=`` wins, anything but host / device is refused when the switches are parsed."""
+    from audiblelight_amd import ambience as amb
+    from tests.conftest import set_switch
+
+    make = lambda **kw: amb.Ambience(2, 0.1, alias="a", noise="white", sample_rate=8000, **kw)  # noqa: E731
+    set_switch(monkeypatch, "AL_AMBIENCE_RNG", None)
+    assert amb.default_rng_mode() == "host" and make().rng == "host" and make(rng="device").rng == "device"
+    set_switch(monkeypatch, "AL_AMBIENCE_RNG", "device")
+    assert amb.default_rng_mode() == "device" and make().rng == "device" and make(rng="host").rng == "host"
+    with pytest.raises(ValueError, match="AL_AMBIENCE_RNG"):
+        set_switch(monkeypatch, "AL_AMBIENCE_RNG", "gpu")
+
+
+def test_pack_audio_thread_pool_branch():
+    """Renderer.pack_audio with more than 2^22 clip samples (a few threads instead of one loop): tests/transfer_cases.py."""
+    from tests import transfer_cases as tc
+
+    tc.run_pack_audio_threaded()
+
+
 def test_accumulate_dispatch_reproduces_the_recorded_sweep():
     """al_spectral_mac_variant over every descriptor field plan_mac reads (tests/mac_regimes.py::SWEEP_AXES: both sides of every
     threshold, every combination of the static / only-static flags and the three A/B switches) against the recording made before the
