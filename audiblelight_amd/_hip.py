@@ -229,6 +229,8 @@ SYMBOLS = {
                                      ct.POINTER(ct.c_double), ct.c_double, _P, ct.c_int32, ct.c_int32, _P, ct.c_double, ct.c_double,
                                      ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int64, ct.c_int64, ct.c_uint64, ct.c_int64, ct.c_int64, _P,
                                      ct.c_int32, _P, ct.c_int64, _P, _S]),
+    "al_ir_metrics_workspace_bytes": (ct.c_int64, [ct.c_int32, ct.c_int32, ct.c_int32]),
+    "al_ir_metrics": (ct.c_int, [_P, ct.c_int32, ct.c_int32, ct.c_int64, ct.c_int64, ct.c_int32, ct.c_double, _P, ct.c_int64, _P, _P, _S]),
     "al_noise_workspace_floats": (ct.c_int64, [ct.c_int32, ct.c_int64]),
     "al_noise_irfft": (ct.c_int, [_P, _P, _P, ct.c_int32, ct.c_int64, ct.c_float, _P, _P, _S]),
     "al_noise_irfft_seeded": (ct.c_int, [ct.c_uint64, _P, ct.c_int32, ct.c_int64, ct.c_float, _P, _P, _S]),
@@ -249,6 +251,7 @@ SOS_MAX_SECTIONS = 16   # AL_SOS_MAX_SECTIONS: second-order sections per al_fx_s
 FXB_SOS, FXB_CHORUS, FXB_PHASER, FXB_DEEMPH = 1, 2, 3, 4   # AL_FXB_*: the kinds of a batched FX launch (al_fx_batch_*)
 FXB_COMPRESSOR, FXB_LIMITER = 6, 7                         # 5 is not a kind
 DYN_TILE = 1024         # samples per tile of k_fx_dynamics (csrc/al_dynfx.h DYN_TILE)
+IRM_TILE = 1024         # samples per workgroup tile of al_ir_metrics (csrc/al_irmetrics.h IRM_TILE)
 PV_TILE = 32            # output frames per tile of the phase scan (csrc/al_stretchfx.h PV_TILE)
 FXB_JOBS = {FXB_SOS: AlFxSosJob, FXB_CHORUS: AlFxModJob, FXB_PHASER: AlFxModJob, FXB_DEEMPH: AlFxDeemphJob,
             FXB_COMPRESSOR: AlFxCompressorJob, FXB_LIMITER: AlFxLimiterJob}

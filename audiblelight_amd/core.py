@@ -295,6 +295,16 @@ class StaticIRState:
     def simulate(self) -> None:  # IRs are given, nothing to trace
         return None
 
+    def metrics(self, alias: Optional[str] = None, edc: bool = False, sample_rate: Optional[float] = None, renderer=None) -> dict:
+        """``{alias: acoustics.IRMetrics}`` of the tensors as they are (acoustics.ir_metrics: reverberation times, DRR, clarity per
+        row, measured on the device); ``sample_rate``: default the ``sample_rate`` of the metadata.  Not part of ``to_dict()``."""
+        from . import acoustics
+
+        rate = self.metadata.get("sample_rate") if sample_rate is None else sample_rate
+        if rate is None:
+            raise ValueError("this state knows no sample rate: give sample_rate")
+        return acoustics.state_metrics(self, rate, alias, edc, renderer)
+
 
 class ShoeboxIRState:
     """WorldState stand-in for a rectangular room whose IRs are generated on the device by the image-source method
@@ -519,6 +529,14 @@ class ShoeboxIRState:
 
     def get_irs(self):
         return self.irs
+
+    def metrics(self, alias: Optional[str] = None, edc: bool = False) -> dict:
+        """``{alias: acoustics.IRMetrics}`` of the generated tensors, measured where they lie (acoustics.ir_metrics: reverberation
+        times, DRR, clarity per row): nothing but the tables is downloaded.  As ``irs``: raises before ``simulate()``.  Not part
+        of ``to_dict()``."""
+        from . import acoustics
+
+        return acoustics.state_metrics(self, self.sample_rate, alias, edc)
 
     def to_dict(self) -> dict:   # worldstate.py:2330-2356 layout, with the room in place of the mesh
         d = dict(backend=self.name, sample_rate=self.sample_rate,

@@ -1,0 +1,534 @@
+// Room-acoustic metrics of an impulse-response tensor that lies in HBM (al_ir_metrics; DESIGN.md "IR metrics"): the Schroeder
+// backward integral E(t) of every row in float64 and, from it, the direct-to-reverberant ratio, the clarities C50 / C80, D50, the
+// centre time, the three decay fits EDT / T20 / T30 with their sample counts and the decay the row has room for; optionally the
+// curve itself at every 256th sample.  The definition is the header comment of al_ir_metrics in include/audiblelight_hip.h; what
+// is here is how it is summed.
+//
+// THE TILE.  A row is cut into tiles of IRM_TILE = 1024 samples, a tile into 4 sub-tiles of 256; a workgroup is ONE WAVE and lane i owns
+// the four samples 4 i .. 4 i + 3 of every sub-tile, so a sub-tile is one 16-byte load per lane and the wave reads 1 KiB in one piece.
+// Rows whose base is not 16-byte aligned take scalar loads (chosen per row).  Samples at and past ir_len are never read.  One wave per
+// workgroup: the LDS hand-overs below are ordered by the wave's own program order (hipcc drops the s_barrier of __syncthreads()), no
+// wave ever waits for another, and the schedule-perturbed builds still sleep around every hand-over.  The code is written for
+// IRM_WAVES waves; with one, the sums over the waves behind are empty.
+//
+// THE ORDER OF E(t) (irm_scan), every term float64, e = (double)h * (double)h exact:
+//   inside a thread   E3 = e3, E2 = e2 + E3, E1 = e1 + E2, E0 = e0 + E1                                  (per sub-tile)
+//   across a wave     the inclusive suffix scan of the threads' E0 in 6 doubling steps (x_l += x_{l + 2^s})
+//   across the waves  the totals of the waves behind this one, from the last backwards (none with one wave per workgroup)
+//   across sub-tiles  the totals of the sub-tiles behind this one, added from the last backwards
+//   across tiles      suffix[k] = suffix[k + 1] + total[k + 1] from the last tile backwards (k_irm_rows, one thread)
+//   E(t) = (own E_k + ((next lane's scan + waves behind) + sub-tiles behind)) + suffix[tile]
+// A tile's total is the value this gives at its first sample, so E(t) is the same expression wherever it is formed: in the first
+// pass (totals), the second (E(t0)) and the two kernels of the third (every sample).  All terms are >= 0, so a term e reaches E(t) through at most
+// 3 (thread) + 6 (wave) + 3 (waves) + 1 + 3 (a sub-tile's total) + 3 (sub-tiles) + 2 (the two outer additions) + 1 (suffix) = 22
+// additions inside its tile and one per tile behind it, each a relative rounding of 2^-53 of a partial sum no larger than E(t):
+// |E - E_exact| <= (22 + n_tiles) 2^-53 E to first order.
+//
+// THE PASSES (no atomics; every hand-over is the workspace between two launches of the stream, or LDS behind a barrier):
+//   k_irm_tiles    (row, tile)  the tile's total, max |h| with its first index, count of non-finite samples
+//   k_irm_rows     row          suffix over the tile totals, peak and t0 (first tile that reaches the maximum), E(t0) by re-reading the
+//                               tile that holds t0, the four thresholds
+//   k_irm_sums     (row, tile)  re-reads the tile, forms E(t) per sample; each sample decides from t alone which window it belongs to.
+//                               The tile's four window sums: workgroup reductions in a fixed shape (irm_block_sum); the knots.  The
+//                               four point values E(t0 + w_d + 1), E(t0 + w_50), E(t0 + w_80), E(L - 1) have one sample and so one
+//                               writer each.  A tile in front of every window whose knots nobody asked for leaves at once.
+//   k_irm_fits     (row, tile)  the fifteen sums of the three fits, each sample deciding from t and E(t) alone: only in the tiles that
+//                               reach past t0 and start above the -35 dB threshold (known from the stored total before anything is
+//                               read: every other workgroup leaves at once); log10 only for samples above that threshold.
+//   k_irm_columns  row          the tile partials, lane-strided and then a shuffle tree (an order that depends on the tile count
+//                               alone), and the 16 columns.
+// A row's numbers depend on its samples, ir_len and fs alone: not on its place in the tensor, the pitch, the strides or the other rows.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "al_common.h"
+#include "al_status.h"
+
+namespace al {
+
+constexpr int IRM_THREADS = 64;                    // one wave: its LDS hand-overs need no s_barrier
+constexpr int IRM_WAVES = IRM_THREADS / 64;
+constexpr int IRM_SUBS = 4;                        // sub-tiles of a tile
+constexpr int IRM_SUB = IRM_THREADS * 4;           // samples of a sub-tile
+constexpr int IRM_TILE = IRM_SUBS * IRM_SUB;       // samples of a tile
+constexpr int IRM_KNOT = 256;                      // samples between two knots of the curve (shoebox.n_knots_of)
+constexpr int IRM_COLS = 16;                       // columns of the table
+constexpr int IRM_HEAD = 4;                        // partials of a tile: sum (t - t0) e, D, early_50, early_80 ...
+constexpr int IRM_FIT = 15;                        // ... and n, sum u, sum u^2, sum y, sum u y of EDT, T20, T30
+constexpr int IRM_PART = IRM_HEAD + IRM_FIT;
+constexpr int IRM_OK = 0, IRM_SILENT = 1, IRM_BAD = 2;
+
+// E(t0) 10^(x/10) for x = -5, -10, -25, -35
+#define AL_IRM_M5 0.31622776601683794
+#define AL_IRM_M10 0.1
+#define AL_IRM_M25 0.0031622776601683794
+#define AL_IRM_M35 0.00031622776601683794
+
+struct IrmRow {          // what k_irm_rows leaves for the passes behind it
+  double e_t0;           // E(t0)
+  double thr[4];         // E(t0) 10^(x/10), x = -5, -10, -25, -35
+  double point[4];       // E(t0 + w_d + 1), E(t0 + w_50), E(t0 + w_80), E(L - 1): zeroed there, written by the sample that holds each
+  double energy, bad;    // E(0), count of non-finite samples
+  float peak;
+  int32_t t0, state, reserved;
+};
+
+struct IrmJob {
+  const float *irs;
+  int32_t n_sources, ir_len, n_tiles, n_knots;
+  int64_t stride_c, pitch, w_d, w_50, w_80;
+  double fs;
+  double *tile_total, *tile_suffix, *partials;   // (rows, n_tiles), (rows, n_tiles), (rows, n_tiles, IRM_PART)
+  IrmRow *rows;
+  float *tile_peak;                              // (rows, n_tiles)
+  int32_t *tile_arg, *tile_bad;
+  double *out, *edc;
+};
+
+inline int64_t irm_tiles(int32_t ir_len) { return ((int64_t)ir_len + IRM_TILE - 1) / IRM_TILE; }
+
+inline int64_t irm_workspace_bytes(int64_t rows, int32_t ir_len) {
+  const int64_t pairs = rows * irm_tiles(ir_len);
+  return pairs * (int64_t)((2 + IRM_PART) * sizeof(double) + sizeof(float) + 2 * sizeof(int32_t)) + rows * (int64_t)sizeof(IrmRow);
+}
+
+// round-half-even of x fs, kept below 2^31 (a window longer than any row is past the end of every row)
+inline int64_t irm_window(double seconds, double fs) {
+  const double w = nearbyint(seconds * fs);
+  return w < 2147483648.0 ? (int64_t)w : (int64_t)2147483648LL;
+}
+
+inline int irm_prepare(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len, double fs,
+                       void *workspace, int64_t workspace_bytes, double *out, double *edc, IrmJob *job) {
+  const char *entry = "al_ir_metrics";
+  if (!irs || !out || !workspace) return fail_arg(entry, "irs, out and workspace must not be null");
+  if (n_capsules < 1 || n_sources < 1 || ir_len < 1) return fail_arg(entry, "n_capsules, n_sources and ir_len must be >= 1");
+  if (pitch < ir_len) return fail_arg(entry, "pitch < ir_len");
+  if (pitch > INT64_MAX / n_sources || stride_c < (int64_t)n_sources * pitch) return fail_arg(entry, "stride_c < n_sources * pitch");
+  const int64_t rows = (int64_t)n_capsules * n_sources, tiles = irm_tiles(ir_len);
+  if (rows > 0x7fffffff) return fail_arg(entry, "more than 2^31 - 1 rows");
+  if (rows * tiles > 0x7fffffff) return fail_arg(entry, "more than 2^31 - 1 (row, tile) pairs");
+  if (!(fs > 0.0) || !(fs <= 1.7976931348623157e308)) return fail_arg(entry, "fs must be finite and positive");
+  if (((uintptr_t)workspace & 15) != 0) return fail_arg(entry, "workspace must be 16-byte aligned");
+  if (workspace_bytes < irm_workspace_bytes(rows, ir_len)) return fail_arg(entry, "workspace_bytes < al_ir_metrics_workspace_bytes(...)");
+  const int64_t pairs = rows * tiles;
+  job->irs = irs;
+  job->n_sources = n_sources; job->ir_len = ir_len; job->n_tiles = (int32_t)tiles; job->n_knots = (ir_len - 1) / IRM_KNOT + 2;
+  job->stride_c = stride_c; job->pitch = pitch;
+  job->w_d = irm_window(0.0025, fs); job->w_50 = irm_window(0.05, fs); job->w_80 = irm_window(0.08, fs);
+  job->fs = fs;
+  job->tile_total = static_cast<double *>(workspace);
+  job->tile_suffix = job->tile_total + pairs;
+  job->partials = job->tile_suffix + pairs;
+  job->rows = reinterpret_cast<IrmRow *>(job->partials + pairs * IRM_PART);
+  job->tile_peak = reinterpret_cast<float *>(job->rows + rows);
+  job->tile_arg = reinterpret_cast<int32_t *>(job->tile_peak + pairs);
+  job->tile_bad = job->tile_arg + pairs;
+  job->out = out; job->edc = edc;
+  return AL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- device side
+__device__ __forceinline__ const float *irm_row_base(const IrmJob &job, int64_t row) {
+  const int64_t c = row / job.n_sources, n = row % job.n_sources;
+  return job.irs + c * job.stride_c + n * job.pitch;
+}
+
+// the thread's 16 samples of the tile that starts at tile0: v[j][k] is sample tile0 + j IRM_SUB + 4 tid + k, 0 at and past L
+__device__ __forceinline__ void irm_load(const float *row, int64_t tile0, int64_t L, int tid, float (&v)[IRM_SUBS][4]) {
+  const bool wide = ((uintptr_t)row & 15) == 0;
+#pragma unroll
+  for (int j = 0; j < IRM_SUBS; ++j) {
+    const int64_t t = tile0 + (int64_t)j * IRM_SUB + 4 * tid;
+    if (wide && t + 4 <= L) {
+      const float4 q = *reinterpret_cast<const float4 *>(row + t);
+      v[j][0] = q.x; v[j][1] = q.y; v[j][2] = q.z; v[j][3] = q.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[j][k] = t + k < L ? row[t + k] : 0.f;
+    }
+  }
+}
+
+// E[j][k]: the sum of e over this sample and every later one of the tile, in the order of the head comment; returns the tile's total
+// (E of its first sample) to every thread.  lds: IRM_WAVES IRM_SUBS + 1 doubles of this call's own.
+__device__ __forceinline__ double irm_scan(const float (&v)[IRM_SUBS][4], double (&E)[IRM_SUBS][4], double *lds, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  double x[IRM_SUBS];
+#pragma unroll
+  for (int j = 0; j < IRM_SUBS; ++j) {
+    E[j][3] = (double)v[j][3] * (double)v[j][3];
+#pragma unroll
+    for (int k = 2; k >= 0; --k) E[j][k] = (double)v[j][k] * (double)v[j][k] + E[j][k + 1];
+    x[j] = E[j][0];
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+#pragma unroll
+    for (int j = 0; j < IRM_SUBS; ++j) {
+      const double o = __shfl_down(x[j], off, 64);
+      if (lane + off < 64) x[j] += o;
+    }
+  }
+  double behind[IRM_SUBS];                    // the scan of the next lane: what lies behind this thread inside its wave
+#pragma unroll
+  for (int j = 0; j < IRM_SUBS; ++j) {
+    const double o = __shfl_down(x[j], 1, 64);
+    behind[j] = lane < 63 ? o : 0.0;
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < IRM_SUBS; ++j) lds[wave * IRM_SUBS + j] = x[j];
+  }
+  __syncthreads();
+  double subs = 0.0;                          // the sub-tiles behind sub-tile j
+#pragma unroll
+  for (int j = IRM_SUBS - 1; j >= 0; --j) {
+    double waves = 0.0;                       // the waves behind this one
+    for (int w = IRM_WAVES - 1; w > wave; --w) waves += lds[w * IRM_SUBS + j];
+    const double add = (behind[j] + waves) + subs;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) E[j][k] += add;
+    double others = 0.0;
+    for (int w = IRM_WAVES - 1; w >= 1; --w) others += lds[w * IRM_SUBS + j];
+    subs += lds[j] + others;
+  }
+  if (tid == 0) lds[IRM_WAVES * IRM_SUBS] = E[0][0];
+  __syncthreads();
+  return lds[IRM_WAVES * IRM_SUBS];
+}
+
+// v[i] summed over the workgroup, in thread 0: a shuffle tree inside each wave, then the waves in order.  lds: IRM_WAVES N doubles of this
+// call's own.
+template <int N>
+__device__ __forceinline__ void irm_block_sum(double (&v)[N], double *lds, int tid) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] += __shfl_down(v[i], off, 64);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) lds[(tid >> 6) * N + i] = v[i];
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      double t = lds[i];
+      for (int w = 1; w < IRM_WAVES; ++w) t += lds[w * N + i];
+      v[i] = t;
+    }
+  }
+}
+
+// ---- pass 1: one workgroup per (row, tile)
+__global__ __launch_bounds__(IRM_THREADS) void k_irm_tiles(IrmJob job) {
+  __shared__ double scan_lds[IRM_WAVES * IRM_SUBS + 1];
+  __shared__ float peak_lds[IRM_WAVES];
+  __shared__ int32_t arg_lds[IRM_WAVES], bad_lds[IRM_WAVES];
+  const int tid = threadIdx.x;
+  const int64_t pair = blockIdx.x, row = pair / job.n_tiles, tile0 = (pair % job.n_tiles) * IRM_TILE, L = job.ir_len;
+  const float *base = irm_row_base(job, row);
+  float v[IRM_SUBS][4];
+  double E[IRM_SUBS][4];
+  irm_load(base, tile0, L, tid, v);
+  const double total = irm_scan(v, E, scan_lds, tid);
+  float peak = 0.f;
+  int32_t arg = (int32_t)tile0, bad = 0;       // samples past L are zeros with larger indices: they never win
+#pragma unroll
+  for (int j = 0; j < IRM_SUBS; ++j) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float a = fabsf(v[j][k]);
+      if (a > peak) {                          // strictly: the first of equal maxima stays
+        peak = a;
+        arg = (int32_t)(tile0 + j * IRM_SUB + 4 * tid + k);
+      }
+      bad += isfinite(v[j][k]) ? 0 : 1;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float p2 = __shfl_down(peak, off, 64);
+    const int32_t a2 = __shfl_down(arg, off, 64);
+    bad += __shfl_down(bad, off, 64);
+    if (p2 > peak || (p2 == peak && a2 < arg)) {
+      peak = p2;
+      arg = a2;
+    }
+  }
+  if ((tid & 63) == 0) {
+    peak_lds[tid >> 6] = peak;
+    arg_lds[tid >> 6] = arg;
+    bad_lds[tid >> 6] = bad;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < IRM_WAVES; ++w) {
+      if (peak_lds[w] > peak || (peak_lds[w] == peak && arg_lds[w] < arg)) {
+        peak = peak_lds[w];
+        arg = arg_lds[w];
+      }
+      bad += bad_lds[w];
+    }
+    job.tile_total[pair] = total;
+    job.tile_peak[pair] = peak;
+    job.tile_arg[pair] = arg;
+    job.tile_bad[pair] = bad;
+  }
+}
+
+// ---- pass 2: one workgroup per row
+__global__ __launch_bounds__(IRM_THREADS) void k_irm_rows(IrmJob job) {
+  __shared__ double scan_lds[IRM_WAVES * IRM_SUBS + 1];
+  __shared__ double suffix_lds;
+  __shared__ int32_t t0_lds, state_lds;
+  const int tid = threadIdx.x;
+  const int64_t row = blockIdx.x, first = row * job.n_tiles, L = job.ir_len;
+  IrmRow *rec = job.rows + row;
+  if (tid == 0) {
+    double s = 0.0;
+    for (int64_t k = job.n_tiles - 1; k >= 0; --k) {
+      job.tile_suffix[first + k] = s;
+      s += job.tile_total[first + k];
+    }
+    float peak = 0.f;
+    int32_t t0 = 0;
+    int64_t bad = 0;
+    for (int64_t k = 0; k < job.n_tiles; ++k) {
+      if (job.tile_peak[first + k] > peak) {
+        peak = job.tile_peak[first + k];
+        t0 = job.tile_arg[first + k];
+      }
+      bad += job.tile_bad[first + k];
+    }
+    const int32_t state = bad > 0 ? IRM_BAD : peak == 0.f ? IRM_SILENT : IRM_OK;
+    rec->energy = s;
+    rec->bad = (double)bad;
+    rec->peak = peak;
+    rec->t0 = t0;
+    rec->state = state;
+    rec->reserved = 0;
+    for (int i = 0; i < 4; ++i) rec->point[i] = rec->thr[i] = 0.0;
+    rec->e_t0 = 0.0;
+    t0_lds = t0;
+    state_lds = state;
+    suffix_lds = job.tile_suffix[first + t0 / IRM_TILE];
+  }
+  __syncthreads();
+  if (state_lds != IRM_OK) return;             // the whole workgroup: nothing of such a row is fitted
+  const int64_t t0 = t0_lds, tile0 = t0 / IRM_TILE * IRM_TILE;
+  float v[IRM_SUBS][4];
+  double E[IRM_SUBS][4];
+  irm_load(irm_row_base(job, row), tile0, L, tid, v);
+  irm_scan(v, E, scan_lds, tid);
+  const int64_t at = t0 - tile0;               // the one thread that holds t0
+  if ((at % IRM_SUB) / 4 == tid) {
+    const int j = (int)(at / IRM_SUB), k = (int)(at % 4);
+    double e_t0 = 0.0;
+#pragma unroll
+    for (int jj = 0; jj < IRM_SUBS; ++jj) {
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk)
+        if (jj == j && kk == k) e_t0 = E[jj][kk] + suffix_lds;
+    }
+    rec->e_t0 = e_t0;
+    rec->thr[0] = e_t0 * AL_IRM_M5;
+    rec->thr[1] = e_t0 * AL_IRM_M10;
+    rec->thr[2] = e_t0 * AL_IRM_M25;
+    rec->thr[3] = e_t0 * AL_IRM_M35;
+  }
+}
+
+// a sample index of the row as an offset from the tile's start, clamped to +-2^30: compared with offsets in [0, IRM_TILE) only
+__device__ __forceinline__ int irm_rel(int64_t t, int64_t tile0) {
+  const int64_t d = t - tile0;
+  return (int)(d < -(1 << 30) ? -(1 << 30) : d > (1 << 30) ? (1 << 30) : d);
+}
+
+// ---- pass 3: one workgroup per (row, tile)
+__global__ __launch_bounds__(IRM_THREADS) void k_irm_sums(IrmJob job) {
+  __shared__ double scan_lds[IRM_WAVES * IRM_SUBS + 1];
+  __shared__ double head_lds[IRM_WAVES * IRM_HEAD];
+  const int tid = threadIdx.x;
+  const int64_t pair = blockIdx.x, row = pair / job.n_tiles, tile = pair % job.n_tiles, tile0 = tile * IRM_TILE, L = job.ir_len;
+  const int64_t tile_end = tile0 + IRM_TILE < L ? tile0 + IRM_TILE : L;
+  float v[IRM_SUBS][4];
+  irm_load(irm_row_base(job, row), tile0, L, tid, v);       // in flight while the row's record is read
+  IrmRow *rec = job.rows + row;
+  double *part = job.partials + pair * IRM_PART;
+  const bool ok = rec->state == IRM_OK;
+  const int64_t t0 = rec->t0, t_r = t0 + job.w_d + 1, t_50 = t0 + job.w_50, t_80 = t0 + job.w_80;
+  const int64_t d_lo = t0 - job.w_d > 0 ? t0 - job.w_d : 0, d_hi = t0 + job.w_d;
+  const int64_t reach = t_80 > t_r ? t_80 : t_r;
+  const bool after = ok && tile_end > t0;                                       // sum (t - t0) e runs to the end of the row
+  const bool head = ok && tile_end > d_lo && tile0 <= reach;
+  if (!after && !head && !job.edc) {           // no window and no knot: nothing of the tile is used (the whole workgroup leaves)
+    if (tid < IRM_HEAD) part[tid] = 0.0;
+    return;
+  }
+  double E[IRM_SUBS][4];
+  const double suffix = job.tile_suffix[pair];
+  irm_scan(v, E, scan_lds, tid);
+  // everything below counts samples from the tile's start: i = t - tile0 in [0, IRM_TILE), the row's marks clamped to +-2^30 around it
+  const int n_valid = (int)(tile_end - tile0);
+  const int r_t0 = irm_rel(t0, tile0), r_r = irm_rel(t_r, tile0), r_50 = irm_rel(t_50, tile0), r_80 = irm_rel(t_80, tile0);
+  const int r_lo = irm_rel(d_lo, tile0), r_hi = irm_rel(d_hi, tile0), r_last = irm_rel(L - 1, tile0);
+  const double u0 = (double)(tile0 - t0);                                       // t - t0 = u0 + i, exact
+  double hs[IRM_HEAD] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int j = 0; j < IRM_SUBS; ++j) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = j * IRM_SUB + 4 * tid + k;
+      const double Et = E[j][k] + suffix;
+      if (i >= n_valid) continue;
+      if (job.edc && k == 0 && (tid & 63) == 0) job.edc[row * job.n_knots + (tile0 + i) / IRM_KNOT] = Et;
+      if (!ok) continue;
+      const double e = (double)v[j][k] * (double)v[j][k];
+      if (i == r_last) rec->point[3] = Et;
+      if (head) {                              // (uniform) the tiles the windows reach
+        if (i == r_r) rec->point[0] = Et;
+        if (i == r_50) rec->point[1] = Et;
+        if (i == r_80) rec->point[2] = Et;
+        if (i >= r_lo && i <= r_hi) hs[1] += e;
+        if (i >= r_t0 && i < r_50) hs[2] += e;
+        if (i >= r_t0 && i < r_80) hs[3] += e;
+      }
+      if (i >= r_t0) hs[0] += (u0 + (double)i) * e;
+    }
+  }
+  if (job.edc && tid == 0 && tile == job.n_tiles - 1) job.edc[row * job.n_knots + job.n_knots - 1] = 0.0;   // E(256 k) at 256 k >= L
+  if (after || head) irm_block_sum<IRM_HEAD>(hs, head_lds, tid);
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < IRM_HEAD; ++i) part[i] = after || head ? hs[i] : 0.0;
+  }
+}
+
+// ---- pass 3, the fits: one workgroup per (row, tile); all but the tiles in which a fit can have samples leave at once
+__global__ __launch_bounds__(IRM_THREADS) void k_irm_fits(IrmJob job) {
+  __shared__ double scan_lds[IRM_WAVES * IRM_SUBS + 1];
+  __shared__ double fit_lds[IRM_WAVES * IRM_FIT];
+  const int tid = threadIdx.x;
+  const int64_t pair = blockIdx.x, row = pair / job.n_tiles, tile0 = (pair % job.n_tiles) * IRM_TILE, L = job.ir_len;
+  const int64_t tile_end = tile0 + IRM_TILE < L ? tile0 + IRM_TILE : L;
+  const IrmRow *rec = job.rows + row;
+  double *part = job.partials + pair * IRM_PART + IRM_HEAD;
+  const int64_t t0 = rec->t0;
+  const double suffix = job.tile_suffix[pair], thr35 = rec->thr[3];
+  // E at the tile's first sample, the largest of the tile: the stored total is what the scan below returns, bit for bit
+  const bool fit = rec->state == IRM_OK && tile_end > t0 && job.tile_total[pair] + suffix > thr35;
+  if (!fit) {                                  // (uniform) wholly before t0 or wholly below -35 dB
+    if (tid < IRM_FIT) part[tid] = 0.0;
+    return;
+  }
+  float v[IRM_SUBS][4];
+  double E[IRM_SUBS][4];
+  irm_load(irm_row_base(job, row), tile0, L, tid, v);
+  irm_scan(v, E, scan_lds, tid);
+  const int n_valid = (int)(tile_end - tile0), r_t0 = irm_rel(t0, tile0);
+  const double u0 = (double)(tile0 - t0);
+  const double e_t0 = rec->e_t0, thr5 = rec->thr[0], thr10 = rec->thr[1], thr25 = rec->thr[2];
+  double ft[IRM_FIT];
+#pragma unroll
+  for (int i = 0; i < IRM_FIT; ++i) ft[i] = 0.0;
+#pragma unroll
+  for (int j = 0; j < IRM_SUBS; ++j) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i = j * IRM_SUB + 4 * tid + k;
+      const double Et = E[j][k] + suffix;
+      if (i >= n_valid || i < r_t0 || !(Et > thr35)) continue;
+      const double u = u0 + (double)i;
+      const double y = 10.0 * log10(Et / e_t0);
+      if (Et > thr10) {                        // EDT: no upper test
+        ft[0] += 1.0; ft[1] += u; ft[2] += u * u; ft[3] += y; ft[4] += u * y;
+      }
+      if (Et <= thr5) {
+        if (Et > thr25) {
+          ft[5] += 1.0; ft[6] += u; ft[7] += u * u; ft[8] += y; ft[9] += u * y;
+        }
+        ft[10] += 1.0; ft[11] += u; ft[12] += u * u; ft[13] += y; ft[14] += u * y;
+      }
+    }
+  }
+  irm_block_sum<IRM_FIT>(ft, fit_lds, tid);
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < IRM_FIT; ++i) part[i] = ft[i];
+  }
+}
+
+// one decay fit from its five sums: (seconds, or NaN)
+__device__ __forceinline__ double irm_fit(const double *s, double e_last, double thr_lo, double fs) {
+  const double n = s[0];
+  if (!(n >= 2.0) || !(e_last <= thr_lo)) return __builtin_nan("");
+  const double a = (n * s[4] - s[1] * s[3]) / (n * s[2] - s[1] * s[1]);
+  return a == 0.0 ? __builtin_nan("") : -60.0 / (a * fs);
+}
+
+__device__ __forceinline__ double irm_db(double num, double den) { return den == 0.0 ? __builtin_inf() : 10.0 * log10(num / den); }
+
+// ---- pass 4: one wave per row
+__global__ __launch_bounds__(64) void k_irm_columns(IrmJob job) {
+  const int lane = threadIdx.x;
+  const int64_t row = blockIdx.x;
+  const IrmRow *rec = job.rows + row;
+  const double *part = job.partials + row * job.n_tiles * IRM_PART;
+  double s[IRM_PART];
+#pragma unroll
+  for (int i = 0; i < IRM_PART; ++i) s[i] = 0.0;
+  if (rec->state == IRM_OK) {                  // (uniform)
+    for (int64_t k = lane; k < job.n_tiles; k += 64) {
+#pragma unroll
+      for (int i = 0; i < IRM_PART; ++i) s[i] += part[k * IRM_PART + i];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+      for (int i = 0; i < IRM_PART; ++i) s[i] += __shfl_down(s[i], off, 64);
+    }
+  }
+  if (lane != 0) return;
+  double *o = job.out + row * IRM_COLS;
+  const double nan = __builtin_nan("");
+  o[0] = rec->bad;
+  if (rec->state != IRM_OK) {
+    const bool silent = rec->state == IRM_SILENT;
+    o[1] = silent ? 0.0 : nan;
+    o[2] = silent ? 0.0 : nan;
+    o[3] = silent ? 0.0 : nan;
+    for (int i = 4; i < IRM_COLS; ++i) o[i] = nan;
+    return;
+  }
+  const double e_t0 = rec->e_t0, e_last = rec->point[3];
+  o[1] = rec->energy;
+  o[2] = (double)rec->t0;
+  o[3] = (double)rec->peak;
+  o[4] = irm_db(s[1], rec->point[0]);
+  o[5] = irm_db(s[2], rec->point[1]);
+  o[6] = irm_db(s[3], rec->point[2]);
+  o[7] = s[2] / e_t0;
+  o[8] = s[0] / (job.fs * e_t0);
+  o[9] = irm_fit(s + IRM_HEAD, e_last, rec->thr[1], job.fs);
+  o[10] = irm_fit(s + IRM_HEAD + 5, e_last, rec->thr[2], job.fs);
+  o[11] = irm_fit(s + IRM_HEAD + 10, e_last, rec->thr[3], job.fs);
+  o[12] = s[IRM_HEAD];
+  o[13] = s[IRM_HEAD + 5];
+  o[14] = s[IRM_HEAD + 10];
+  o[15] = 10.0 * log10(e_last / e_t0);
+}
+
+inline void launch_ir_metrics(const IrmJob &job, int64_t rows, hipStream_t stream) {
+  const unsigned pairs = (unsigned)(rows * job.n_tiles);
+  hipLaunchKernelGGL(k_irm_tiles, dim3(pairs), dim3(IRM_THREADS), 0, stream, job);
+  hipLaunchKernelGGL(k_irm_rows, dim3((unsigned)rows), dim3(IRM_THREADS), 0, stream, job);
+  hipLaunchKernelGGL(k_irm_sums, dim3(pairs), dim3(IRM_THREADS), 0, stream, job);
+  hipLaunchKernelGGL(k_irm_fits, dim3(pairs), dim3(IRM_THREADS), 0, stream, job);
+  hipLaunchKernelGGL(k_irm_columns, dim3((unsigned)rows), dim3(64), 0, stream, job);
+}
+
+}  // namespace al

@@ -29,6 +29,7 @@
 #include "al_dynfx.h"
 #include "al_fft.h"
 #include "al_ingest.h"
+#include "al_irmetrics.h"
 #include "al_ism.h"
 #include "al_ism_bands.h"
 #include "al_ism_sphere.h"
@@ -729,6 +730,20 @@ int al_ism_shoebox_sphere(const double *sources, int32_t n_sources, const double
     return rc;
   al::launch_ism_shoebox_sphere(job, mix >= 0, (hipStream_t)stream);
   return check_launch("k_ism_sphere");
+}
+
+// ---- room-acoustic metrics of an IR tensor where it lies: DESIGN.md "IR metrics"
+int64_t al_ir_metrics_workspace_bytes(int32_t n_capsules, int32_t n_sources, int32_t ir_len) {
+  if (n_capsules < 1 || n_sources < 1 || ir_len < 1) return 0;
+  return al::irm_workspace_bytes((int64_t)n_capsules * n_sources, ir_len);
+}
+
+int al_ir_metrics(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len, double fs,
+                  void *workspace, int64_t workspace_bytes, double *out, double *edc, al_stream_t stream) {
+  al::IrmJob job;
+  if (int rc = al::irm_prepare(irs, n_capsules, n_sources, stride_c, pitch, ir_len, fs, workspace, workspace_bytes, out, edc, &job)) return rc;
+  al::launch_ir_metrics(job, (int64_t)n_capsules * n_sources, (hipStream_t)stream);
+  return check_launch("k_irm_columns");
 }
 
 int al_resample_poly(const float *x, int32_t rows, int64_t n_in, const float *taps, int32_t half_len, int32_t up, int32_t down,

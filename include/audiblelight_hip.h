@@ -763,6 +763,41 @@ int al_ism_shoebox_sphere(const double *sources, int32_t n_sources, const double
                           int64_t capsule_id0, const double *ln_env, int32_t n_knots, void *workspace, int64_t workspace_bytes, float *out,
                           al_stream_t stream);
 
+/* ROOM-ACOUSTIC METRICS of an IR tensor where it lies (DESIGN.md "IR metrics").  irs: float32 DEVICE tensor h[c, n, t], c < n_capsules,
+ * n < n_sources, t < ir_len = L >= 1, element c * stride_c + n * pitch + t (floats; pitch >= L, stride_c >= n_sources * pitch: what
+ * al_ism_shoebox* write and what a view into a larger tensor has).  Samples [L, pitch) are never read.  fs > 0 is the sample rate.
+ * The window lengths are integers formed once on the host, round-half-even: w_d = rint(0.0025 fs), w_50 = rint(0.05 fs),
+ * w_80 = rint(0.08 fs) (each kept at 2^31 at the most).  Per row, everything in float64:
+ *   e[t] = (double)h[t] * (double)h[t] (exact);  E(t) = sum_{u = t}^{L-1} e[u], E(t) = 0 for t >= L  (Schroeder's backward integral)
+ *   bad = number of non-finite samples;  peak = max_t |h[t]|;  t0 = the smallest t with |h[t]| == peak;  energy = E(0)
+ *   D = sum of e[t] over max(0, t0 - w_d) <= t <= min(L - 1, t0 + w_d) (summed directly);  R = E(t0 + w_d + 1)
+ *   drr_db = 10 log10(D / R), +inf when R == 0
+ *   X in {50, 80}: early_X = sum of e[t] over t0 <= t < min(L, t0 + w_X) (summed directly), late_X = E(t0 + w_X),
+ *                  cX_db = 10 log10(early_X / late_X), +inf when late_X == 0
+ *   d50 = early_50 / E(t0);   ts = sum_{t >= t0} (t - t0) e[t] / (fs E(t0))  (centre time, seconds)
+ *   three decay fits over (hi, lo) dB: EDT (0, -10), T20 (-5, -25), T30 (-5, -35):
+ *     S = { t in [t0, L) : E(t) > E(t0) 10^(lo/10) and (hi == 0 or E(t) <= E(t0) 10^(hi/10)) },  n = |S|
+ *     valid when n >= 2 and E(L - 1) <= E(t0) 10^(lo/10) (the decay reaches lo inside the row), else the time is NaN
+ *     ordinary least squares of y_t = 10 log10(E(t) / E(t0)) on u = t - t0 over S:
+ *     a = (n sum(u y) - sum(u) sum(y)) / (n sum(u^2) - sum(u)^2),  RT = -60 / (a fs) seconds, a == 0 gives NaN
+ *     (EDT has no upper test: with one, sample t0 would sit exactly on its threshold)
+ *   dyn_db = 10 log10(E(L - 1) / E(t0)): the decay the row has room for (-inf when the last sample is zero)
+ *   a silent row (peak == 0): bad = energy = peak = t0 = 0, NaN in every other column;  a row with bad > 0: NaN in every column but bad
+ * NO NOISE-FLOOR COMPENSATION (no Lundeby truncation, no subtraction): a measured IR with a noise floor reads long; dyn_db says so.
+ * out: float64 DEVICE table (rows, 16), row = c * n_sources + n, columns in this order:
+ *   bad, energy, t0, peak, drr_db, c50_db, c80_db, d50, ts, edt, t20, t30, n_edt, n_t20, n_t30, dyn_db
+ * edc: NULL, or a float64 DEVICE table (rows, n_knots), n_knots = (L - 1) / 256 + 2: edc[row][k] = E(256 k), so the last knot is 0 (of a
+ * row with non-finite samples: what the sum gives, NaN or inf in front of them).  The table has the same bits with and without it.
+ * workspace: DEVICE, 16-byte aligned, workspace_bytes >= al_ir_metrics_workspace_bytes(n_capsules, n_sources, ir_len) (0 for extents
+ * below 1).  Four launches on `stream`: the tensor is read twice (tiles in front of every window with edc == NULL: once).  Every sum is
+ * float64 in an order that depends on ir_len alone (csrc/al_irmetrics.h), so a row's 16 columns and knots have the same bits alone,
+ * among other rows, at any pitch or stride_c, and in two runs.  No allocation, no synchronisation, no atomics.
+ * AL_E_BADARG: null irs, out or workspace; an extent below 1; pitch < ir_len; stride_c < n_sources * pitch; more than 2^31 - 1 rows or
+ * (row, 1024-sample tile) pairs; fs not finite or not positive; a workspace that is too small or not 16-byte aligned. */
+int64_t al_ir_metrics_workspace_bytes(int32_t n_capsules, int32_t n_sources, int32_t ir_len);
+int al_ir_metrics(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len, double fs,
+                  void *workspace, int64_t workspace_bytes, double *out, double *edc, al_stream_t stream);
+
 /* dst[t] = src[t mod m] for t < n: np.pad(..., mode="wrap") of Augmentation.process. */
 int al_wrap_copy(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream);
 
