@@ -54,6 +54,12 @@
 // the exp is evaluated.  The omni pattern (or a null table) and m = 0 give gs = 1 + 0 / d = 1 and exp(x - 0) = exp(x): the bits of
 // the plain kernels.  With a tail every (row, source) pair reads a knot table of its own
 // (IsmTail::env_src_stride).  The instantiations without SRC are the kernels as they were.
+//
+// THE HOST SIDE.  The five point-receiver entries (al_ism_shoebox, _tail, _dir, _dir_tail, _src) share ism_images_prepare, which
+// turns their arguments into the kernels' job (no pattern table: omni capsules; null source patterns and air 0: no source side;
+// mix < 0: no tail), and launch_ism_images, which picks the image kernel by (patterns, K, TAIL, SRC) and adds k_ism_tail.  An entry
+// states what it requires beyond that.  ism_prepare is the part every shoebox entry shares (al_ism_bands.h and al_ism_sphere.h call
+// it too), ism_tail_prepare and ism_source_prepare the tail's and the source side's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -514,21 +520,16 @@ inline int ism_prepare(const double *sources, int32_t n_sources, const double *c
   return AL_OK;
 }
 
-inline void launch_ism_shoebox(const IsmJob &job, hipStream_t stream) {
-  const int64_t groups = (int64_t)job.n_tiles * job.n_sources * job.n_capsules;
-  hipLaunchKernelGGL(k_ism_shoebox<false>, dim3((unsigned)groups), dim3(ISM_THREADS), 0, stream, job);
-}
-
 // the sample at which the image sum of a row with a tail ends: min(ir_len, M + F), for any mix and fade >= 0 (no overflow)
 inline int32_t ism_tail_y_end(int64_t mix, int64_t fade, int32_t ir_len) {
   return mix < ir_len && fade < ir_len && mix + fade < ir_len ? (int32_t)(mix + fade) : ir_len;
 }
 
-// al_ism_shoebox_tail's further arguments into a job ism_prepare has filled: the tail, the split, the two grids
+// the tail's arguments (mix >= 0: the entry or the prepare that calls this has seen to it) into a job ism_prepare has filled: the tail,
+// the split, the two grids; one knot table for every row and source (the strides 0)
 inline int ism_tail_prepare(int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env,
                             int32_t n_knots, IsmJob *job) {
   if (!ln_env) return fail(AL_E_BADARG, "al_ism_shoebox_tail: null envelope table");
-  if (mix < 0) return fail(AL_E_BADARG, "al_ism_shoebox_tail: mix must be >= 0");
   if (fade < 1) return fail(AL_E_BADARG, "al_ism_shoebox_tail: fade must be >= 1");
   if (source_id0 < 0 || capsule_id0 < 0) return fail(AL_E_BADARG, "al_ism_shoebox_tail: source_id0 and capsule_id0 must be >= 0");
   if (source_id0 + job->n_sources > 0x100000000ll || capsule_id0 + job->n_capsules > 0x100000000ll)
@@ -553,13 +554,6 @@ inline int ism_tail_prepare(int64_t mix, int64_t fade, uint64_t seed, int64_t so
   if ((int64_t)tail.tail_blocks * job->n_sources * job->n_capsules > 0x7fffffff)
     return fail(AL_E_BADARG, "al_ism_shoebox_tail: more than 2^31 - 1 workgroups (spans of 4096 samples x pairs): split the call");
   return AL_OK;
-}
-
-inline void launch_ism_shoebox_tail(const IsmJob &job, hipStream_t stream) {
-  const int64_t pairs = (int64_t)job.n_sources * job.n_capsules;
-  hipLaunchKernelGGL(k_ism_shoebox<true>, dim3((unsigned)(job.n_tiles * pairs)), dim3(ISM_THREADS), 0, stream, job);
-  if (job.tail.tail_blocks > 0)
-    hipLaunchKernelGGL(k_ism_tail, dim3((unsigned)(job.tail.tail_blocks * pairs)), dim3(ISM_TAIL_THREADS), 0, stream, job);
 }
 
 // DIRECTIONAL RECEIVERS (al_ism_shoebox_dir, al_ism_shoebox_dir_tail; DESIGN.md "Shoebox IRs: directional receivers").  A call takes
@@ -684,51 +678,7 @@ __global__ __launch_bounds__(ISM_THREADS) ISM_WAVES_PER_SIMD(SRC && K == 4 ? 4 :
   }
 }
 
-// al_ism_shoebox_dir's arguments as the kernel's job (ism_prepare counts the image workgroups per POSITION; the rows are P K)
-inline int ism_dir_prepare(const double *sources, int32_t n_sources, const double *receivers, int32_t n_receivers, const double *patterns,
-                           int32_t n_channels, const double *L, const double *beta, double c, double fs, int32_t max_order,
-                           int32_t ir_len, int32_t pitch, float *out, IsmDirJob *dj) {
-  if (n_channels < 1 || n_channels > ISM_MAX_CHANNELS) return fail(AL_E_BADARG, "al_ism_shoebox_dir: n_channels must be in 1 .. 4");
-  if (!patterns) return fail(AL_E_BADARG, "al_ism_shoebox_dir: null pattern table");
-  if (int rc = ism_prepare(sources, n_sources, receivers, n_receivers, L, beta, c, fs, max_order, ir_len, pitch, out, &dj->base)) return rc;
-  if ((int64_t)n_receivers * n_channels > 0x7fffffff) return fail(AL_E_BADARG, "al_ism_shoebox_dir: more than 2^31 - 1 rows (n_receivers x n_channels)");
-  dj->patterns = patterns;
-  dj->n_positions = n_receivers;
-  dj->n_channels = n_channels;
-  dj->base.n_capsules = n_receivers * n_channels;
-  return AL_OK;
-}
-
-// al_ism_shoebox_dir_tail's further arguments: ism_tail_prepare over the P K rows, a knot table per row
-inline int ism_dir_tail_prepare(int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env,
-                                int32_t n_knots, IsmDirJob *dj) {
-  if (int rc = ism_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, &dj->base)) return rc;
-  dj->base.tail.env_stride = (uint32_t)n_knots;
-  return AL_OK;
-}
-
-template <bool TAIL, bool SRC = false>
-inline void launch_ism_dir_images(const IsmDirJob &dj, hipStream_t stream) {
-  const dim3 grid((unsigned)((int64_t)dj.base.n_tiles * dj.base.n_sources * dj.n_positions)), block(ISM_THREADS);
-  switch (dj.n_channels) {
-    case 1: hipLaunchKernelGGL((k_ism_shoebox_dir<1, TAIL, SRC>), grid, block, 0, stream, dj); break;
-    case 2: hipLaunchKernelGGL((k_ism_shoebox_dir<2, TAIL, SRC>), grid, block, 0, stream, dj); break;
-    case 3: hipLaunchKernelGGL((k_ism_shoebox_dir<3, TAIL, SRC>), grid, block, 0, stream, dj); break;
-    default: hipLaunchKernelGGL((k_ism_shoebox_dir<4, TAIL, SRC>), grid, block, 0, stream, dj); break;
-  }
-}
-
-inline void launch_ism_shoebox_dir(const IsmDirJob &dj, hipStream_t stream) { launch_ism_dir_images<false>(dj, stream); }
-
-inline void launch_ism_shoebox_dir_tail(const IsmDirJob &dj, hipStream_t stream) {
-  launch_ism_dir_images<true>(dj, stream);
-  const IsmJob &job = dj.base;
-  if (job.tail.tail_blocks > 0)
-    hipLaunchKernelGGL(k_ism_tail, dim3((unsigned)((int64_t)job.tail.tail_blocks * job.n_sources * job.n_capsules)), dim3(ISM_TAIL_THREADS),
-                       0, stream, job);
-}
-
-// SOURCE PATTERNS AND AIR (al_ism_shoebox_src).  The source side of a job that ism_prepare (or ism_dir_prepare) has filled
+// the source side of a job that ism_prepare has filled
 inline int ism_source_prepare(const double *source_patterns, double air, IsmJob *job) {
   if (!isfinite(air) || !(air >= 0.0)) return fail(AL_E_BADARG, "al_ism_shoebox_src: air must be finite and >= 0 (Np/m)");
   job->source_patterns = source_patterns;
@@ -736,49 +686,59 @@ inline int ism_source_prepare(const double *source_patterns, double air, IsmJob 
   return AL_OK;
 }
 
-// al_ism_shoebox_src's arguments as a directional job; patterns == nullptr (with n_channels == 1): omni capsules, dj->patterns null.
-// mix < 0: no tail, and the tail's arguments are not looked at.  ln_env: (rows, N, n_knots)
-inline int ism_src_prepare(const double *sources, int32_t n_sources, const double *source_patterns, const double *receivers,
-                           int32_t n_receivers, const double *patterns, int32_t n_channels, const double *L, const double *beta,
-                           double air, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade,
-                           uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, float *out,
-                           IsmDirJob *dj) {
-  if (!patterns) {
-    if (n_channels != 1) return fail(AL_E_BADARG, "al_ism_shoebox_src: a null pattern table (omni capsules) takes n_channels == 1");
-    if (int rc = ism_prepare(sources, n_sources, receivers, n_receivers, L, beta, c, fs, max_order, ir_len, pitch, out, &dj->base)) return rc;
-    dj->patterns = nullptr;
-    dj->n_positions = n_receivers;
-    dj->n_channels = 1;
-  } else if (int rc = ism_dir_prepare(sources, n_sources, receivers, n_receivers, patterns, n_channels, L, beta, c, fs, max_order, ir_len,
-                                      pitch, out, dj)) {
-    return rc;
-  }
+// THE PREPARE OF THE POINT-RECEIVER ENTRIES (al_ism_shoebox, _tail, _dir, _dir_tail, _src): their arguments as the kernels' job, 0 with
+// *dj filled or the error of the first bad argument.  patterns == nullptr (with n_channels == 1): omni capsules, dj->patterns null and
+// the rows are the positions.  source_patterns == nullptr and air == 0: no source side.  mix < 0: no tail, and the tail's arguments are
+// not looked at; else ln_env holds a knot table every env_row_stride knots from row to row and every env_src_stride from source to
+// source (0: one table serves them all).  What an entry requires beyond this (a pattern table, a tail) it states itself.
+inline int ism_images_prepare(const double *sources, int32_t n_sources, const double *source_patterns, const double *receivers,
+                              int32_t n_receivers, const double *patterns, int32_t n_channels, const double *L, const double *beta,
+                              double air, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade,
+                              uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots,
+                              int64_t env_row_stride, int64_t env_src_stride, float *out, IsmDirJob *dj) {
+  if (!patterns && n_channels != 1) return fail(AL_E_BADARG, "al_ism_shoebox_src: a null pattern table (omni capsules) takes n_channels == 1");
+  if (n_channels < 1 || n_channels > ISM_MAX_CHANNELS) return fail(AL_E_BADARG, "al_ism_shoebox_dir: n_channels must be in 1 .. 4");
+  // ism_prepare counts the image workgroups per POSITION; the rows are P K
+  if (int rc = ism_prepare(sources, n_sources, receivers, n_receivers, L, beta, c, fs, max_order, ir_len, pitch, out, &dj->base)) return rc;
+  if ((int64_t)n_receivers * n_channels > 0x7fffffff) return fail(AL_E_BADARG, "al_ism_shoebox_dir: more than 2^31 - 1 rows (n_receivers x n_channels)");
+  dj->patterns = patterns;
+  dj->n_positions = n_receivers;
+  dj->n_channels = n_channels;
+  dj->base.n_capsules = n_receivers * n_channels;
   if (int rc = ism_source_prepare(source_patterns, air, &dj->base)) return rc;
   if (mix >= 0) {
     if (int rc = ism_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, &dj->base)) return rc;
-    dj->base.tail.env_src_stride = (uint32_t)n_knots;
-    if ((int64_t)n_knots * n_sources > 0xffffffffll) return fail(AL_E_BADARG, "al_ism_shoebox_src: n_knots x n_sources must be below 2^32");
-    dj->base.tail.env_stride = (uint32_t)((int64_t)n_knots * n_sources);
+    if (env_row_stride > 0xffffffffll) return fail(AL_E_BADARG, "al_ism_shoebox_src: n_knots x n_sources must be below 2^32");
+    dj->base.tail.env_stride = (uint32_t)env_row_stride;
+    dj->base.tail.env_src_stride = (uint32_t)env_src_stride;
   }
   return AL_OK;
 }
 
-inline void launch_ism_shoebox_src(const IsmDirJob &dj, bool with_tail, hipStream_t stream) {
-  const IsmJob &job = dj.base;
-  const int64_t pairs = (int64_t)job.n_sources * job.n_capsules;
-  if (!dj.patterns) {
-    const dim3 grid((unsigned)(job.n_tiles * pairs)), block(ISM_THREADS);
-    if (with_tail)
-      hipLaunchKernelGGL((k_ism_shoebox<true, true>), grid, block, 0, stream, job);
-    else
-      hipLaunchKernelGGL((k_ism_shoebox<false, true>), grid, block, 0, stream, job);
-  } else if (with_tail) {
-    launch_ism_dir_images<true, true>(dj, stream);
-  } else {
-    launch_ism_dir_images<false, true>(dj, stream);
+// the image kernel of a job: k_ism_shoebox for omni capsules, k_ism_shoebox_dir<K> for a pattern table
+template <bool TAIL, bool SRC>
+inline void launch_ism_image_kernel(const IsmDirJob &dj, hipStream_t stream) {
+  const dim3 grid((unsigned)((int64_t)dj.base.n_tiles * dj.base.n_sources * dj.n_positions)), block(ISM_THREADS);
+  switch (dj.patterns ? dj.n_channels : 0) {
+    case 0: hipLaunchKernelGGL((k_ism_shoebox<TAIL, SRC>), grid, block, 0, stream, dj.base); break;
+    case 1: hipLaunchKernelGGL((k_ism_shoebox_dir<1, TAIL, SRC>), grid, block, 0, stream, dj); break;
+    case 2: hipLaunchKernelGGL((k_ism_shoebox_dir<2, TAIL, SRC>), grid, block, 0, stream, dj); break;
+    case 3: hipLaunchKernelGGL((k_ism_shoebox_dir<3, TAIL, SRC>), grid, block, 0, stream, dj); break;
+    default: hipLaunchKernelGGL((k_ism_shoebox_dir<4, TAIL, SRC>), grid, block, 0, stream, dj); break;
   }
+}
+
+// THE LAUNCH OF THE POINT-RECEIVER ENTRIES: the image kernel, with a tail over the tiles below the split, then k_ism_tail past it.
+// src: the instantiations with the source side (al_ism_shoebox_src takes them whatever its source table and air are)
+inline void launch_ism_images(const IsmDirJob &dj, bool with_tail, bool src, hipStream_t stream) {
+  if (with_tail)
+    src ? launch_ism_image_kernel<true, true>(dj, stream) : launch_ism_image_kernel<true, false>(dj, stream);
+  else
+    src ? launch_ism_image_kernel<false, true>(dj, stream) : launch_ism_image_kernel<false, false>(dj, stream);
+  const IsmJob &job = dj.base;
   if (with_tail && job.tail.tail_blocks > 0)
-    hipLaunchKernelGGL(k_ism_tail, dim3((unsigned)(job.tail.tail_blocks * pairs)), dim3(ISM_TAIL_THREADS), 0, stream, job);
+    hipLaunchKernelGGL(k_ism_tail, dim3((unsigned)((int64_t)job.tail.tail_blocks * job.n_sources * job.n_capsules)), dim3(ISM_TAIL_THREADS),
+                       0, stream, job);
 }
 
 }  // namespace al

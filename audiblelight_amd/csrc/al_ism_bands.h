@@ -11,7 +11,8 @@
 //     exactly 0, which adds +-0 to that band's sum: the bits of leaving the image out; an image dead in every band of the group is
 //     left out of the list), a lane forms the tap's shape once per (image, sample) and adds it into NB float64 accumulators.  B > 4
 //     takes ceil(B / 4) launches over groups of bands: each band's sum keeps the canonical order, so grouping cannot change bits.
-//     Every word of the workspace rows of the pass is written (zeros where no image reaches), none is read.
+//     Every word of the workspace rows of the pass is written (zeros where no image reaches), none is read.  The kernel constructs
+//     its variant and calls ism_workspace_rows, the body it shares with k_ism_sphere (al_ism_sphere.h).
 //   k_ism_band_combine  one workgroup of ONE WAVE per (pair, output tile of ISM_TILE samples), as every kernel of al_ism.h.  Band
 //     rows and phi_b go through LDS one band at a time, ISM_BAND_CHUNK taps at a time (2 ISM_BAND_CHUNK - 1 row samples serve a
 //     chunk: 6 KB of LDS whatever `half` is); a lane keeps ONE float64 accumulator for each of its ISM_PER_LANE outputs
@@ -36,7 +37,9 @@
 //     512, 1024: the smallest that holds `half`) sizes the LDS arrays; ISM_BAND_TAIL_MAX_HALF = 1024 is the cap with a tail.
 // The entry walks the pairs in PASSES of workspace_bytes / bytes_per_pair pairs, gather then combine, in order on the one stream: the
 // workspace is reused in stream order, nothing is allocated and nothing synchronises.  A row's bits do not depend on the pass it is
-// generated in: both kernels index the workspace by the pair's place in its pass only to find their own rows.
+// generated in: both kernels index the workspace by the pair's place in its pass only to find their own rows.  The pass loop
+// (ism_rows_passes), the checks of rows, half, workspace and tail (ism_rows_range, ism_rows_prepare) and the workspace's size
+// (ism_rows_workspace_bytes) serve the sphere call too; the three band entries go through one ism_bands_prepare (mix < 0: no tail).
 // SOURCE PATTERNS AND AIR WITH BANDS (al_ism_shoebox_bands_src; al_ism.h "THE SOURCE SIDE").  k_ism_bands<NB, true> takes IsmBandsSrc<NB>:
 // the source gain gs goes into the rigid-wall amplitude 1 / (4 pi d), and band b's gain becomes exp(sum k ln beta_b - m_b d) with
 // its own air coefficient m_b (IsmBandJob::air).  With a tail the knot tables are (N, B, n_knots): a table per (source, band),
@@ -121,36 +124,52 @@ struct IsmBandsSrc : IsmBands<NB> {
   }
 };
 
-template <int NB, bool SRC = false>
-__global__ __launch_bounds__(ISM_THREADS) void k_ism_bands(IsmBandJob bj) {
-  __shared__ IsmDirEntry<NB> list[ISM_DIR_LIST];
+// the pair of a workgroup of a pass whose grid has `tiles` workgroups per pair: its place in the pass, its source n and its row cap
+__device__ __forceinline__ int64_t ism_pass_pair(const IsmBandJob &bj, int tiles, int &n, int &cap) {
+  const int64_t local = blockIdx.x / (unsigned)tiles, pair = bj.pair0 + local;   // c * N + n
+  n = (int)(pair % bj.base.n_sources), cap = (int)(pair / bj.base.n_sources);
+  return local;
+}
+
+// THE WORKSPACE ROWS of one (pair, tile of W), what k_ism_bands and k_ism_sphere (al_ism_sphere.h) share: the V::NG rows
+// [band0, band0 + V::NG) of the pair are the gather of source n at receiver pos of `job` under the variant v over the shifted axis,
+// zeros in a tile that no tap reaches
+template <class V>
+__device__ __forceinline__ void ism_workspace_rows(const IsmBandJob &bj, const IsmJob &job, const V &v, int n, int pos) {
+  constexpr int NB = V::NG;
+  __shared__ typename V::Entry list[V::LIST];
   __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];
   __shared__ int wave_total[2];
-  const IsmJob &job = bj.base;
   const int tid = threadIdx.x;
   const int tile = (int)(blockIdx.x % (unsigned)bj.n_ws_tiles);
-  const int64_t local = blockIdx.x / (unsigned)bj.n_ws_tiles, pair = bj.pair0 + local;   // c * N + n
-  const int n = (int)(pair % job.n_sources), cap = (int)(pair / job.n_sources);
+  const int64_t local = blockIdx.x / (unsigned)bj.n_ws_tiles;
   // the tile in workspace words w and in samples s = w - half
   const int w_lo = tile * ISM_TILE, w = w_lo + tid;
   const int s_lo = w_lo - bj.half;
-  const int s_end = bj.y_end + bj.half;                // the band sums are formed for s < s_end
+  const int s_end = bj.y_end + bj.half;                // the row sums are formed for s < s_end
   const int t_hi = min(s_lo + ISM_TILE, s_end) - 1;
-  double *rows = bj.workspace + (local * bj.n_bands + bj.band0) * (int64_t)bj.W;   // band band0 of the pair; band k is k * W on
+  double *rows = bj.workspace + (local * bj.n_bands + bj.band0) * (int64_t)bj.W;   // row band0 of the pair; row k is k * W on
   if (t_hi < s_lo || t_hi < -ISM_HALF) {   // a tile past s_end, or so far below sample 0 that no tap reaches it (tau > 0)
     for (int k = 0; k < NB; ++k)
       for (int s = 0; s < ISM_PER_LANE; ++s) rows[(int64_t)k * bj.W + w + s * ISM_THREADS] = 0.0;
     return;
   }
   double acc[ISM_PER_LANE][NB] = {};
-  if constexpr (SRC)
-    ism_gather(job, IsmBandsSrc<NB>{{bj}, ism_source(job, n)}, n, cap, s_lo, t_hi, s_end, list, win_c, win_s, wave_total, acc);
-  else
-    ism_gather(job, IsmBands<NB>{bj}, n, cap, s_lo, t_hi, s_end, list, win_c, win_s, wave_total, acc);
+  ism_gather(job, v, n, pos, s_lo, t_hi, s_end, list, win_c, win_s, wave_total, acc);
 #pragma unroll
   for (int s = 0; s < ISM_PER_LANE; ++s)   // w + s * ISM_THREADS < W: the tile lies inside the row
 #pragma unroll
     for (int k = 0; k < NB; ++k) rows[(int64_t)k * bj.W + w + s * ISM_THREADS] = acc[s][k];
+}
+
+template <int NB, bool SRC = false>
+__global__ __launch_bounds__(ISM_THREADS) void k_ism_bands(IsmBandJob bj) {
+  int n, cap;
+  ism_pass_pair(bj, bj.n_ws_tiles, n, cap);
+  if constexpr (SRC)
+    ism_workspace_rows(bj, bj.base, IsmBandsSrc<NB>{{bj}, ism_source(bj.base, n)}, n, cap);
+  else
+    ism_workspace_rows(bj, bj.base, IsmBands<NB>{bj}, n, cap);
 }
 
 // draw s of row (cap, n); zero outside [0, ir_len)
@@ -354,26 +373,74 @@ inline int64_t ism_bands_layout(IsmBandJob *bj, int32_t y_end, int64_t workspace
   return per_pair;
 }
 
-// al_ism_shoebox_bands_workspace_bytes: bytes per pair, or AL_E_BADARG.  mix < 0: no tail (y_end = ir_len)
-inline int64_t ism_bands_workspace_bytes(int32_t n_bands, int32_t half, int32_t ir_len, int64_t mix, int64_t fade) {
-  if (n_bands < 1 || n_bands > ISM_MAX_BANDS) return fail(AL_E_BADARG, "al_ism_shoebox_bands: n_bands must be in 1 .. 8");
-  if (half < 1 || half > ISM_BAND_MAX_HALF) return fail(AL_E_BADARG, "al_ism_shoebox_bands: half must be in 1 .. 4096");
-  if (ir_len < 1) return fail(AL_E_BADARG, "al_ism_shoebox_bands: ir_len must be >= 1");
-  if (mix >= 0 && fade < 1) return fail(AL_E_BADARG, "al_ism_shoebox_bands: fade must be >= 1");
+// THE WORKSPACE FAMILIES (bands here, Legendre orders in al_ism_sphere.h) share their row checks, their workspace and their passes.
+// `entry` names the C entry in every refusal, `what` its row count ("n_bands", "n_orders")
+inline int ism_rows_range(const char *entry, const char *what, int32_t n_rows, int32_t max_rows, int32_t half, int32_t max_half) {
+  char why[64];
+  if (n_rows < 1 || n_rows > max_rows)
+    snprintf(why, sizeof(why), "%s must be in 1 .. %d", what, max_rows);
+  else if (half < 1 || half > max_half)
+    snprintf(why, sizeof(why), "half must be in 1 .. %d", max_half);
+  else
+    return AL_OK;
+  return fail_arg(entry, why);
+}
+
+// al_ism_shoebox_bands_workspace_bytes and al_ism_shoebox_sphere_workspace_bytes: bytes per pair, or AL_E_BADARG.  mix < 0: no tail
+// (y_end = ir_len)
+inline int64_t ism_rows_workspace_bytes(const char *entry, const char *what, int32_t n_rows, int32_t max_rows, int32_t half, int32_t max_half,
+                                        int32_t ir_len, int64_t mix, int64_t fade) {
+  if (int rc = ism_rows_range(entry, what, n_rows, max_rows, half, max_half)) return rc;
+  if (ir_len < 1) return fail_arg(entry, "ir_len must be >= 1");
+  if (mix >= 0 && fade < 1) return fail_arg(entry, "fade must be >= 1");
   IsmBandJob bj;
-  bj.n_bands = n_bands;
+  bj.n_bands = n_rows;
   bj.half = half;
   bj.base.n_tiles = 1;
   return ism_bands_layout(&bj, mix < 0 ? ir_len : ism_tail_y_end(mix, fade, ir_len), 0);
 }
 
-// al_ism_shoebox_bands's arguments as the kernels' job: 0 with *bj filled, or the error of the first bad argument
+// what both families check once ism_prepare has filled bj->base and n_bands and half are set (ism_rows_range): the mirror cells the
+// row sums reach, the workspace, with mix >= 0 the tail (ism_tail_prepare, the pitch and the grid of k_ism_band_tail), and the
+// workspace's size against the layout of a row that ends at y_end
+inline int ism_rows_prepare(const char *entry, const double *L, void *workspace, int64_t workspace_bytes, int64_t mix, int64_t fade,
+                            uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, IsmBandJob *bj) {
+  IsmJob &base = bj->base;
+  for (int i = 0; i < 3; ++i)   // the row sums reach `half` past the row
+    if (!(base.c * ((double)base.ir_len + (double)bj->half + 42.0) / base.fs / L[i] + 2.0 <= ISM_MAX_HALF_WIDTH))
+      return fail_arg(entry, "c (ir_len + half + 42) / fs spans more than 2^20 mirror cells of the room");
+  if (!workspace || ((uintptr_t)workspace & 15) != 0) return fail_arg(entry, "workspace must be 16-byte aligned and not null");
+  bj->workspace = (double *)workspace;
+  bj->band0 = 0;
+  bj->pair0 = 0;
+  bj->band_tail_blocks = 0;
+  int32_t y_end = base.ir_len;
+  if (mix >= 0) {   // a row with a tail needs y_end = min(ir_len, M + F) samples of every row sum only
+    if (int rc = ism_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, &base)) return rc;
+    if (base.pitch > 0x7fffffff - 2 * (ISM_BT_SPAN + ISM_BAND_TAIL_MAX_HALF))   // k_ism_band_tail counts span + half past the row in int32
+      return fail_arg(entry, "pitch must be at most 2^31 - 4097 with a tail");
+    y_end = base.tail.y_end;
+    bj->band_tail_blocks = base.tail.split < base.pitch ? (base.pitch - base.tail.split + ISM_BT_SPAN - 1) / ISM_BT_SPAN : 0;
+    if ((int64_t)bj->band_tail_blocks * base.n_sources * base.n_capsules > 0x7fffffff)
+      return fail_arg(entry, "more than 2^31 - 1 workgroups (spans of 1024 samples x pairs): split the call");
+  }
+  if (workspace_bytes < ism_bands_layout(bj, y_end, workspace_bytes)) {
+    char why[96];
+    snprintf(why, sizeof(why), "workspace smaller than %s_workspace_bytes (one pair)", entry);
+    return fail_arg(entry, why);
+  }
+  return AL_OK;
+}
+
+// the arguments of al_ism_shoebox_bands, _bands_tail and _bands_src as the kernels' job: 0 with *bj filled, or the error of the first
+// bad argument.  mix < 0: no tail, and the tail's arguments are not looked at; else ln_env is (B, n_knots)
 inline int ism_bands_prepare(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
                              const double *beta, int32_t n_bands, const double *filters, int32_t half, double c, double fs,
-                             int32_t max_order, int32_t ir_len, int32_t pitch, void *workspace, int64_t workspace_bytes, float *out,
-                             IsmBandJob *bj, bool with_tail = false) {
-  if (n_bands < 1 || n_bands > ISM_MAX_BANDS) return fail(AL_E_BADARG, "al_ism_shoebox_bands: n_bands must be in 1 .. 8");
-  if (half < 1 || half > ISM_BAND_MAX_HALF) return fail(AL_E_BADARG, "al_ism_shoebox_bands: half must be in 1 .. 4096");
+                             int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0,
+                             int64_t capsule_id0, const double *ln_env, int32_t n_knots, void *workspace, int64_t workspace_bytes, float *out,
+                             IsmBandJob *bj) {
+  if (int rc = ism_rows_range("al_ism_shoebox_bands", "n_bands", n_bands, ISM_MAX_BANDS, half, ISM_BAND_MAX_HALF)) return rc;
+  if (mix >= 0 && half > ISM_BAND_TAIL_MAX_HALF) return fail(AL_E_BADARG, "al_ism_shoebox_bands_tail: half must be in 1 .. 1024 with a tail");
   if (!beta) return fail(AL_E_BADARG, "al_ism_shoebox: null pointer");
   if (!filters) return fail(AL_E_BADARG, "al_ism_shoebox_bands: null filter table");
   double column[6];
@@ -387,68 +454,52 @@ inline int ism_bands_prepare(const double *sources, int32_t n_sources, const dou
   }
   for (int b = n_bands; b < ISM_MAX_BANDS; ++b)
     for (int i = 0; i < 6; ++i) bj->ln_beta[b][i] = 0.0, bj->beta_zero[b][i] = 0;
-  for (int i = 0; i < 3; ++i)   // the band sums reach `half` past the row
-    if (!(c * ((double)ir_len + (double)half + 42.0) / fs / L[i] + 2.0 <= ISM_MAX_HALF_WIDTH))
-      return fail(AL_E_BADARG, "al_ism_shoebox_bands: c (ir_len + half + 42) / fs spans more than 2^20 mirror cells of the room");
-  if (!workspace || ((uintptr_t)workspace & 15) != 0) return fail(AL_E_BADARG, "al_ism_shoebox_bands: workspace must be 16-byte aligned and not null");
   bj->filters = filters;
-  bj->workspace = (double *)workspace;
   bj->n_bands = n_bands;
   bj->half = half;
-  bj->band0 = 0;
-  bj->pair0 = 0;
-  bj->band_tail_blocks = 0;
   for (int b = 0; b < ISM_MAX_BANDS; ++b) bj->air[b] = 0.0;
-  if (workspace_bytes < ism_bands_layout(bj, ir_len, workspace_bytes) && !with_tail)   // with a tail: ism_bands_tail_prepare, against the shorter row
-    return fail(AL_E_BADARG, "al_ism_shoebox_bands: workspace smaller than al_ism_shoebox_bands_workspace_bytes (one pair)");
+  if (int rc = ism_rows_prepare("al_ism_shoebox_bands", L, workspace, workspace_bytes, mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, bj))
+    return rc;
+  if (mix >= 0) bj->base.tail.env_stride = (uint32_t)n_knots;   // from band b to band b + 1
   return AL_OK;
 }
 
-// al_ism_shoebox_bands_tail's further arguments into a job ism_bands_prepare has filled (with the workspace check left to here:
-// a row with a tail needs y_end = min(ir_len, M + F) band samples only)
-inline int ism_bands_tail_prepare(int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env,
-                                  int32_t n_knots, int64_t workspace_bytes, IsmBandJob *bj) {
-  if (bj->half > ISM_BAND_TAIL_MAX_HALF) return fail(AL_E_BADARG, "al_ism_shoebox_bands_tail: half must be in 1 .. 1024 with a tail");
-  if (int rc = ism_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, &bj->base)) return rc;
-  if (bj->base.pitch > 0x7fffffff - 2 * (ISM_BT_SPAN + ISM_BAND_TAIL_MAX_HALF))   // k_ism_band_tail counts span + half past the row in int32
-    return fail(AL_E_BADARG, "al_ism_shoebox_bands_tail: pitch must be at most 2^31 - 4097");
-  IsmTail &tail = bj->base.tail;
-  tail.env_stride = (uint32_t)n_knots;   // from band b to band b + 1
-  if (workspace_bytes < ism_bands_layout(bj, tail.y_end, workspace_bytes))
-    return fail(AL_E_BADARG, "al_ism_shoebox_bands: workspace smaller than al_ism_shoebox_bands_workspace_bytes (one pair)");
-  bj->band_tail_blocks = tail.split < bj->base.pitch ? (bj->base.pitch - tail.split + ISM_BT_SPAN - 1) / ISM_BT_SPAN : 0;
-  if ((int64_t)bj->band_tail_blocks * bj->base.n_sources * bj->base.n_capsules > 0x7fffffff)
-    return fail(AL_E_BADARG, "al_ism_shoebox_bands_tail: more than 2^31 - 1 workgroups (spans of 1024 samples x pairs): split the call");
+// al_ism_shoebox_bands_src's further arguments into a job ism_bands_prepare has filled: the source patterns, the air coefficient of
+// every band, a knot table per (source, band)
+inline int ism_bands_source_prepare(const double *source_patterns, const double *air, bool with_tail, IsmBandJob *bj) {
+  if (!air) return fail(AL_E_BADARG, "al_ism_shoebox_bands_src: null air table");
+  for (int b = 0; b < bj->n_bands; ++b) {
+    if (int rc = ism_source_prepare(source_patterns, air[b], &bj->base)) return rc;
+    bj->air[b] = air[b];
+  }
+  bj->base.air = 0.0;   // the bands carry their own
+  if (with_tail) bj->base.tail.env_src_stride = bj->base.tail.env_stride * (uint32_t)bj->n_bands;   // (N, B, n_knots): at most 8 x 2^23 knots
   return AL_OK;
 }
 
-template <int NB, bool SRC>
-inline void launch_ism_bands_group(const IsmBandJob &bj, int64_t pairs, hipStream_t stream) {
-  hipLaunchKernelGGL((k_ism_bands<NB, SRC>), dim3((unsigned)(pairs * bj.n_ws_tiles)), dim3(ISM_THREADS), 0, stream, bj);
-}
-
-template <bool TAIL, bool SRC = false>
-inline void launch_ism_bands_passes(const IsmBandJob &job, hipStream_t stream) {
-  const int64_t pairs = (int64_t)job.base.n_sources * job.base.n_capsules;
-  IsmBandJob bj = job;
-  for (int64_t pair0 = 0; pair0 < pairs; pair0 += job.pairs_per_pass) {
-    const int64_t in_pass = pairs - pair0 < job.pairs_per_pass ? pairs - pair0 : job.pairs_per_pass;
+// THE PASS LOOP of both families: the pairs in passes of what the workspace holds, per pass the gathers over groups of at most
+// ISM_BAND_GROUP rows and then the combine, in order on the one stream.  bj is the band job INSIDE the job the two callables hand their
+// kernels: the loop sets its pair0 and band0.  gather(group size as an integral constant, grid), combine(grid)
+template <class Gather, class Combine>
+inline void ism_rows_passes(IsmBandJob &bj, Gather gather, Combine combine) {
+  const int64_t pairs = (int64_t)bj.base.n_sources * bj.base.n_capsules;
+  for (int64_t pair0 = 0; pair0 < pairs; pair0 += bj.pairs_per_pass) {
+    const int64_t in_pass = pairs - pair0 < bj.pairs_per_pass ? pairs - pair0 : bj.pairs_per_pass;
     bj.pair0 = pair0;
-    for (int band0 = 0; band0 < job.n_bands; band0 += ISM_BAND_GROUP) {
+    const dim3 grid((unsigned)(in_pass * bj.n_ws_tiles));
+    for (int band0 = 0; band0 < bj.n_bands; band0 += ISM_BAND_GROUP) {
       bj.band0 = band0;
-      switch (job.n_bands - band0 < ISM_BAND_GROUP ? job.n_bands - band0 : ISM_BAND_GROUP) {
-        case 1: launch_ism_bands_group<1, SRC>(bj, in_pass, stream); break;
-        case 2: launch_ism_bands_group<2, SRC>(bj, in_pass, stream); break;
-        case 3: launch_ism_bands_group<3, SRC>(bj, in_pass, stream); break;
-        default: launch_ism_bands_group<4, SRC>(bj, in_pass, stream); break;
+      switch (bj.n_bands - band0 < ISM_BAND_GROUP ? bj.n_bands - band0 : ISM_BAND_GROUP) {
+        case 1: gather(std::integral_constant<int, 1>{}, grid); break;
+        case 2: gather(std::integral_constant<int, 2>{}, grid); break;
+        case 3: gather(std::integral_constant<int, 3>{}, grid); break;
+        default: gather(std::integral_constant<int, 4>{}, grid); break;
       }
     }
     bj.band0 = 0;
-    hipLaunchKernelGGL(k_ism_band_combine<TAIL>, dim3((unsigned)(in_pass * bj.n_out_tiles)), dim3(ISM_THREADS), 0, stream, bj);
+    combine(dim3((unsigned)(in_pass * bj.n_out_tiles)));
   }
 }
-
-inline void launch_ism_shoebox_bands(const IsmBandJob &job, hipStream_t stream) { launch_ism_bands_passes<false>(job, stream); }
 
 // the samples past the split of every row of a job with a tail
 inline void launch_ism_band_tail(const IsmBandJob &job, hipStream_t stream) {
@@ -463,31 +514,23 @@ inline void launch_ism_band_tail(const IsmBandJob &job, hipStream_t stream) {
   }
 }
 
-inline void launch_ism_shoebox_bands_tail(const IsmBandJob &job, hipStream_t stream) {
-  launch_ism_bands_passes<true>(job, stream);
-  launch_ism_band_tail(job, stream);
+// THE LAUNCH OF THE BAND ENTRIES: the passes, then with a tail the samples past the split.  src: k_ism_bands<NB, true>
+// (al_ism_shoebox_bands_src takes it whatever its source table and air are)
+template <bool TAIL, bool SRC>
+inline void launch_ism_bands_passes(const IsmBandJob &job, hipStream_t stream) {
+  IsmBandJob bj = job;
+  const dim3 block(ISM_THREADS);
+  ism_rows_passes(
+      bj, [&](auto nb, dim3 grid) { hipLaunchKernelGGL((k_ism_bands<decltype(nb)::value, SRC>), grid, block, 0, stream, bj); },
+      [&](dim3 grid) { hipLaunchKernelGGL(k_ism_band_combine<TAIL>, grid, block, 0, stream, bj); });
+  if (TAIL) launch_ism_band_tail(job, stream);
 }
 
-// al_ism_shoebox_bands_src's further arguments into a job ism_bands_prepare (and, with mix >= 0, ism_bands_tail_prepare) has filled:
-// the source patterns, the air coefficient of every band, a knot table per (source, band)
-inline int ism_bands_source_prepare(const double *source_patterns, const double *air, bool with_tail, IsmBandJob *bj) {
-  if (!air) return fail(AL_E_BADARG, "al_ism_shoebox_bands_src: null air table");
-  for (int b = 0; b < bj->n_bands; ++b) {
-    if (int rc = ism_source_prepare(source_patterns, air[b], &bj->base)) return rc;
-    bj->air[b] = air[b];
-  }
-  bj->base.air = 0.0;   // the bands carry their own
-  if (with_tail) bj->base.tail.env_src_stride = bj->base.tail.env_stride * (uint32_t)bj->n_bands;   // (N, B, n_knots): at most 8 x 2^23 knots
-  return AL_OK;
-}
-
-inline void launch_ism_shoebox_bands_src(const IsmBandJob &job, bool with_tail, hipStream_t stream) {
-  if (with_tail) {
-    launch_ism_bands_passes<true, true>(job, stream);
-    launch_ism_band_tail(job, stream);
-  } else {
-    launch_ism_bands_passes<false, true>(job, stream);
-  }
+inline void launch_ism_shoebox_bands(const IsmBandJob &job, bool with_tail, bool src, hipStream_t stream) {
+  if (with_tail)
+    src ? launch_ism_bands_passes<true, true>(job, stream) : launch_ism_bands_passes<true, false>(job, stream);
+  else
+    src ? launch_ism_bands_passes<false, true>(job, stream) : launch_ism_bands_passes<false, false>(job, stream);
 }
 
 }  // namespace al

@@ -11,8 +11,8 @@
 //   k_ism_sphere<NB, SRC>  ism_gather (al_ism.h) over the shifted axis with the variant IsmSphere<NB>: a list entry carries the
 //     gains P_l(mu) of the NB <= 4 orders [order0, order0 + NB) (the recurrence runs from 0 to the group's top order for every
 //     image; the walls' one bit says which images are dead), one workgroup of ONE WAVE per (pair, tile of W), float64 order rows
-//     written into the workspace [pair in pass][n_orders][W] exactly as k_ism_bands writes band rows; ceil(n_orders / 4) launches
-//     per pass.  Every order keeps its own accumulator and the canonical order of the images, so the grouping cannot change bits.
+//     written into the workspace [pair in pass][n_orders][W] by ism_workspace_rows, the body of k_ism_bands; ceil(n_orders / 4)
+//     launches per pass (ism_rows_passes).  Every order keeps its own accumulator and the canonical order of the images, so the grouping cannot change bits.
 //     The receiver position of the gather is the centre for every capsule: the kernel puts it into LDS and hands the gather a job
 //     whose one "capsule" is that LDS triple.  SRC: the source's pattern and the air in the common amplitude, as IsmOmniSrc.
 //   k_ism_band_combine<false> (al_ism_bands.h, as it is)  the rows without a tail: it indexes by n_bands alone, here n_orders.
@@ -82,41 +82,20 @@ struct IsmSphereSrc : IsmSphere<NB> {
 // spills 16 and 40 bytes per lane to scratch when asked, so it is left at the default.)
 template <int NB, bool SRC>
 __global__ __launch_bounds__(ISM_THREADS) ISM_WAVES_PER_SIMD(NB == 3 ? 4 : 1) void k_ism_sphere(IsmSphereJob sj) {
-  __shared__ IsmDirEntry<NB> list[ISM_DIR_LIST];
-  __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];
   __shared__ double centre[3];
-  __shared__ int wave_total[2];
   const IsmBandJob &bj = sj.bj;
-  const int tid = threadIdx.x;
-  const int tile = (int)(blockIdx.x % (unsigned)bj.n_ws_tiles);
-  const int64_t local = blockIdx.x / (unsigned)bj.n_ws_tiles, pair = bj.pair0 + local;   // c * N + n
-  const int n = (int)(pair % bj.base.n_sources), cap = (int)(pair / bj.base.n_sources);
-  // the tile in workspace words w and in samples s = w - half
-  const int w_lo = tile * ISM_TILE, w = w_lo + tid;
-  const int s_lo = w_lo - bj.half;
-  const int s_end = bj.y_end + bj.half;                // the order sums are formed for s < s_end
-  const int t_hi = min(s_lo + ISM_TILE, s_end) - 1;
-  double *rows = bj.workspace + (local * bj.n_bands + bj.band0) * (int64_t)bj.W;   // order band0 of the pair; order k is k * W on
-  if (t_hi < s_lo || t_hi < -ISM_HALF) {   // a tile past s_end, or so far below sample 0 that no tap reaches it (tau > 0)
-    for (int k = 0; k < NB; ++k)
-      for (int s = 0; s < ISM_PER_LANE; ++s) rows[(int64_t)k * bj.W + w + s * ISM_THREADS] = 0.0;
-    return;
-  }
-  if (tid < 3) centre[tid] = sj.centre[tid];
+  int n, cap;
+  ism_pass_pair(bj, bj.n_ws_tiles, n, cap);
+  if (threadIdx.x < 3) centre[threadIdx.x] = sj.centre[threadIdx.x];
   __syncthreads();   // one wave: orders the LDS traffic
   IsmJob job = bj.base;   // uniform over the wave: scalar values, no vector register and no scratch holds the copy (hipcc parks
                           // 83 to 101 of the kernel's scalars in VGPR lanes, as it parks 60 to 76 in k_ism_bands<4>)
   job.capsules = centre;  // the gather's receiver 0 is the centre of the sphere, whatever the capsule
   const double *dir = sj.directions + 3 * (int64_t)cap;
-  double acc[ISM_PER_LANE][NB] = {};
   if constexpr (SRC)
-    ism_gather(job, IsmSphereSrc<NB>{{{job}, dir, bj.band0}, ism_source(job, n)}, n, 0, s_lo, t_hi, s_end, list, win_c, win_s, wave_total, acc);
+    ism_workspace_rows(bj, job, IsmSphereSrc<NB>{{{job}, dir, bj.band0}, ism_source(job, n)}, n, 0);
   else
-    ism_gather(job, IsmSphere<NB>{{job}, dir, bj.band0}, n, 0, s_lo, t_hi, s_end, list, win_c, win_s, wave_total, acc);
-#pragma unroll
-  for (int s = 0; s < ISM_PER_LANE; ++s)   // w + s * ISM_THREADS < W: the tile lies inside the row
-#pragma unroll
-    for (int k = 0; k < NB; ++k) rows[(int64_t)k * bj.W + w + s * ISM_THREADS] = acc[s][k];
+    ism_workspace_rows(bj, job, IsmSphere<NB>{{job}, dir, bj.band0}, n, 0);
 }
 
 // out[t] = float32(w_e sum_l sum_j b_l[j] y_l[t - j] + w_l n(t)) for the tiles below the split of a row with a tail; grid, lanes and
@@ -198,20 +177,8 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_sphere_combine(IsmSphereJob
   }
 }
 
-// al_ism_shoebox_sphere_workspace_bytes: bytes per pair, or AL_E_BADARG.  mix < 0: no tail (y_end = ir_len)
-inline int64_t ism_sphere_workspace_bytes(int32_t n_orders, int32_t half, int32_t ir_len, int64_t mix, int64_t fade) {
-  if (n_orders < 1 || n_orders > ISM_SPHERE_MAX_ORDERS) return fail(AL_E_BADARG, "al_ism_shoebox_sphere: n_orders must be in 1 .. 64");
-  if (half < 1 || half > ISM_SPHERE_MAX_HALF) return fail(AL_E_BADARG, "al_ism_shoebox_sphere: half must be in 1 .. 1024");
-  if (ir_len < 1) return fail(AL_E_BADARG, "al_ism_shoebox_sphere: ir_len must be >= 1");
-  if (mix >= 0 && fade < 1) return fail(AL_E_BADARG, "al_ism_shoebox_sphere: fade must be >= 1");
-  IsmBandJob bj;
-  bj.n_bands = n_orders;
-  bj.half = half;
-  bj.base.n_tiles = 1;
-  return ism_bands_layout(&bj, mix < 0 ? ir_len : ism_tail_y_end(mix, fade, ir_len), 0);
-}
-
-// al_ism_shoebox_sphere's arguments as the kernels' job: 0 with *sj filled, or the error of the first bad argument
+// al_ism_shoebox_sphere's arguments as the kernels' job: 0 with *sj filled, or the error of the first bad argument.  mix < 0: no
+// tail, and the tail's arguments are not looked at
 inline int ism_sphere_prepare(const double *sources, int32_t n_sources, const double *source_patterns, const double *centre,
                               const double *directions, int32_t n_capsules, const double *L, const double *beta, double air,
                               const double *filters, int32_t n_orders, int32_t half, const double *diffuse, double c, double fs,
@@ -219,90 +186,54 @@ inline int ism_sphere_prepare(const double *sources, int32_t n_sources, const do
                               int64_t capsule_id0, const double *ln_env, int32_t n_knots, void *workspace, int64_t workspace_bytes, float *out,
                               IsmSphereJob *sj) {
   IsmBandJob *bj = &sj->bj;
-  const bool with_tail = mix >= 0;
-  if (n_orders < 1 || n_orders > ISM_SPHERE_MAX_ORDERS) return fail(AL_E_BADARG, "al_ism_shoebox_sphere: n_orders must be in 1 .. 64");
-  if (half < 1 || half > ISM_SPHERE_MAX_HALF) return fail(AL_E_BADARG, "al_ism_shoebox_sphere: half must be in 1 .. 1024");
+  if (int rc = ism_rows_range("al_ism_shoebox_sphere", "n_orders", n_orders, ISM_SPHERE_MAX_ORDERS, half, ISM_SPHERE_MAX_HALF)) return rc;
   if (!centre) return fail(AL_E_BADARG, "al_ism_shoebox: null pointer");
   if (!filters) return fail(AL_E_BADARG, "al_ism_shoebox_sphere: null filter table");
-  if (with_tail && !diffuse) return fail(AL_E_BADARG, "al_ism_shoebox_sphere: null diffuse-field filter");
+  if (mix >= 0 && !diffuse) return fail(AL_E_BADARG, "al_ism_shoebox_sphere: null diffuse-field filter");
   // ism_prepare refuses what al_ism_shoebox refuses; the "capsules" it counts are the directions' rows
   if (int rc = ism_prepare(sources, n_sources, directions, n_capsules, L, beta, c, fs, max_order, ir_len, pitch, out, &bj->base)) return rc;
   for (int i = 0; i < 3; ++i) {
     if (!isfinite(centre[i])) return fail(AL_E_BADARG, "al_ism_shoebox_sphere: the centre must be finite");
     sj->centre[i] = centre[i];
-    if (!(c * ((double)ir_len + (double)half + 42.0) / fs / L[i] + 2.0 <= ISM_MAX_HALF_WIDTH))   // the order sums reach `half` past the row
-      return fail(AL_E_BADARG, "al_ism_shoebox_sphere: c (ir_len + half + 42) / fs spans more than 2^20 mirror cells of the room");
   }
   if (int rc = ism_source_prepare(source_patterns, air, &bj->base)) return rc;
-  if (!workspace || ((uintptr_t)workspace & 15) != 0)
-    return fail(AL_E_BADARG, "al_ism_shoebox_sphere: workspace must be 16-byte aligned and not null");
   for (int b = 0; b < ISM_MAX_BANDS; ++b) {   // the band tables are not read: the walls are the job's one column
     bj->air[b] = 0.0;
     for (int i = 0; i < 6; ++i) bj->ln_beta[b][i] = 0.0, bj->beta_zero[b][i] = 0;
   }
   bj->filters = filters;
-  bj->workspace = (double *)workspace;
   bj->n_bands = n_orders;
   bj->half = half;
-  bj->band0 = 0;
-  bj->pair0 = 0;
-  bj->band_tail_blocks = 0;
   sj->directions = directions;
   sj->diffuse = diffuse;
-  int32_t y_end = ir_len;
-  if (with_tail) {
-    if (int rc = ism_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, &bj->base)) return rc;
-    if (bj->base.pitch > 0x7fffffff - 2 * (ISM_BT_SPAN + ISM_BAND_TAIL_MAX_HALF))   // k_ism_band_tail counts span + half past the row in int32
-      return fail(AL_E_BADARG, "al_ism_shoebox_sphere: pitch must be at most 2^31 - 4097 with a tail");
+  if (int rc = ism_rows_prepare("al_ism_shoebox_sphere", L, workspace, workspace_bytes, mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, bj))
+    return rc;
+  if (mix >= 0) {
     if ((int64_t)n_knots * n_sources > 0xffffffffll) return fail(AL_E_BADARG, "al_ism_shoebox_sphere: n_knots x n_sources must be below 2^32");
-    IsmTail &tail = bj->base.tail;
-    tail.env_stride = 0;                       // one law for every capsule
-    tail.env_src_stride = (uint32_t)n_knots;   // (N, n_knots): a table per source
-    y_end = tail.y_end;
-    bj->band_tail_blocks = tail.split < bj->base.pitch ? (bj->base.pitch - tail.split + ISM_BT_SPAN - 1) / ISM_BT_SPAN : 0;
-    if ((int64_t)bj->band_tail_blocks * n_sources * n_capsules > 0x7fffffff)
-      return fail(AL_E_BADARG, "al_ism_shoebox_sphere: more than 2^31 - 1 workgroups (spans of 1024 samples x pairs): split the call");
+    bj->base.tail.env_src_stride = (uint32_t)n_knots;   // (N, n_knots): a table per source, one law for every capsule
   }
-  if (workspace_bytes < ism_bands_layout(bj, y_end, workspace_bytes))
-    return fail(AL_E_BADARG, "al_ism_shoebox_sphere: workspace smaller than al_ism_shoebox_sphere_workspace_bytes (one pair)");
   return AL_OK;
 }
 
-template <int NB>
-inline void launch_ism_sphere_group(const IsmSphereJob &sj, bool src, int64_t pairs, hipStream_t stream) {
-  const dim3 grid((unsigned)(pairs * sj.bj.n_ws_tiles)), block(ISM_THREADS);
-  if (src)
-    hipLaunchKernelGGL((k_ism_sphere<NB, true>), grid, block, 0, stream, sj);
-  else
-    hipLaunchKernelGGL((k_ism_sphere<NB, false>), grid, block, 0, stream, sj);
-}
-
-// the passes over the workspace (gathers, then the combine, in order on the one stream), then the samples past the split
+// THE LAUNCH: the passes over the workspace (ism_rows_passes), then with a tail the samples past the split
 inline void launch_ism_shoebox_sphere(const IsmSphereJob &job, bool with_tail, hipStream_t stream) {
-  const IsmJob &base = job.bj.base;
-  const int64_t pairs = (int64_t)base.n_sources * base.n_capsules;
-  const bool src = base.source_patterns != nullptr || base.air != 0.0;   // null and 0: the kernels without the source side
-  const int n_orders = job.bj.n_bands;
+  const bool src = job.bj.base.source_patterns != nullptr || job.bj.base.air != 0.0;   // null and 0: the kernels without the source side
   IsmSphereJob sj = job;
-  for (int64_t pair0 = 0; pair0 < pairs; pair0 += job.bj.pairs_per_pass) {
-    const int64_t in_pass = pairs - pair0 < job.bj.pairs_per_pass ? pairs - pair0 : job.bj.pairs_per_pass;
-    sj.bj.pair0 = pair0;
-    for (int order0 = 0; order0 < n_orders; order0 += ISM_BAND_GROUP) {
-      sj.bj.band0 = order0;
-      switch (n_orders - order0 < ISM_BAND_GROUP ? n_orders - order0 : ISM_BAND_GROUP) {
-        case 1: launch_ism_sphere_group<1>(sj, src, in_pass, stream); break;
-        case 2: launch_ism_sphere_group<2>(sj, src, in_pass, stream); break;
-        case 3: launch_ism_sphere_group<3>(sj, src, in_pass, stream); break;
-        default: launch_ism_sphere_group<4>(sj, src, in_pass, stream); break;
-      }
-    }
-    sj.bj.band0 = 0;
-    const dim3 grid((unsigned)(in_pass * sj.bj.n_out_tiles)), block(ISM_THREADS);
-    if (with_tail)
-      hipLaunchKernelGGL(k_ism_sphere_combine, grid, block, 0, stream, sj);
-    else
-      hipLaunchKernelGGL(k_ism_band_combine<false>, grid, block, 0, stream, sj.bj);
-  }
+  const dim3 block(ISM_THREADS);
+  ism_rows_passes(
+      sj.bj,
+      [&](auto nb, dim3 grid) {
+        if (src)
+          hipLaunchKernelGGL((k_ism_sphere<decltype(nb)::value, true>), grid, block, 0, stream, sj);
+        else
+          hipLaunchKernelGGL((k_ism_sphere<decltype(nb)::value, false>), grid, block, 0, stream, sj);
+      },
+      [&](dim3 grid) {
+        if (with_tail)
+          hipLaunchKernelGGL(k_ism_sphere_combine, grid, block, 0, stream, sj);
+        else
+          hipLaunchKernelGGL(k_ism_band_combine<false>, grid, block, 0, stream, sj.bj);
+      });
   if (with_tail) {   // k_ism_band_tail as it stands: one band, whose filter is psi_d, under the source's knots
     IsmBandJob tj = job.bj;
     tj.n_bands = 1;

@@ -604,13 +604,17 @@ int al_pack_ragged_irs(const void *src, int32_t src_is_f64, const int64_t *offse
   return check_launch("k_pack_ragged");
 }
 
-// ---- shoebox room IRs (image-source method): DESIGN.md "Shoebox IRs"
+// ---- shoebox room IRs (image-source method): DESIGN.md "Shoebox IRs".  The five point-receiver entries share one prepare and one
+// launch (al_ism.h); each hands over what it has (no patterns: one channel; no source side: null and 0; no tail: mix = -1; else the
+// knot tables' strides from row to row and from source to source) and states what it requires
 int al_ism_shoebox(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
                    const double *beta, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, float *out,
                    al_stream_t stream) {
-  al::IsmJob job;
-  if (int rc = al::ism_prepare(sources, n_sources, capsules, n_capsules, L, beta, c, fs, max_order, ir_len, pitch, out, &job)) return rc;
-  al::launch_ism_shoebox(job, (hipStream_t)stream);
+  al::IsmDirJob job;
+  if (int rc = al::ism_images_prepare(sources, n_sources, nullptr, capsules, n_capsules, nullptr, 1, L, beta, 0.0, c, fs, max_order, ir_len,
+                                      pitch, -1, 0, 0, 0, 0, nullptr, 0, 0, 0, out, &job))
+    return rc;
+  al::launch_ism_images(job, false, false, (hipStream_t)stream);
   return check_launch("k_ism_shoebox");
 }
 
@@ -618,10 +622,12 @@ int al_ism_shoebox_tail(const double *sources, int32_t n_sources, const double *
                         const double *beta, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix,
                         int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots,
                         float *out, al_stream_t stream) {
-  al::IsmJob job;
-  if (int rc = al::ism_prepare(sources, n_sources, capsules, n_capsules, L, beta, c, fs, max_order, ir_len, pitch, out, &job)) return rc;
-  if (int rc = al::ism_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, &job)) return rc;
-  al::launch_ism_shoebox_tail(job, (hipStream_t)stream);
+  al::IsmDirJob job;
+  if (mix < 0) return al::fail(AL_E_BADARG, "al_ism_shoebox_tail: mix must be >= 0");
+  if (int rc = al::ism_images_prepare(sources, n_sources, nullptr, capsules, n_capsules, nullptr, 1, L, beta, 0.0, c, fs, max_order, ir_len,
+                                      pitch, mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, 0, 0, out, &job))
+    return rc;
+  al::launch_ism_images(job, true, false, (hipStream_t)stream);
   return check_launch("k_ism_tail");
 }
 
@@ -630,10 +636,11 @@ int al_ism_shoebox_dir(const double *sources, int32_t n_sources, const double *r
                        int32_t n_channels, const double *L, const double *beta, double c, double fs, int32_t max_order, int32_t ir_len,
                        int32_t pitch, float *out, al_stream_t stream) {
   al::IsmDirJob job;
-  if (int rc = al::ism_dir_prepare(sources, n_sources, receivers, n_receivers, patterns, n_channels, L, beta, c, fs, max_order, ir_len,
-                                   pitch, out, &job))
+  if (!patterns) return al::fail(AL_E_BADARG, "al_ism_shoebox_dir: null pattern table");
+  if (int rc = al::ism_images_prepare(sources, n_sources, nullptr, receivers, n_receivers, patterns, n_channels, L, beta, 0.0, c, fs,
+                                      max_order, ir_len, pitch, -1, 0, 0, 0, 0, nullptr, 0, 0, 0, out, &job))
     return rc;
-  al::launch_ism_shoebox_dir(job, (hipStream_t)stream);
+  al::launch_ism_images(job, false, false, (hipStream_t)stream);
   return check_launch("k_ism_shoebox_dir");
 }
 
@@ -643,17 +650,20 @@ int al_ism_shoebox_dir_tail(const double *sources, int32_t n_sources, const doub
                             int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, float *out,
                             al_stream_t stream) {
   al::IsmDirJob job;
-  if (int rc = al::ism_dir_prepare(sources, n_sources, receivers, n_receivers, patterns, n_channels, L, beta, c, fs, max_order, ir_len,
-                                   pitch, out, &job))
+  if (mix < 0) return al::fail(AL_E_BADARG, "al_ism_shoebox_tail: mix must be >= 0");
+  if (!patterns) return al::fail(AL_E_BADARG, "al_ism_shoebox_dir: null pattern table");
+  if (int rc = al::ism_images_prepare(sources, n_sources, nullptr, receivers, n_receivers, patterns, n_channels, L, beta, 0.0, c, fs,
+                                      max_order, ir_len, pitch, mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, n_knots, 0, out,
+                                      &job))
     return rc;
-  if (int rc = al::ism_dir_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, &job)) return rc;
-  al::launch_ism_shoebox_dir_tail(job, (hipStream_t)stream);
+  al::launch_ism_images(job, true, false, (hipStream_t)stream);
   return check_launch("k_ism_tail");
 }
 
 // ---- the same with frequency-dependent walls in bands: DESIGN.md "Shoebox IRs: frequency-dependent walls"
 int64_t al_ism_shoebox_bands_workspace_bytes(int32_t n_bands, int32_t half, int32_t ir_len, int64_t mix, int64_t fade) {
-  return al::ism_bands_workspace_bytes(n_bands, half, ir_len, mix, fade);
+  return al::ism_rows_workspace_bytes("al_ism_shoebox_bands", "n_bands", n_bands, al::ISM_MAX_BANDS, half, al::ISM_BAND_MAX_HALF, ir_len, mix,
+                                      fade);
 }
 
 int al_ism_shoebox_bands(const double *sources, int32_t n_sources, const double *capsules, int32_t n_capsules, const double *L,
@@ -662,9 +672,9 @@ int al_ism_shoebox_bands(const double *sources, int32_t n_sources, const double 
                          al_stream_t stream) {
   al::IsmBandJob job;
   if (int rc = al::ism_bands_prepare(sources, n_sources, capsules, n_capsules, L, beta, n_bands, filters, half, c, fs, max_order, ir_len,
-                                     pitch, workspace, workspace_bytes, out, &job))
+                                     pitch, -1, 0, 0, 0, 0, nullptr, 0, workspace, workspace_bytes, out, &job))
     return rc;
-  al::launch_ism_shoebox_bands(job, (hipStream_t)stream);
+  al::launch_ism_shoebox_bands(job, false, false, (hipStream_t)stream);
   return check_launch("k_ism_band_combine");
 }
 
@@ -674,11 +684,11 @@ int al_ism_shoebox_bands_tail(const double *sources, int32_t n_sources, const do
                               int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, void *workspace,
                               int64_t workspace_bytes, float *out, al_stream_t stream) {
   al::IsmBandJob job;
+  if (mix < 0) return al::fail(AL_E_BADARG, "al_ism_shoebox_tail: mix must be >= 0");
   if (int rc = al::ism_bands_prepare(sources, n_sources, capsules, n_capsules, L, beta, n_bands, filters, half, c, fs, max_order, ir_len,
-                                     pitch, workspace, workspace_bytes, out, &job, true))
+                                     pitch, mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, workspace, workspace_bytes, out, &job))
     return rc;
-  if (int rc = al::ism_bands_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, workspace_bytes, &job)) return rc;
-  al::launch_ism_shoebox_bands_tail(job, (hipStream_t)stream);
+  al::launch_ism_shoebox_bands(job, true, false, (hipStream_t)stream);
   return check_launch("k_ism_band_tail");
 }
 
@@ -687,11 +697,12 @@ int al_ism_shoebox_src(const double *sources, int32_t n_sources, const double *s
                        int32_t n_receivers, const double *patterns, int32_t n_channels, const double *L, const double *beta, double air,
                        double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade, uint64_t seed,
                        int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, float *out, al_stream_t stream) {
-  al::IsmDirJob job;
-  if (int rc = al::ism_src_prepare(sources, n_sources, source_patterns, receivers, n_receivers, patterns, n_channels, L, beta, air, c, fs,
-                                   max_order, ir_len, pitch, mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, out, &job))
+  al::IsmDirJob job;   // ln_env: (rows, N, n_knots)
+  if (int rc = al::ism_images_prepare(sources, n_sources, source_patterns, receivers, n_receivers, patterns, n_channels, L, beta, air, c, fs,
+                                      max_order, ir_len, pitch, mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots,
+                                      (int64_t)n_knots * n_sources, n_knots, out, &job))
     return rc;
-  al::launch_ism_shoebox_src(job, mix >= 0, (hipStream_t)stream);
+  al::launch_ism_images(job, mix >= 0, true, (hipStream_t)stream);
   return check_launch("k_ism_shoebox_src");
 }
 
@@ -701,20 +712,18 @@ int al_ism_shoebox_bands_src(const double *sources, int32_t n_sources, const dou
                              int64_t mix, int64_t fade, uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env,
                              int32_t n_knots, void *workspace, int64_t workspace_bytes, float *out, al_stream_t stream) {
   al::IsmBandJob job;
-  const bool with_tail = mix >= 0;
   if (int rc = al::ism_bands_prepare(sources, n_sources, capsules, n_capsules, L, beta, n_bands, filters, half, c, fs, max_order, ir_len,
-                                     pitch, workspace, workspace_bytes, out, &job, with_tail))
+                                     pitch, mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, workspace, workspace_bytes, out, &job))
     return rc;
-  if (with_tail)
-    if (int rc = al::ism_bands_tail_prepare(mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots, workspace_bytes, &job)) return rc;
-  if (int rc = al::ism_bands_source_prepare(source_patterns, air, with_tail, &job)) return rc;
-  al::launch_ism_shoebox_bands_src(job, with_tail, (hipStream_t)stream);
+  if (int rc = al::ism_bands_source_prepare(source_patterns, air, mix >= 0, &job)) return rc;
+  al::launch_ism_shoebox_bands(job, mix >= 0, true, (hipStream_t)stream);
   return check_launch("k_ism_bands_src");
 }
 
 // ---- capsules on a rigid sphere (arrays, a spherical head): DESIGN.md "Shoebox IRs: rigid-sphere receivers"
 int64_t al_ism_shoebox_sphere_workspace_bytes(int32_t n_orders, int32_t half, int32_t ir_len, int64_t mix, int64_t fade) {
-  return al::ism_sphere_workspace_bytes(n_orders, half, ir_len, mix, fade);
+  return al::ism_rows_workspace_bytes("al_ism_shoebox_sphere", "n_orders", n_orders, al::ISM_SPHERE_MAX_ORDERS, half, al::ISM_SPHERE_MAX_HALF,
+                                      ir_len, mix, fade);
 }
 
 int al_ism_shoebox_sphere(const double *sources, int32_t n_sources, const double *source_patterns, const double *centre,

@@ -560,119 +560,98 @@ def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sa
     for bit."""
     room, betas, sources, capsules, ir_len, fs, c, order = check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c,
                                                                           max_order, tail, patterns, bands, source_patterns, air)
-    if bands is not None and (isinstance(workspace_cap, (bool, np.bool_)) or not isinstance(workspace_cap, (int, np.integer))
-                              or workspace_cap < 0):
-        raise ValueError("workspace_cap must be an integer >= 0 (bytes)")
+    if bands is not None:
+        _check_workspace_cap(workspace_cap)
     if patterns is not None:
         patterns = check_patterns(patterns, len(capsules))
     n, n_cap, pitch = len(sources), len(capsules), pitch_of(ir_len)
-    n_rows = n_cap * (1 if patterns is None else patterns.shape[1])
-    if tail is not None:
-        for name, v, count in (("source_id0", source_id0, n), ("capsule_id0", capsule_id0, n_rows)):
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0 or int(v) + count > 1 << 32:
-                raise ValueError(f"{name} must be an integer >= 0 with {name} + count <= 2^32")
-    mem, lib = renderer.mem, renderer.lib
-    mix, fade = (-1, 0) if tail is None else tail_samples(tail, room, fs, c)
-    if source_patterns is not None or air is not None:
-        return _shoebox_irs_source(renderer, room, betas, sources, capsules, ir_len, fs, c, order, tail, mix, fade, int(source_id0),
-                                   int(capsule_id0), patterns, bands, workspace_cap, source_patterns, air)
-    # the entry and its arguments: head, (pattern | band) middle, lengths, [tail], [workspace], out, stream
-    entry = "al_ism_shoebox"
-    middle = walls = (room.ctypes.data_as(ct.POINTER(ct.c_double)), betas.ctypes.data_as(ct.POINTER(ct.c_double)))
-    tail_block = workspace_pair = ()
-    ln_env = None       # with a tail: one knot table per row, per distinct pattern or per band column
-    if bands is not None:
-        n_bands, half = betas.shape[1], int(bands.half)
-        per_pair = lib.call("al_ism_shoebox_bands_workspace_bytes", n_bands, half, ir_len, mix, fade)
-        if per_pair <= 0:
-            raise ValueError(f"al_ism_shoebox_bands_workspace_bytes refused {n_bands} bands, half = {half}, ir_len = {ir_len}")
-        pairs_per_pass = max(1, min(n * n_cap, int(workspace_cap) // per_pair))
-        workspace = mem.empty(pairs_per_pass * per_pair // 8, dtype=np.float64)
-        table_dev = mem.upload(band_filters(bands.centres, fs, half).reshape(-1))
-        entry, middle = entry + "_bands", walls + (n_bands, mem.ptr(table_dev), half)
-        workspace_pair = (mem.ptr(workspace), pairs_per_pass * per_pair)
-        if tail is not None:
-            ln_env = np.stack([tail_envelope(room, betas[:, b], ir_len, fs, mix, c, tail.rt60) for b in range(n_bands)])
-    elif patterns is not None:
-        table_dev = mem.upload(patterns.reshape(-1))
-        entry, middle = entry + "_dir", (mem.ptr(table_dev), patterns.shape[1]) + walls
-        if tail is not None:
-            tables = {}
-            for pattern in patterns.reshape(-1, 4):
-                if pattern.tobytes() not in tables:
-                    tables[pattern.tobytes()] = tail_envelope(room, betas, ir_len, fs, mix, c, tail.rt60, pattern)
-            ln_env = np.stack([tables[pattern.tobytes()] for pattern in patterns.reshape(-1, 4)])
-    elif tail is not None:
-        ln_env = tail_envelope(room, betas, ir_len, fs, mix, c, tail.rt60)[None]
-    if tail is not None:
-        env_dev = mem.upload(ln_env.reshape(-1))
-        entry, tail_block = entry + "_tail", (mix, fade, int(tail.seed), int(source_id0), int(capsule_id0), mem.ptr(env_dev), ln_env.shape[1])
-    src_dev, cap_dev = mem.upload(sources.reshape(-1)), mem.upload(capsules.reshape(-1))
-    out = mem.empty(n_rows * n * pitch)
-    lib.call(entry, mem.ptr(src_dev), n, mem.ptr(cap_dev), n_cap, *middle, c, fs, order, ir_len, pitch, *tail_block, *workspace_pair,
-             mem.ptr(out), mem.stream())
-    return out, (n * pitch, pitch), ir_len
-
-
-def _shoebox_irs_source(renderer, room, betas, sources, capsules, ir_len, fs, c, order, tail, mix, fade, source_id0, capsule_id0,
-                        patterns, bands, workspace_cap, source_patterns, air):
-    """``shoebox_irs_device`` with source patterns or air (arguments checked): the one call of ``al_ism_shoebox_src`` or
-    ``al_ism_shoebox_bands_src``."""
-    mem, lib = renderer.mem, renderer.lib
-    n, n_cap, pitch = len(sources), len(capsules), pitch_of(ir_len)
     K = 1 if patterns is None else patterns.shape[1]
     n_rows = n_cap * K
+    if tail is not None:
+        _check_ids(source_id0, capsule_id0, n, n_rows)
+    mem, lib = renderer.mem, renderer.lib
+    mix, fade = (-1, 0) if tail is None else tail_samples(tail, room, fs, c)
+    # the entries with the source side take its arguments whether or not there is a tail; the others have a name per combination
+    src = source_patterns is not None or air is not None
     spat = None if source_patterns is None else check_source_patterns(source_patterns, n)
     air = check_air(0.0 if air is None else air, None if bands is None else betas.shape[1])
-    keep = [mem.upload(sources.reshape(-1)), mem.upload(capsules.reshape(-1))]      # device tables, alive until the call is enqueued
-    spat_ptr = 0
-    if spat is not None:
-        keep.append(mem.upload(spat.reshape(-1)))
-        spat_ptr = mem.ptr(keep[-1])
-    source_keys = [b""] * n if spat is None else [row.tobytes() for row in spat]
-    source_of = (lambda key: None) if spat is None else (lambda key: np.frombuffer(key, dtype=np.float64))
+    keep = []      # device tables, alive until the call is enqueued
+
+    def ptr_of(table):
+        if table is None:
+            return 0
+        keep.append(mem.upload(table.reshape(-1)))
+        return mem.ptr(keep[-1])
+
+    head = (ptr_of(sources), n) + ((ptr_of(spat),) if src else ()) + (ptr_of(capsules), n_cap)
     walls = (room.ctypes.data_as(ct.POINTER(ct.c_double)), betas.ctypes.data_as(ct.POINTER(ct.c_double)))
-    env_ptr, n_knots, seed = 0, 0, 0
-    tables = {}      # one quadrature per distinct (receiver pattern, source pattern) or (source pattern, band)
-    out = mem.empty(n_rows * n * pitch)
+    sources_of = [None] * n if spat is None else list(spat)
+    workspace_pair = ()
     if bands is not None:
         n_bands, half = betas.shape[1], int(bands.half)
-        per_pair = lib.call("al_ism_shoebox_bands_workspace_bytes", n_bands, half, ir_len, mix, fade)
-        if per_pair <= 0:
-            raise ValueError(f"al_ism_shoebox_bands_workspace_bytes refused {n_bands} bands, half = {half}, ir_len = {ir_len}")
-        pairs_per_pass = max(1, min(n * n_cap, int(workspace_cap) // per_pair))
-        workspace = mem.empty(pairs_per_pass * per_pair // 8, dtype=np.float64)
-        keep.append(mem.upload(band_filters(bands.centres, fs, half).reshape(-1)))
-        filters_ptr = mem.ptr(keep[-1])
-        if tail is not None:
-            for key in source_keys:
-                for b in range(n_bands):
-                    if (key, b) not in tables:
-                        tables[key, b] = tail_envelope(room, betas[:, b], ir_len, fs, mix, c, tail.rt60, None, source_of(key), float(air[b]))
-            ln_env = np.stack([np.stack([tables[key, b] for b in range(n_bands)]) for key in source_keys])      # (N, B, n_knots)
-            keep.append(mem.upload(ln_env.reshape(-1)))
-            env_ptr, n_knots, seed = mem.ptr(keep[-1]), ln_env.shape[2], int(tail.seed)
-        lib.call("al_ism_shoebox_bands_src", mem.ptr(keep[0]), n, spat_ptr, mem.ptr(keep[1]), n_cap, *walls, n_bands, filters_ptr, half,
-                 air.ctypes.data_as(ct.POINTER(ct.c_double)), c, fs, order, ir_len, pitch, mix, fade, seed, source_id0, capsule_id0, env_ptr,
-                 n_knots, mem.ptr(workspace), pairs_per_pass * per_pair, mem.ptr(out), mem.stream())
-        return out, (n * pitch, pitch), ir_len
-    pat_ptr = 0
-    if patterns is not None:
-        keep.append(mem.upload(patterns.reshape(-1)))
-        pat_ptr = mem.ptr(keep[-1])
+        entry = "al_ism_shoebox_bands"
+        workspace, workspace_bytes = _workspace(renderer, entry, n_bands, half, ir_len, mix, fade, n * n_cap, workspace_cap)
+        workspace_pair = (mem.ptr(workspace), workspace_bytes)
+        middle = walls + (n_bands, ptr_of(band_filters(bands.centres, fs, half)), half)
+        middle += (air.ctypes.data_as(ct.POINTER(ct.c_double)),) if src else ()
+        # a knot table per band, (1, B, n_knots), or per (source, band), (N, B, n_knots)
+        keys = [[(b, None, source) for b in range(n_bands)] for source in (sources_of if src else [None])]
+    else:
+        entry = "al_ism_shoebox" + ("_dir" if patterns is not None and not src else "")
+        middle = ((ptr_of(patterns), K) if patterns is not None or src else ()) + walls + ((float(air[0]),) if src else ())
+        # one knot table, one per row, (rows, 1, n_knots), or one per (row, source), (rows, N, n_knots)
+        rows = [None] * (n_rows if src else 1) if patterns is None else list(patterns.reshape(-1, 4))
+        keys = [[(None, row, source) for source in (sources_of if src else [None])] for row in rows]
+    tail_block = (mix, fade, 0, int(source_id0), int(capsule_id0), 0, 0) if src else ()
     if tail is not None:
-        rows = [None] * n_rows if patterns is None else list(patterns.reshape(-1, 4))
-        for row in rows:
-            for key in source_keys:
-                pair = (b"" if row is None else row.tobytes(), key)
-                if pair not in tables:
-                    tables[pair] = tail_envelope(room, betas, ir_len, fs, mix, c, tail.rt60, row, source_of(key), float(air[0]))
-        ln_env = np.stack([np.stack([tables[b"" if row is None else row.tobytes(), key] for key in source_keys]) for row in rows])
-        keep.append(mem.upload(ln_env.reshape(-1)))                                                         # (rows, N, n_knots)
-        env_ptr, n_knots, seed = mem.ptr(keep[-1]), ln_env.shape[2], int(tail.seed)
-    lib.call("al_ism_shoebox_src", mem.ptr(keep[0]), n, spat_ptr, mem.ptr(keep[1]), n_cap, pat_ptr, K, *walls, float(air[0]), c, fs, order,
-             ir_len, pitch, mix, fade, seed, source_id0, capsule_id0, env_ptr, n_knots, mem.ptr(out), mem.stream())
+        ln_env = _envelope_tables(room, betas, ir_len, fs, mix, c, tail.rt60, air, keys)
+        tail_block = (mix, fade, int(tail.seed), int(source_id0), int(capsule_id0), ptr_of(ln_env), ln_env.shape[-1])
+    out = mem.empty(n_rows * n * pitch)
+    lib.call(entry + ("_src" if src else "_tail" if tail is not None else ""), *head, *middle, c, fs, order, ir_len, pitch, *tail_block,
+             *workspace_pair, mem.ptr(out), mem.stream())
     return out, (n * pitch, pitch), ir_len
+
+
+def _check_workspace_cap(workspace_cap) -> None:
+    if isinstance(workspace_cap, (bool, np.bool_)) or not isinstance(workspace_cap, (int, np.integer)) or workspace_cap < 0:
+        raise ValueError("workspace_cap must be an integer >= 0 (bytes)")
+
+
+def _check_ids(source_id0, capsule_id0, n_sources: int, n_rows: int) -> None:
+    """The first noise ids of a call with a tail: its sources and rows count on from them within 32 bits."""
+    for name, v, count in (("source_id0", source_id0, n_sources), ("capsule_id0", capsule_id0, n_rows)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0 or int(v) + count > 1 << 32:
+            raise ValueError(f"{name} must be an integer >= 0 with {name} + count <= 2^32")
+
+
+def _workspace(renderer, entry: str, n_rows: int, half: int, ir_len: int, mix: int, fade: int, pairs: int, workspace_cap: int):
+    """``(buffer, bytes)`` of a float64 workspace for the row sums of ``entry`` (the band or the sphere call), allocated for the call:
+    what all ``pairs`` need, at most ``workspace_cap`` bytes and at least one pair's."""
+    what = "bands" if entry.endswith("bands") else "orders"
+    per_pair = renderer.lib.call(entry + "_workspace_bytes", n_rows, half, ir_len, mix, fade)
+    if per_pair <= 0:
+        raise ValueError(f"{entry}_workspace_bytes refused {n_rows} {what}, half = {half}, ir_len = {ir_len}")
+    pairs_per_pass = max(1, min(pairs, int(workspace_cap) // per_pair))
+    return renderer.mem.empty(pairs_per_pass * per_pair // 8, dtype=np.float64), pairs_per_pass * per_pair
+
+
+def _envelope_tables(room, betas, ir_len, fs, mix, c, rt60, air, keys) -> np.ndarray:
+    """The knot tables of a call with a tail, stacked as ``keys`` is nested.  A key is ``(band or None, receiver pattern or None,
+    source pattern or None)``; band ``b`` decays under column ``b`` of ``betas`` and ``air[b]``.  One quadrature (``tail_envelope``)
+    per distinct key."""
+    tables = {}
+
+    def table(key):
+        if isinstance(key, list):
+            return np.stack([table(k) for k in key])
+        band, pattern, source = key
+        name = (band, None if pattern is None else pattern.tobytes(), None if source is None else source.tobytes())
+        if name not in tables:
+            tables[name] = tail_envelope(room, betas if band is None else betas[:, band], ir_len, fs, mix, c, rt60, pattern, source,
+                                         float(air[0 if band is None else band]))
+        return tables[name]
+
+    return table(keys)
 
 
 # ----------------------------------------------------------------------------- capsules on a rigid sphere
@@ -884,24 +863,17 @@ def shoebox_sphere_irs_device(renderer, room, betas, sources, centre, directions
                                                                     ir_len, sample_rate, c, max_order, tail, None, None, source_patterns, air)
     centre, radius = check_sphere(room, centre, radius, sources)
     directions = check_directions(directions)
-    if isinstance(workspace_cap, (bool, np.bool_)) or not isinstance(workspace_cap, (int, np.integer)) or workspace_cap < 0:
-        raise ValueError("workspace_cap must be an integer >= 0 (bytes)")
+    _check_workspace_cap(workspace_cap)
     table = sphere_filters(radius, fs, c, n_orders, half)
     n_orders, half = table.shape[0], (table.shape[1] - 1) // 2
     n, n_cap, pitch = len(sources), len(directions), pitch_of(ir_len)
     if tail is not None:
-        for name, v, count in (("source_id0", source_id0, n), ("capsule_id0", capsule_id0, n_cap)):
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0 or int(v) + count > 1 << 32:
-                raise ValueError(f"{name} must be an integer >= 0 with {name} + count <= 2^32")
+        _check_ids(source_id0, capsule_id0, n, n_cap)
     mem, lib = renderer.mem, renderer.lib
     mix, fade = (-1, 0) if tail is None else tail_samples(tail, room, fs, c)
     spat = None if source_patterns is None else check_source_patterns(source_patterns, n)
-    air = float(check_air(0.0 if air is None else air)[0])
-    per_pair = lib.call("al_ism_shoebox_sphere_workspace_bytes", n_orders, half, ir_len, mix, fade)
-    if per_pair <= 0:
-        raise ValueError(f"al_ism_shoebox_sphere_workspace_bytes refused {n_orders} orders, half = {half}, ir_len = {ir_len}")
-    pairs_per_pass = max(1, min(n * n_cap, int(workspace_cap) // per_pair))
-    workspace = mem.empty(pairs_per_pass * per_pair // 8, dtype=np.float64)
+    air = check_air(0.0 if air is None else air)
+    workspace, workspace_bytes = _workspace(renderer, "al_ism_shoebox_sphere", n_orders, half, ir_len, mix, fade, n * n_cap, workspace_cap)
     keep = [mem.upload(sources.reshape(-1)), mem.upload(directions.reshape(-1)), mem.upload(table.reshape(-1))]
     spat_ptr = diffuse_ptr = env_ptr = 0
     n_knots = seed = 0
@@ -911,19 +883,15 @@ def shoebox_sphere_irs_device(renderer, room, betas, sources, centre, directions
     if tail is not None:
         keep.append(mem.upload(sphere_diffuse_filter(radius, fs, c, n_orders, half)))
         diffuse_ptr = mem.ptr(keep[-1])
-        tables = {}      # one quadrature per distinct source pattern: the omni law of tail_envelope
-        for key in ([b""] * n if spat is None else [row.tobytes() for row in spat]):
-            if key not in tables:
-                tables[key] = tail_envelope(room, betas, ir_len, fs, mix, c, tail.rt60, None,
-                                            None if spat is None else np.frombuffer(key, dtype=np.float64), air)
-        ln_env = np.stack([tables[b"" if spat is None else row.tobytes()] for row in (range(n) if spat is None else spat)])
+        # a knot table per source, (N, n_knots): the omni law of tail_envelope
+        ln_env = _envelope_tables(room, betas, ir_len, fs, mix, c, tail.rt60, air, [(None, None, source) for source in ([None] * n if spat is None else spat)])
         keep.append(mem.upload(ln_env.reshape(-1)))
         env_ptr, n_knots, seed = mem.ptr(keep[-1]), ln_env.shape[1], int(tail.seed)
     out = mem.empty(n_cap * n * pitch)
     lib.call("al_ism_shoebox_sphere", mem.ptr(keep[0]), n, spat_ptr, centre.ctypes.data_as(ct.POINTER(ct.c_double)), mem.ptr(keep[1]), n_cap,
-             room.ctypes.data_as(ct.POINTER(ct.c_double)), betas.ctypes.data_as(ct.POINTER(ct.c_double)), air, mem.ptr(keep[2]), n_orders, half,
-             diffuse_ptr, c, fs, order, ir_len, pitch, mix, fade, seed, int(source_id0), int(capsule_id0), env_ptr, n_knots,
-             mem.ptr(workspace), pairs_per_pass * per_pair, mem.ptr(out), mem.stream())
+             room.ctypes.data_as(ct.POINTER(ct.c_double)), betas.ctypes.data_as(ct.POINTER(ct.c_double)), float(air[0]), mem.ptr(keep[2]), n_orders,
+             half, diffuse_ptr, c, fs, order, ir_len, pitch, mix, fade, seed, int(source_id0), int(capsule_id0), env_ptr, n_knots,
+             mem.ptr(workspace), workspace_bytes, mem.ptr(out), mem.stream())
     return out, (n * pitch, pitch), ir_len
 
 
