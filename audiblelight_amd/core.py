@@ -305,6 +305,17 @@ class StaticIRState:
             raise ValueError("this state knows no sample rate: give sample_rate")
         return acoustics.state_metrics(self, rate, alias, edc, renderer)
 
+    def band_metrics(self, alias: Optional[str] = None, bands=None, edc: bool = False, sample_rate: Optional[float] = None,
+                     renderer=None) -> dict:
+        """``{alias: acoustics.IRBandMetrics}``: ``metrics()`` per octave band (acoustics.ir_band_metrics; ``bands``: a
+        ``shoebox.ShoeboxBands``, its dictionary, or None for the six octave centres).  Not part of ``to_dict()``."""
+        from . import acoustics
+
+        rate = self.metadata.get("sample_rate") if sample_rate is None else sample_rate
+        if rate is None:
+            raise ValueError("this state knows no sample rate: give sample_rate")
+        return acoustics.state_band_metrics(self, rate, alias, bands, edc, renderer)
+
 
 class ShoeboxIRState:
     """WorldState stand-in for a rectangular room whose IRs are generated on the device by the image-source method
@@ -537,6 +548,14 @@ class ShoeboxIRState:
         from . import acoustics
 
         return acoustics.state_metrics(self, self.sample_rate, alias, edc)
+
+    def band_metrics(self, alias: Optional[str] = None, bands=None, edc: bool = False) -> dict:
+        """``{alias: acoustics.IRBandMetrics}``: ``metrics()`` per octave band, split and measured where the tensors lie
+        (acoustics.ir_band_metrics).  ``bands`` None: the state's own bands where it has them (a room with ``bands=`` or
+        ``materials=`` is measured in the bands it was built in), else the six octave centres.  Not part of ``to_dict()``."""
+        from . import acoustics
+
+        return acoustics.state_band_metrics(self, self.sample_rate, alias, self.bands if bands is None else bands, edc)
 
     def to_dict(self) -> dict:   # worldstate.py:2330-2356 layout, with the room in place of the mesh
         d = dict(backend=self.name, sample_rate=self.sample_rate,

@@ -2,7 +2,8 @@
 // backward integral E(t) of every row in float64 and, from it, the direct-to-reverberant ratio, the clarities C50 / C80, D50, the
 // centre time, the three decay fits EDT / T20 / T30 with their sample counts and the decay the row has room for; optionally the
 // curve itself at every 256th sample.  The definition is the header comment of al_ir_metrics in include/audiblelight_hip.h; what
-// is here is how it is summed.
+// is here is how it is summed.  The same per octave band (al_ir_band_split, al_ir_band_metrics) is the second half of this file: a
+// band split in front of these passes.
 //
 // THE TILE.  A row is cut into tiles of IRM_TILE = 1024 samples, a tile into 4 sub-tiles of 256; a workgroup is ONE WAVE and lane i owns
 // the four samples 4 i .. 4 i + 3 of every sub-tile, so a sub-tile is one 16-byte load per lane and the wave reads 1 KiB in one piece.
@@ -529,6 +530,234 @@ inline void launch_ir_metrics(const IrmJob &job, int64_t rows, hipStream_t strea
   hipLaunchKernelGGL(k_irm_sums, dim3(pairs), dim3(IRM_THREADS), 0, stream, job);
   hipLaunchKernelGGL(k_irm_fits, dim3(pairs), dim3(IRM_THREADS), 0, stream, job);
   hipLaunchKernelGGL(k_irm_columns, dim3((unsigned)rows), dim3(64), 0, stream, job);
+}
+
+// =============================================================================================== the octave-band split in front
+// BAND ROWS of an IR tensor where it lies (al_ir_band_split, al_ir_band_metrics; DESIGN.md "IR metrics: octave bands").  With phi_b
+// the zero-phase FIR of band b (2 half + 1 float64 taps, a device table: shoebox.band_filters; the table handed in is the definition)
+// and h taken as +0 outside [0, L):
+//   g_b[t] = float32( sum_{j = -half .. half} phi_b[j] (double)h[t - j] ),   one float64 accumulator, j ascending, every step an fma
+// (written as fma(): the bits do not depend on what the compiler contracts per basic block, which the schedule-perturbed builds
+// split).  The filter's ring past either end of the row is cut: a band row holds the samples [0, L) of the infinite convolution.
+// THE KERNEL.  One workgroup of ONE WAVE per (row, tile of IRB_TILE = 1024 outputs).  The row's samples tile0 - half .. tile0 + 1023 +
+// half go into LDS ONCE, as float32, and serve all B bands; the taps of a band follow IRB_CHUNK = 256 at a time.  A lane owns
+// IRB_PER_LANE = 16 CONSECUTIVE outputs: per tap it reads the tap (a broadcast) and ONE new sample, the other fifteen slide through
+// registers as float64 (one conversion per tap), and does 16 float64 multiply-adds into 16 accumulators (the scheme of
+// k_ism_band_tail, four times as wide: a quarter of the LDS reads per multiply-add).  The lanes read the segment 16 words apart, which
+// on 32 banks would be a 16-way conflict: word i lies at i + i / 16 (irb_at), so the lanes are 17 words apart and no two of a
+// 32-lane group share a bank; the segment is shifted by 16 .. 31 words so that the 16 words a lane takes in during one turn of its
+// window never straddle a skipped word (one address per turn, 16 immediate offsets).  Four 16-byte stores per lane and band; pads [L, out_pitch) are written +0; every output word has one
+// writer.  HCAP (256, 1024, 4096: the smallest that holds `half`) sizes the segment.  One wave: the __syncthreads() order LDS traffic
+// only (no barrier instruction), and the perturbed builds sleep around each.
+// al_ir_band_metrics walks the rows in PASSES of what its workspace holds: per pass one split into the workspace (float32 band rows at
+// the pitch ir_len rounded up to 4) and the five k_irm_* passes above over them as a tensor of (rows in the pass, n_bands) rows, with the
+// pass's slice of the tables as targets; all in order on the one stream.  A row's band rows depend on its samples, the table, half and
+// ir_len alone, and the metrics on the band rows alone: not on the pass, the pitch, the strides or the other rows.
+constexpr int IRB_TILE = 1024;         // outputs of a workgroup
+constexpr int IRB_PER_LANE = 16;       // consecutive outputs of a lane
+constexpr int IRB_CHUNK = 256;         // taps staged per step
+constexpr int IRB_MAX_BANDS = 8;
+constexpr int IRB_MAX_HALF = 4096;
+static_assert(64 * IRB_PER_LANE == IRB_TILE, "k_ir_band_split: a wave covers a tile");
+static_assert(IRB_CHUNK % IRB_PER_LANE == 0, "k_ir_band_split: the window turns a whole number of times per chunk");
+
+struct IrbJob {
+  const float *irs;
+  const double *filters;               // (n_bands, 2 half + 1), device
+  float *out;                          // band rows of the first row of the launch: [row - row0][n_bands][out_pitch]
+  int64_t stride_c, pitch, out_pitch;
+  int64_t row0;                        // first row of the launch (a pass of al_ir_band_metrics)
+  int32_t n_sources, ir_len, n_bands, half;
+  int32_t n_tiles;                     // ceil(out_pitch / IRB_TILE)
+};
+
+// where word i of the staged segment lies: one word skipped after every 16
+__device__ __forceinline__ int irb_at(int i) { return i + (i >> 4); }
+
+template <int HCAP>
+__global__ __launch_bounds__(64) void k_ir_band_split(IrbJob job) {
+  __shared__ float seg[(IRB_TILE + 2 * HCAP + 32) / 16 * 17];   // sample tile0 - half + i is word i + shift, which lies at irb_at(i + shift)
+  __shared__ double tap[IRB_CHUNK];
+  const int lane = threadIdx.x;
+  const int64_t local = blockIdx.x / (unsigned)job.n_tiles, row = job.row0 + local, L = job.ir_len;
+  const int64_t tile0 = (int64_t)(blockIdx.x % (unsigned)job.n_tiles) * IRB_TILE, t0 = tile0 + IRB_PER_LANE * lane;
+  const int half = job.half, n_taps = 2 * half + 1;
+  float *g = job.out + local * job.n_bands * job.out_pitch;
+  if (tile0 >= L) {   // (uniform) a tile of pad samples only; out_pitch is a multiple of 4: a quad is inside the row or outside it
+    for (int b = 0; b < job.n_bands; ++b)
+#pragma unroll
+      for (int q = 0; q < IRB_PER_LANE; q += 4)
+        if (t0 + q < job.out_pitch) *reinterpret_cast<float4 *>(g + b * job.out_pitch + t0 + q) = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  // shift in [16, 32) puts the word that enters a lane's window behind tap 16 k on the last word of a run of 16 (2 half - 1 + shift = 15
+  // mod 16): the 16 words of one turn of the window then lie side by side, one address per turn
+  const int shift = 16 + ((16 - ((2 * half) & 15)) & 15);
+  const float *h = job.irs + (row / job.n_sources) * job.stride_c + (row % job.n_sources) * job.pitch;
+  const int64_t s_first = tile0 - half;
+  for (int i = lane; i < IRB_TILE + 2 * half; i += 64) {
+    const int64_t s = s_first + i;
+    seg[irb_at(i + shift)] = s >= 0 && s < L ? h[s] : 0.f;   // samples at and past L are never read
+  }
+  if (lane == 0) seg[irb_at(shift - 1)] = 0.f;   // what lane 0 loads behind the last tap; no output uses it
+  __syncthreads();
+  // output t0 + q under tap m = j + half reads sample t0 + q + half - m: word at + q - m
+  const int at = IRB_PER_LANE * lane + 2 * half + shift;
+  for (int b = 0; b < job.n_bands; ++b) {
+    const double *phi = job.filters + (int64_t)b * n_taps;
+    double acc[IRB_PER_LANE], d[IRB_PER_LANE];
+#pragma unroll
+    for (int q = 0; q < IRB_PER_LANE; ++q) {
+      acc[q] = 0.0;
+      d[q] = (double)seg[irb_at(at + q)];
+    }
+    for (int c0 = 0; c0 < n_taps; c0 += IRB_CHUNK) {
+      __syncthreads();   // the reads of the chunk before are over
+      for (int k = lane; k < IRB_CHUNK; k += 64) tap[k] = c0 + k < n_taps ? phi[c0 + k] : 0.0;
+      __syncthreads();
+      const int m_end = min(IRB_CHUNK, n_taps - c0), enter = at - c0 - 1;   // word enter - i comes in behind tap c0 + i
+      int i = 0;
+      for (; i + IRB_PER_LANE <= m_end; i += IRB_PER_LANE) {   // whole turns: the window comes round, no register moves
+        const float *run = seg + irb_at(enter - i);             // word enter - i - k at run[-k], k < 16
+#pragma unroll
+        for (int k = 0; k < IRB_PER_LANE; ++k) {
+          const double w = tap[i + k];
+#pragma unroll
+          for (int q = 0; q < IRB_PER_LANE; ++q) acc[q] = fma(w, d[q], acc[q]);
+#pragma unroll
+          for (int q = IRB_PER_LANE - 1; q > 0; --q) d[q] = d[q - 1];
+          d[0] = (double)run[-k];
+        }
+      }
+      for (; i < m_end; ++i) {   // the taps past the last whole turn (the last chunk only)
+        const double w = tap[i];
+#pragma unroll
+        for (int q = 0; q < IRB_PER_LANE; ++q) acc[q] = fma(w, d[q], acc[q]);
+#pragma unroll
+        for (int q = IRB_PER_LANE - 1; q > 0; --q) d[q] = d[q - 1];
+        d[0] = (double)seg[irb_at(enter - i)];
+      }
+    }
+    float *gb = g + b * job.out_pitch;
+#pragma unroll
+    for (int q = 0; q < IRB_PER_LANE; q += 4) {
+      if (t0 + q >= job.out_pitch) continue;
+      float v[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = t0 + q + k < L ? (float)acc[q + k] : 0.f;
+      *reinterpret_cast<float4 *>(gb + t0 + q) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+  }
+}
+
+// what al_ir_band_split and al_ir_band_metrics check alike: the view (as al_ir_metrics), the table and the two ranges
+inline int irb_check(const char *entry, const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch,
+                     int32_t ir_len, const double *filters, int32_t n_bands, int32_t half) {
+  if (!irs) return fail_arg(entry, "irs must not be null");
+  if (n_capsules < 1 || n_sources < 1 || ir_len < 1) return fail_arg(entry, "n_capsules, n_sources and ir_len must be >= 1");
+  if (pitch < ir_len) return fail_arg(entry, "pitch < ir_len");
+  if (pitch > INT64_MAX / n_sources || stride_c < (int64_t)n_sources * pitch) return fail_arg(entry, "stride_c < n_sources * pitch");
+  if ((int64_t)n_capsules * n_sources > 0x7fffffff) return fail_arg(entry, "more than 2^31 - 1 rows");
+  if (n_bands < 1 || n_bands > IRB_MAX_BANDS) return fail_arg(entry, "n_bands must be in 1 .. 8");
+  if (half < 1 || half > IRB_MAX_HALF) return fail_arg(entry, "half must be in 1 .. 4096");
+  if (!filters) return fail_arg(entry, "filters must not be null");
+  return AL_OK;
+}
+
+inline void irb_fill(IrbJob *job, const float *irs, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len,
+                     const double *filters, int32_t n_bands, int32_t half, float *out, int64_t out_pitch) {
+  job->irs = irs; job->filters = filters; job->out = out;
+  job->stride_c = stride_c; job->pitch = pitch; job->out_pitch = out_pitch; job->row0 = 0;
+  job->n_sources = n_sources; job->ir_len = ir_len; job->n_bands = n_bands; job->half = half;
+  job->n_tiles = (int32_t)((out_pitch + IRB_TILE - 1) / IRB_TILE);
+}
+
+inline int irb_split_prepare(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len,
+                             const double *filters, int32_t n_bands, int32_t half, float *out, int64_t out_pitch, IrbJob *job) {
+  const char *entry = "al_ir_band_split";
+  if (int rc = irb_check(entry, irs, n_capsules, n_sources, stride_c, pitch, ir_len, filters, n_bands, half)) return rc;
+  if (!out) return fail_arg(entry, "out must not be null");
+  if (((uintptr_t)out & 15) != 0) return fail_arg(entry, "out must be 16-byte aligned");
+  if (out_pitch < ir_len) return fail_arg(entry, "out_pitch < ir_len");
+  if ((out_pitch & 3) != 0) return fail_arg(entry, "out_pitch must be a multiple of 4");
+  const int64_t rows = (int64_t)n_capsules * n_sources;
+  if (out_pitch > INT64_MAX - IRB_TILE || rows > 0x7fffffff / ((out_pitch + IRB_TILE - 1) / IRB_TILE))
+    return fail_arg(entry, "more than 2^31 - 1 (row, 1024-sample tile of out_pitch) pairs: split the call");
+  irb_fill(job, irs, n_sources, stride_c, pitch, ir_len, filters, n_bands, half, out, out_pitch);
+  return AL_OK;
+}
+
+// `rows` rows from job.row0 on
+inline void launch_ir_band_split(const IrbJob &job, int64_t rows, hipStream_t stream) {
+  const dim3 grid((unsigned)(rows * job.n_tiles)), block(64);
+  if (job.half <= 256)
+    hipLaunchKernelGGL(k_ir_band_split<256>, grid, block, 0, stream, job);
+  else if (job.half <= 1024)
+    hipLaunchKernelGGL(k_ir_band_split<1024>, grid, block, 0, stream, job);
+  else
+    hipLaunchKernelGGL(k_ir_band_split<4096>, grid, block, 0, stream, job);
+}
+
+// ---- the band metrics: the split and the five passes above, pass by pass over a capped workspace
+struct IrbMetricsJob {
+  IrbJob split;                        // out: the band rows at the head of the workspace
+  char *metrics_workspace;             // behind the band rows of a full pass
+  int64_t metrics_bytes, rows, rows_per_pass;
+  double fs, *out, *edc;
+};
+
+inline int64_t irb_pitch(int32_t ir_len) { return ((int64_t)ir_len + 3) / 4 * 4; }
+
+// one row's share of the workspace: its n_bands band rows and what al_ir_metrics needs for them, a multiple of 16 bytes
+inline int64_t irb_row_bytes(int32_t n_bands, int32_t ir_len) {
+  const int64_t bytes = (int64_t)n_bands * irb_pitch(ir_len) * (int64_t)sizeof(float) + irm_workspace_bytes(n_bands, ir_len);
+  return (bytes + 15) / 16 * 16;
+}
+
+inline int64_t irb_metrics_workspace_bytes(int32_t n_bands, int32_t ir_len) {
+  const char *entry = "al_ir_band_metrics_workspace_bytes";
+  if (n_bands < 1 || n_bands > IRB_MAX_BANDS) return fail_arg(entry, "n_bands must be in 1 .. 8");
+  if (ir_len < 1) return fail_arg(entry, "ir_len must be >= 1");
+  return irb_row_bytes(n_bands, ir_len);
+}
+
+inline int irb_metrics_prepare(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len,
+                               double fs, const double *filters, int32_t n_bands, int32_t half, void *workspace, int64_t workspace_bytes,
+                               double *out, double *edc, IrbMetricsJob *job) {
+  const char *entry = "al_ir_band_metrics";
+  if (int rc = irb_check(entry, irs, n_capsules, n_sources, stride_c, pitch, ir_len, filters, n_bands, half)) return rc;
+  if (!out || !workspace) return fail_arg(entry, "out and workspace must not be null");
+  if (!(fs > 0.0) || !(fs <= 1.7976931348623157e308)) return fail_arg(entry, "fs must be finite and positive");
+  if (((uintptr_t)workspace & 15) != 0) return fail_arg(entry, "workspace must be 16-byte aligned");
+  const int64_t per_row = irb_row_bytes(n_bands, ir_len);
+  if (workspace_bytes < per_row) return fail_arg(entry, "workspace_bytes < al_ir_band_metrics_workspace_bytes(...) (one row)");
+  const int64_t rows = (int64_t)n_capsules * n_sources, P = irb_pitch(ir_len);
+  int64_t per_pass = workspace_bytes / per_row;   // ... and no more than al_ir_metrics accepts: (row, band, tile) triples below 2^31
+  if (per_pass > rows) per_pass = rows;
+  if (per_pass > 0x7fffffff / (n_bands * irm_tiles(ir_len))) per_pass = 0x7fffffff / (n_bands * irm_tiles(ir_len));
+  irb_fill(&job->split, irs, n_sources, stride_c, pitch, ir_len, filters, n_bands, half, static_cast<float *>(workspace), P);
+  job->metrics_workspace = static_cast<char *>(workspace) + per_pass * n_bands * P * (int64_t)sizeof(float);   // a multiple of 16
+  job->metrics_bytes = irm_workspace_bytes(per_pass * n_bands, ir_len);
+  job->rows = rows; job->rows_per_pass = per_pass;
+  job->fs = fs; job->out = out; job->edc = edc;
+  return AL_OK;
+}
+
+inline int launch_ir_band_metrics(const IrbMetricsJob &job, hipStream_t stream) {
+  IrbJob split = job.split;
+  const int32_t B = split.n_bands, L = split.ir_len;
+  const int64_t n_knots = (L - 1) / IRM_KNOT + 2;
+  for (int64_t row0 = 0; row0 < job.rows; row0 += job.rows_per_pass) {
+    const int64_t in_pass = job.rows - row0 < job.rows_per_pass ? job.rows - row0 : job.rows_per_pass;
+    split.row0 = row0;
+    launch_ir_band_split(split, in_pass, stream);
+    IrmJob metrics;   // the band rows as a tensor of (in_pass, B) rows
+    if (int rc = irm_prepare(split.out, (int32_t)in_pass, B, B * split.out_pitch, split.out_pitch, L, job.fs, job.metrics_workspace,
+                             job.metrics_bytes, job.out + row0 * B * IRM_COLS, job.edc ? job.edc + row0 * B * n_knots : nullptr, &metrics))
+      return rc;
+    launch_ir_metrics(metrics, in_pass * B, stream);
+  }
+  return AL_OK;
 }
 
 }  // namespace al

@@ -755,6 +755,29 @@ int al_ir_metrics(const float *irs, int32_t n_capsules, int32_t n_sources, int64
   return check_launch("k_irm_columns");
 }
 
+// ---- the same per octave band, a device band split in front: DESIGN.md "IR metrics: octave bands"
+int al_ir_band_split(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len,
+                     const double *filters, int32_t n_bands, int32_t half, float *out, int64_t out_pitch, al_stream_t stream) {
+  al::IrbJob job;
+  if (int rc = al::irb_split_prepare(irs, n_capsules, n_sources, stride_c, pitch, ir_len, filters, n_bands, half, out, out_pitch, &job))
+    return rc;
+  al::launch_ir_band_split(job, (int64_t)n_capsules * n_sources, (hipStream_t)stream);
+  return check_launch("k_ir_band_split");
+}
+
+int64_t al_ir_band_metrics_workspace_bytes(int32_t n_bands, int32_t ir_len) { return al::irb_metrics_workspace_bytes(n_bands, ir_len); }
+
+int al_ir_band_metrics(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len,
+                       double fs, const double *filters, int32_t n_bands, int32_t half, void *workspace, int64_t workspace_bytes,
+                       double *out, double *edc, al_stream_t stream) {
+  al::IrbMetricsJob job;
+  if (int rc = al::irb_metrics_prepare(irs, n_capsules, n_sources, stride_c, pitch, ir_len, fs, filters, n_bands, half, workspace,
+                                       workspace_bytes, out, edc, &job))
+    return rc;
+  if (int rc = al::launch_ir_band_metrics(job, (hipStream_t)stream)) return rc;
+  return check_launch("k_irm_columns");
+}
+
 int al_resample_poly(const float *x, int32_t rows, int64_t n_in, const float *taps, int32_t half_len, int32_t up, int32_t down,
                      float *out, int64_t n_out, int64_t out_pitch, al_stream_t stream) {
   if (!x || !taps || !out || rows <= 0 || rows > 65535 || n_in <= 0 || half_len < 0 || up <= 0 || down <= 0 || n_out <= 0 ||

@@ -798,6 +798,37 @@ int64_t al_ir_metrics_workspace_bytes(int32_t n_capsules, int32_t n_sources, int
 int al_ir_metrics(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len, double fs,
                   void *workspace, int64_t workspace_bytes, double *out, double *edc, al_stream_t stream);
 
+/* THE SAME PER OCTAVE BAND (DESIGN.md "IR metrics: octave bands").  al_ir_band_split cuts every row of the view al_ir_metrics takes (irs,
+ * n_capsules, n_sources, stride_c, pitch, ir_len = L: element c * stride_c + n * pitch + t, samples [L, pitch) never read, any
+ * alignment of the rows) into n_bands = B band rows.  filters: float64 DEVICE table (B, 2 half + 1), filters[b][j + half] = phi_b[j]
+ * (shoebox.band_filters: zero-phase FIRs that sum to an impulse; any table is taken, never read on the host: the table handed in is the
+ * definition).  With row = c * n_sources + n and h taken as +0 outside [0, L):
+ *   out[(row * B + b) * out_pitch + t] = float32( sum_{j = -half .. half} phi_b[j] * (double)h[t - j] ),   t < L,
+ * one float64 accumulator per output starting at +0, j ascending, every step one fused multiply-add (written as such: the bits do not
+ * depend on the compiler's contraction).  The filter's ring in front of sample 0 and past sample L - 1 is cut, so a band row holds
+ * slightly less energy than the infinite convolution.  Pads [L, out_pitch) are written +0; every output word is written once.  A
+ * non-finite sample spreads over the 2 half + 1 outputs around it in every band.  A band row's bits depend on the row's samples, the
+ * table, half and L alone.  One launch, no atomics, all offsets 64-bit.
+ * AL_E_BADARG: what al_ir_metrics refuses for irs and the five extents and strides; n_bands outside 1 .. 8; half outside 1 .. 4096; null
+ * filters or out; out not 16-byte aligned; out_pitch < ir_len or not a multiple of 4; more than 2^31 - 1 (row, 1024-sample tile of
+ * out_pitch) pairs.  A refused call writes nothing.
+ * al_ir_band_metrics: the 16 columns and the knots of al_ir_metrics for every band row.  out: float64 DEVICE table (rows, B, 16); edc:
+ * NULL or (rows, B, n_knots).  THE CONTRACT: columns and knots of (row, b) carry the bits al_ir_metrics gives for row (row, b) of the
+ * tensor al_ir_band_split writes (as a tensor of rows x B rows), whatever pass the row fell into, pitch, stride_c and the other rows
+ * are.  t0 of a band is the peak of the BAND row (a zero-phase filter rings before the direct sound).  workspace: DEVICE, 16-byte
+ * aligned, workspace_bytes >= al_ir_band_metrics_workspace_bytes(n_bands, ir_len), ONE ROW'S SHARE (its B band rows at the pitch L
+ * rounded up to 4, and al_ir_metrics' workspace for them; negative, AL_E_BADARG, for n_bands outside 1 .. 8 or ir_len < 1).  The rows
+ * are walked in passes of workspace_bytes / share rows (never more (row, band, tile) triples than al_ir_metrics accepts): per pass one
+ * split into the workspace and al_ir_metrics' five launches over it, in order on `stream`.  No allocation, no synchronisation, no atomics.
+ * AL_E_BADARG: what al_ir_band_split refuses for the arguments they share; null out or workspace; fs not finite or not positive; a
+ * workspace that is not 16-byte aligned or smaller than one row's share. */
+int al_ir_band_split(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len,
+                     const double *filters, int32_t n_bands, int32_t half, float *out, int64_t out_pitch, al_stream_t stream);
+int64_t al_ir_band_metrics_workspace_bytes(int32_t n_bands, int32_t ir_len);
+int al_ir_band_metrics(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len,
+                       double fs, const double *filters, int32_t n_bands, int32_t half, void *workspace, int64_t workspace_bytes,
+                       double *out, double *edc, al_stream_t stream);
+
 /* dst[t] = src[t mod m] for t < n: np.pad(..., mode="wrap") of Augmentation.process. */
 int al_wrap_copy(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream);
 
