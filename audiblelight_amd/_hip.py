@@ -236,6 +236,9 @@ SYMBOLS = {
     "al_ir_band_metrics_workspace_bytes": (ct.c_int64, [ct.c_int32, ct.c_int32]),
     "al_ir_band_metrics": (ct.c_int, [_P, ct.c_int32, ct.c_int32, ct.c_int64, ct.c_int64, ct.c_int32, ct.c_double, _P, ct.c_int32,
                                   ct.c_int32, _P, ct.c_int64, _P, _P, _S]),
+    "al_ir_pair_metrics_workspace_bytes": (ct.c_int64, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32]),
+    "al_ir_pair_metrics": (ct.c_int, [_P, ct.c_int32, ct.c_int32, ct.c_int64, ct.c_int64, ct.c_int32, ct.c_double, _P, _P, ct.c_int32,
+                                  ct.c_int32, _P, ct.c_int64, _P, _P, _S]),
     "al_noise_workspace_floats": (ct.c_int64, [ct.c_int32, ct.c_int64]),
     "al_noise_irfft": (ct.c_int, [_P, _P, _P, ct.c_int32, ct.c_int64, ct.c_float, _P, _P, _S]),
     "al_noise_irfft_seeded": (ct.c_int, [ct.c_uint64, _P, ct.c_int32, ct.c_int64, ct.c_float, _P, _P, _S]),

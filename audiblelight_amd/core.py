@@ -316,6 +316,19 @@ class StaticIRState:
             raise ValueError("this state knows no sample rate: give sample_rate")
         return acoustics.state_band_metrics(self, rate, alias, bands, edc, renderer)
 
+    def pair_metrics(self, alias: Optional[str] = None, pairs=None, max_lag=None, bands=None, curves: bool = False,
+                     sample_rate: Optional[float] = None, renderer=None) -> dict:
+        """``{alias: acoustics.IRPairMetrics}``: IACC, ITD and ILD per (capsule pair, emitter) (acoustics.ir_pair_metrics; ``pairs``
+        None: consecutive capsules).  ``bands``: None for the broadband rows, True for the six octave centres, or a
+        ``shoebox.ShoeboxBands`` / its dictionary (acoustics.ir_pair_band_metrics).  Not part of ``to_dict()``."""
+        from . import acoustics, shoebox
+
+        rate = self.metadata.get("sample_rate") if sample_rate is None else sample_rate
+        if rate is None:
+            raise ValueError("this state knows no sample rate: give sample_rate")
+        return acoustics.state_pair_metrics(self, rate, alias, pairs, max_lag, shoebox.ShoeboxBands() if bands is True else bands, curves,
+                                            renderer)
+
 
 class ShoeboxIRState:
     """WorldState stand-in for a rectangular room whose IRs are generated on the device by the image-source method
@@ -556,6 +569,17 @@ class ShoeboxIRState:
         from . import acoustics
 
         return acoustics.state_band_metrics(self, self.sample_rate, alias, self.bands if bands is None else bands, edc)
+
+    def pair_metrics(self, alias: Optional[str] = None, pairs=None, max_lag=None, bands=None, curves: bool = False) -> dict:
+        """``{alias: acoustics.IRPairMetrics}``: IACC, ITD and ILD per (capsule pair, emitter), measured where the tensors lie
+        (acoustics.ir_pair_metrics; ``pairs`` None: consecutive capsules, the layout of ``add_binaural_listener``).  ``bands``: None
+        for the broadband rows; True for the state's own bands where it has them, else the six octave centres; or a
+        ``shoebox.ShoeboxBands`` / its dictionary (acoustics.ir_pair_band_metrics).  Not part of ``to_dict()``."""
+        from . import acoustics, shoebox
+
+        if bands is True:
+            bands = self.bands if self.bands is not None else shoebox.ShoeboxBands()
+        return acoustics.state_pair_metrics(self, self.sample_rate, alias, pairs, max_lag, bands, curves)
 
     def to_dict(self) -> dict:   # worldstate.py:2330-2356 layout, with the room in place of the mesh
         d = dict(backend=self.name, sample_rate=self.sample_rate,

@@ -2,8 +2,9 @@
 // backward integral E(t) of every row in float64 and, from it, the direct-to-reverberant ratio, the clarities C50 / C80, D50, the
 // centre time, the three decay fits EDT / T20 / T30 with their sample counts and the decay the row has room for; optionally the
 // curve itself at every 256th sample.  The definition is the header comment of al_ir_metrics in include/audiblelight_hip.h; what
-// is here is how it is summed.  The same per octave band (al_ir_band_split, al_ir_band_metrics) is the second half of this file: a
-// band split in front of these passes.
+// is here is how it is summed.  The same per octave band (al_ir_band_split, al_ir_band_metrics) is the second part of this file: a
+// band split in front of these passes.  The third part measures PAIRS of rows (al_ir_pair_metrics): the windowed cross-correlation of
+// two rows behind IACC, ITD and ILD.
 //
 // THE TILE.  A row is cut into tiles of IRM_TILE = 1024 samples, a tile into 4 sub-tiles of 256; a workgroup is ONE WAVE and lane i owns
 // the four samples 4 i .. 4 i + 3 of every sub-tile, so a sub-tile is one 16-byte load per lane and the wave reads 1 KiB in one piece.
@@ -100,9 +101,9 @@ inline int64_t irm_window(double seconds, double fs) {
   return w < 2147483648.0 ? (int64_t)w : (int64_t)2147483648LL;
 }
 
-inline int irm_prepare(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len, double fs,
-                       void *workspace, int64_t workspace_bytes, double *out, double *edc, IrmJob *job) {
-  const char *entry = "al_ir_metrics";
+// what al_ir_metrics and al_ir_pair_metrics check alike: the three pointers, the view, fs and the workspace's alignment
+inline int irm_check(const char *entry, const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch,
+                     int32_t ir_len, double fs, const void *workspace, const double *out) {
   if (!irs || !out || !workspace) return fail_arg(entry, "irs, out and workspace must not be null");
   if (n_capsules < 1 || n_sources < 1 || ir_len < 1) return fail_arg(entry, "n_capsules, n_sources and ir_len must be >= 1");
   if (pitch < ir_len) return fail_arg(entry, "pitch < ir_len");
@@ -112,6 +113,14 @@ inline int irm_prepare(const float *irs, int32_t n_capsules, int32_t n_sources, 
   if (rows * tiles > 0x7fffffff) return fail_arg(entry, "more than 2^31 - 1 (row, tile) pairs");
   if (!(fs > 0.0) || !(fs <= 1.7976931348623157e308)) return fail_arg(entry, "fs must be finite and positive");
   if (((uintptr_t)workspace & 15) != 0) return fail_arg(entry, "workspace must be 16-byte aligned");
+  return AL_OK;
+}
+
+inline int irm_prepare(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len, double fs,
+                       void *workspace, int64_t workspace_bytes, double *out, double *edc, IrmJob *job) {
+  const char *entry = "al_ir_metrics";
+  if (int rc = irm_check(entry, irs, n_capsules, n_sources, stride_c, pitch, ir_len, fs, workspace, out)) return rc;
+  const int64_t rows = (int64_t)n_capsules * n_sources, tiles = irm_tiles(ir_len);
   if (workspace_bytes < irm_workspace_bytes(rows, ir_len)) return fail_arg(entry, "workspace_bytes < al_ir_metrics_workspace_bytes(...)");
   const int64_t pairs = rows * tiles;
   job->irs = irs;
@@ -758,6 +767,299 @@ inline int launch_ir_band_metrics(const IrbMetricsJob &job, hipStream_t stream) 
     launch_ir_metrics(metrics, in_pass * B, stream);
   }
   return AL_OK;
+}
+
+// ======================================================================================================== pairs of rows
+// INTERAURAL / INTER-CAPSULE MEASURES of an IR tensor where it lies (al_ir_pair_metrics; DESIGN.md "IR metrics: channel pairs"): per
+// (pair (a, b), source n), with x = h[a, n, :], y = h[b, n, :] (+0 outside [0, L)), T0 the earlier of the two rows' t0 and the windows
+// E = [T0, min(L, T0 + w_80)), Lw = [min(L, T0 + w_80), L):  r_W[j] = sum_{t in W} x[t] y[t + j] for j = -J .. J,  exx_W = sum x[t]^2,
+// eyy_W = sum y[t]^2, and from them the peak of the normalised correlation, its lag and the level difference of the early, the late and
+// the whole window.  The definition is the header comment of al_ir_pair_metrics in include/audiblelight_hip.h; what is here is how
+// it is summed.
+//
+// THE TILE.  One workgroup of ONE WAVE per (pair x source, tile of IRP_TILE = 1024 samples t, counted from sample 0 of the row whatever
+// T0 is).  x[tile] and y[tile0 - J .. tile0 + 1023 + J] go into LDS once, as float32 (4 KiB and at most 12.3 KiB: JCAP = 64, 256 or
+// 1024, the smallest that holds J, sizes the second).  LANES OWN LAGS: lane l holds the lags j = -J + l + 64 k, IRP_BLOCK = 4 values of
+// k at a time (then 2, then 1 for what is left of ceil((2 J + 1) / 64)).  The loop over t is uniform over the wave, so the two window
+// boundaries cut it into at most two plain ranges and nothing is masked.  Per t the wave reads x[t] once (a broadcast) and, per lag,
+// y[t + j] (consecutive lanes, consecutive words: no bank conflict) and does one float64 fused multiply-add per lag.
+//
+// THE ORDER, every term float64, every product of two float32 exact:
+//   r_W[j] of a tile    one accumulator from +0, t ascending over the tile's samples that lie in W, each step one fma()
+//   exx_W, eyy_W        the same chain over the same t, of x[t] x[t] and y[t] y[t] (carried by every lane beside the first block of
+//   of a tile           lags): for y == x all three are the same bits, so a row against itself correlates to exactly 1
+//   across tiles        from +0, the tiles' partials in ascending tile order (k_irp_columns, one lane per lag)
+//   the whole window    r_A[j] = r_E[j] + r_L[j], exx_A = exx_E + exx_L, eyy_A = eyy_E + eyy_L: one addition each
+// so a term reaches r_W[j], exx_W or eyy_W through at most 1024 + n_tiles additions (+ 1 for A): an order that depends on
+// (ir_len, max_lag) alone, a sample being given to its window by comparing t.  T0 is read from the rows table and only ever compared
+// with t (clamped to [0, L] first): no address is formed from it.
+// THE ARG-MAX over the lags: a lane keeps the first of its lags (ascending) at which |r_W[j]| is largest, then a shuffle tree takes
+// the larger |r|, on a tie the smaller j.
+//
+// THE PASSES (no atomics; the hand-over is the workspace between the two launches of the stream):
+//   k_irp_tiles    (pair x source, tile)  the tile's 2 (2 J + 1) + 4 partials; a tile in front of T0 writes zeros and leaves at once;
+//                                         a (pair, source) whose line is NaN by its state reads and writes nothing
+//   k_irp_columns  pair x source          the tiles added up per (window, lag) -- this is also the optional curve --, the three
+//                                         arg-maxima, the 17 columns.  (The issue's second and third kernel in one: the sums over the
+//                                         tiles are the lanes' own lags of the arg-max, so nothing needs to be handed over.)
+// A (pair, source)'s numbers depend on its two rows, their two lines of the rows table, ir_len, max_lag and fs alone.
+constexpr int IRP_TILE = 1024;         // samples t of a workgroup
+constexpr int IRP_BLOCK = 4;           // lags a lane carries through one walk over the tile
+constexpr int IRP_COLS = 17;
+constexpr int IRP_MAX_LAG = 1024;
+constexpr int IRP_OK = 0, IRP_SILENT = 1, IRP_BAD = 2, IRP_RANGE = 3;
+static_assert(IRP_TILE == IRM_TILE, "al_ir_pair_metrics: the (row, tile) limit of irm_check is counted in these tiles");
+
+struct IrpJob {
+  const float *irs;
+  const double *rows;                  // (n_capsules n_sources, IRM_COLS): al_ir_metrics' table of the same view; bad, energy, t0 are read
+  const int32_t *pairs;                // (n_pairs, 2)
+  double *partials;                    // (n_pairs n_sources, n_tiles, 2 n_lags + 4): r_E, r_L, then exx_E, eyy_E, exx_L, eyy_L
+  double *out, *xcorr;                 // (n_pairs n_sources, 17); NULL or (n_pairs n_sources, 2, n_lags)
+  int64_t stride_c, pitch, w_80;
+  int32_t n_capsules, n_sources, ir_len, n_tiles, max_lag, n_lags, n_chunks, n_pairs;
+};
+
+// the two extents the workspace is sized by, checked: (pair x source, tile) workgroups through *groups
+inline int irp_extent(const char *entry, int32_t n_pairs, int32_t n_sources, int32_t ir_len, int32_t max_lag, int64_t *groups) {
+  if (n_pairs < 1) return fail_arg(entry, "n_pairs must be >= 1");
+  if (n_sources < 1 || ir_len < 1) return fail_arg(entry, "n_sources and ir_len must be >= 1");
+  if (max_lag < 0 || max_lag > IRP_MAX_LAG) return fail_arg(entry, "max_lag must be in 0 .. 1024");
+  const int64_t lines = (int64_t)n_pairs * n_sources, tiles = irm_tiles(ir_len);
+  if (lines > 0x7fffffff / tiles) return fail_arg(entry, "more than 2^31 - 1 (pair x source, tile) workgroups: split the pairs");
+  *groups = lines * tiles;
+  return AL_OK;
+}
+
+inline int64_t irp_part(int32_t max_lag) { return 2 * (2 * (int64_t)max_lag + 1) + 4; }
+
+inline int64_t irp_workspace_bytes(int32_t n_pairs, int32_t n_sources, int32_t ir_len, int32_t max_lag) {
+  int64_t groups;
+  if (int rc = irp_extent("al_ir_pair_metrics_workspace_bytes", n_pairs, n_sources, ir_len, max_lag, &groups)) return rc;
+  return groups * irp_part(max_lag) * (int64_t)sizeof(double);
+}
+
+inline int irp_prepare(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len, double fs,
+                       const double *rows, const int32_t *pairs, int32_t n_pairs, int32_t max_lag, void *workspace, int64_t workspace_bytes,
+                       double *out, double *xcorr, IrpJob *job) {
+  const char *entry = "al_ir_pair_metrics";
+  if (int rc = irm_check(entry, irs, n_capsules, n_sources, stride_c, pitch, ir_len, fs, workspace, out)) return rc;
+  if (!rows || !pairs) return fail_arg(entry, "rows and pairs must not be null");
+  int64_t groups;
+  if (int rc = irp_extent(entry, n_pairs, n_sources, ir_len, max_lag, &groups)) return rc;
+  if (workspace_bytes < groups * irp_part(max_lag) * (int64_t)sizeof(double))
+    return fail_arg(entry, "workspace_bytes < al_ir_pair_metrics_workspace_bytes(...)");
+  job->irs = irs; job->rows = rows; job->pairs = pairs;
+  job->partials = static_cast<double *>(workspace); job->out = out; job->xcorr = xcorr;
+  job->stride_c = stride_c; job->pitch = pitch; job->w_80 = irm_window(0.08, fs);
+  job->n_capsules = n_capsules; job->n_sources = n_sources; job->ir_len = ir_len; job->n_tiles = (int32_t)irm_tiles(ir_len);
+  job->max_lag = max_lag; job->n_lags = 2 * max_lag + 1; job->n_chunks = (job->n_lags + 63) / 64; job->n_pairs = n_pairs;
+  return AL_OK;
+}
+
+struct IrpLine {           // what both kernels derive alike for line = pair * n_sources + source
+  int32_t state, a, b;
+  double bad, t0;          // the two rows' bad added; T0 as the table has it
+  int64_t e_lo, e_hi;      // E = [e_lo, e_hi), Lw = [e_hi, L): T0 and T0 + w_80 clamped to [0, L]
+};
+
+__device__ __forceinline__ IrpLine irp_line(const IrpJob &job, int64_t line) {
+  IrpLine r;
+  const int64_t p = line / job.n_sources, n = line % job.n_sources, L = job.ir_len;
+  r.a = job.pairs[2 * p];
+  r.b = job.pairs[2 * p + 1];
+  r.bad = r.t0 = __builtin_nan("");
+  r.e_lo = r.e_hi = L;
+  r.state = IRP_RANGE;
+  if (r.a < 0 || r.a >= job.n_capsules || r.b < 0 || r.b >= job.n_capsules) return r;   // the view is not touched for such a pair
+  const double *ra = job.rows + ((int64_t)r.a * job.n_sources + n) * IRM_COLS, *rb = job.rows + ((int64_t)r.b * job.n_sources + n) * IRM_COLS;
+  r.bad = ra[0] + rb[0];
+  r.state = ra[0] > 0.0 || rb[0] > 0.0 ? IRP_BAD : ra[1] == 0.0 || rb[1] == 0.0 ? IRP_SILENT : IRP_OK;
+  if (r.state != IRP_OK) return r;
+  r.t0 = fmin(ra[2], rb[2]);
+  const double up = ceil(r.t0);                // t >= T0 is t >= ceil(T0); a table of al_ir_metrics holds whole numbers
+  if (up == up) {                              // a NaN compares false with every t: both windows stay empty
+    const int64_t first = up < -2147483648.0 ? -2147483648LL : up > 2147483648.0 ? 2147483648LL : (int64_t)up;
+    r.e_lo = first < 0 ? 0 : first > L ? L : first;
+    r.e_hi = first + job.w_80 < r.e_lo ? r.e_lo : first + job.w_80 > L ? L : first + job.w_80;
+  }
+  return r;
+}
+
+// K lags of every lane (index idx0 + 64 q of the 2 J + 1, q < K) over the tile's samples [e0, e1) of window E and [e1, nv) of window Lw;
+// with ENERGY the two energies of either window ride along in the same order (yz: y at lag 0, ys + J)
+template <int K, bool ENERGY>
+__device__ __forceinline__ void irp_lags(const float *xs, const float *yl, const float *yz, int e0, int e1, int nv, double *part, int idx0,
+                                         int n_lags) {
+  double acc[2][K], en[2][2];
+#pragma unroll
+  for (int w = 0; w < 2; ++w) {
+    en[w][0] = en[w][1] = 0.0;
+#pragma unroll
+    for (int q = 0; q < K; ++q) acc[w][q] = 0.0;
+  }
+#pragma unroll
+  for (int w = 0; w < 2; ++w) {
+    const int first = w == 0 ? e0 : e1, last = w == 0 ? e1 : nv;
+#pragma unroll 4
+    for (int i = first; i < last; ++i) {
+      const double xv = (double)xs[i];
+#pragma unroll
+      for (int q = 0; q < K; ++q) acc[w][q] = fma(xv, (double)yl[i + 64 * q], acc[w][q]);
+      if constexpr (ENERGY) {
+        const double yv = (double)yz[i];
+        en[w][0] = fma(xv, xv, en[w][0]);
+        en[w][1] = fma(yv, yv, en[w][1]);
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < K; ++q) {
+    const int idx = idx0 + 64 * q;
+    if (idx < n_lags) {
+      part[idx] = acc[0][q];
+      part[n_lags + idx] = acc[1][q];
+    }
+  }
+  if constexpr (ENERGY) {
+    if (idx0 == 0) {                           // lane 0 of the first block: exx_E, eyy_E, exx_L, eyy_L
+      part[2 * n_lags] = en[0][0];
+      part[2 * n_lags + 1] = en[0][1];
+      part[2 * n_lags + 2] = en[1][0];
+      part[2 * n_lags + 3] = en[1][1];
+    }
+  }
+}
+
+// ---- pass 1: one workgroup per (pair x source, tile)
+template <int JCAP>
+__global__ __launch_bounds__(64) void k_irp_tiles(IrpJob job) {
+  __shared__ float xs[IRP_TILE];
+  __shared__ float ys[IRP_TILE + 64 * (JCAP / 32 + 1)];       // sample tile0 - J + i at ys[i], i < IRP_TILE + 64 n_chunks
+  const int lane = threadIdx.x;
+  const int64_t group = blockIdx.x, line = group / job.n_tiles, tile0 = (group % job.n_tiles) * IRP_TILE, L = job.ir_len;
+  const IrpLine ln = irp_line(job, line);
+  if (ln.state != IRP_OK) return;              // (uniform) k_irp_columns reads nothing of such a line
+  const int J = job.max_lag, n_lags = job.n_lags;
+  const int nv = (int)(tile0 + IRP_TILE < L ? IRP_TILE : L - tile0);
+  const int e0 = (int)(ln.e_lo - tile0 < 0 ? 0 : ln.e_lo - tile0 > nv ? nv : ln.e_lo - tile0);
+  const int e1 = (int)(ln.e_hi - tile0 < 0 ? 0 : ln.e_hi - tile0 > nv ? nv : ln.e_hi - tile0);
+  double *part = job.partials + group * (2 * (int64_t)n_lags + 4);
+  if (e0 == nv) {                              // (uniform) the tile lies in front of T0: e1 == nv as well, both windows miss it
+    for (int i = lane; i < 2 * n_lags + 4; i += 64) part[i] = 0.0;
+    return;
+  }
+  const int64_t n = line % job.n_sources;
+  const float *x = job.irs + ln.a * job.stride_c + n * job.pitch, *y = job.irs + ln.b * job.stride_c + n * job.pitch;
+  for (int i = lane; i < IRP_TILE; i += 64) xs[i] = tile0 + i < L ? x[tile0 + i] : 0.f;     // samples at and past L are never read
+  for (int i = lane; i < IRP_TILE + 64 * job.n_chunks; i += 64) {
+    const int64_t s = tile0 - J + i;
+    ys[i] = s >= 0 && s < L ? y[s] : 0.f;
+  }
+  __syncthreads();
+  const float *yl = ys + lane, *yz = ys + J;
+  int kb = job.n_chunks >= IRP_BLOCK ? IRP_BLOCK : job.n_chunks >= 2 ? 2 : 1;   // the first block of lags carries the energies
+  if (kb == IRP_BLOCK)
+    irp_lags<IRP_BLOCK, true>(xs, yl, yz, e0, e1, nv, part, lane, n_lags);
+  else if (kb == 2)
+    irp_lags<2, true>(xs, yl, yz, e0, e1, nv, part, lane, n_lags);
+  else
+    irp_lags<1, true>(xs, yl, yz, e0, e1, nv, part, lane, n_lags);
+  for (; kb + IRP_BLOCK <= job.n_chunks; kb += IRP_BLOCK) irp_lags<IRP_BLOCK, false>(xs, yl + 64 * kb, yz, e0, e1, nv, part, lane + 64 * kb, n_lags);
+  if (kb + 2 <= job.n_chunks) {
+    irp_lags<2, false>(xs, yl + 64 * kb, yz, e0, e1, nv, part, lane + 64 * kb, n_lags);
+    kb += 2;
+  }
+  if (kb < job.n_chunks) irp_lags<1, false>(xs, yl + 64 * kb, yz, e0, e1, nv, part, lane + 64 * kb, n_lags);
+}
+
+// ---- pass 2: one wave per (pair x source)
+__global__ __launch_bounds__(64) void k_irp_columns(IrpJob job) {
+  const int lane = threadIdx.x;
+  const int64_t line = blockIdx.x, L = job.ir_len;
+  const IrpLine ln = irp_line(job, line);
+  const int n_lags = job.n_lags, none = 0x7fffffff;
+  const int64_t S = 2 * (int64_t)n_lags + 4;
+  const double nan = __builtin_nan("");
+  double *o = job.out + line * IRP_COLS;
+  double *xc = job.xcorr ? job.xcorr + line * 2 * n_lags : nullptr;
+  if (ln.state != IRP_OK) {                    // (uniform)
+    if (xc)
+      for (int i = lane; i < 2 * n_lags; i += 64) xc[i] = nan;
+    if (lane == 0) {
+      o[0] = ln.state == IRP_BAD ? ln.bad : ln.state == IRP_SILENT ? 0.0 : nan;
+      for (int i = 1; i < IRP_COLS; ++i) o[i] = nan;
+    }
+    return;
+  }
+  const double *part = job.partials + line * job.n_tiles * S;
+  double best[3] = {-1.0, -1.0, -1.0}, at[3] = {nan, nan, nan};     // the largest |r_W|, r_W there, and where: E, Lw, A
+  int32_t arg[3] = {none, none, none};
+  for (int idx = lane; idx < n_lags; idx += 64) {                   // ascending j inside a lane
+    double r[3] = {0.0, 0.0, 0.0};
+    for (int64_t k = 0; k < job.n_tiles; ++k) {
+      r[0] += part[k * S + idx];
+      r[1] += part[k * S + n_lags + idx];
+    }
+    r[2] = r[0] + r[1];
+    if (xc) {
+      xc[idx] = r[0];
+      xc[n_lags + idx] = r[1];
+    }
+#pragma unroll
+    for (int w = 0; w < 3; ++w) {
+      if (fabs(r[w]) > best[w]) {              // strictly: the first of equal maxima stays
+        best[w] = fabs(r[w]);
+        at[w] = r[w];
+        arg[w] = idx - job.max_lag;
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int w = 0; w < 3; ++w) {
+      const double b2 = __shfl_down(best[w], off, 64), r2 = __shfl_down(at[w], off, 64);
+      const int32_t j2 = __shfl_down(arg[w], off, 64);
+      if (b2 > best[w] || (b2 == best[w] && j2 < arg[w])) {
+        best[w] = b2;
+        at[w] = r2;
+        arg[w] = j2;
+      }
+    }
+  }
+  double en[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t k = 0; k < job.n_tiles; ++k) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) en[i] += part[k * S + 2 * n_lags + i];
+  }
+  if (lane != 0) return;
+  const double exx[3] = {en[0], en[2], en[0] + en[2]}, eyy[3] = {en[1], en[3], en[1] + en[3]};
+  const int64_t count[3] = {ln.e_hi - ln.e_lo, L - ln.e_hi, L - ln.e_lo};
+  o[0] = 0.0;
+  o[1] = isfinite(ln.t0) ? ln.t0 : nan;        // an infinity can only come from a table al_ir_metrics did not write
+#pragma unroll
+  for (int w = 0; w < 3; ++w) {
+    const double den = exx[w] * eyy[w];
+    const bool peak = count[w] > 0 && den != 0.0 && arg[w] != none;
+    o[2 + 5 * w] = peak ? at[w] / sqrt(den) : nan;
+    o[3 + 5 * w] = peak ? (double)arg[w] : nan;
+    o[4 + 5 * w] = 10.0 * log10(exx[w] / eyy[w]);
+    o[5 + 5 * w] = exx[w];
+    o[6 + 5 * w] = eyy[w];
+  }
+}
+
+inline void launch_ir_pair_metrics(const IrpJob &job, hipStream_t stream) {
+  const int64_t lines = (int64_t)job.n_pairs * job.n_sources;
+  const dim3 grid((unsigned)(lines * job.n_tiles)), block(64);
+  if (job.max_lag <= 64)
+    hipLaunchKernelGGL(k_irp_tiles<64>, grid, block, 0, stream, job);
+  else if (job.max_lag <= 256)
+    hipLaunchKernelGGL(k_irp_tiles<256>, grid, block, 0, stream, job);
+  else
+    hipLaunchKernelGGL(k_irp_tiles<1024>, grid, block, 0, stream, job);
+  hipLaunchKernelGGL(k_irp_columns, dim3((unsigned)lines), block, 0, stream, job);
 }
 
 }  // namespace al

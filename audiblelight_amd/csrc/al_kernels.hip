@@ -778,6 +778,22 @@ int al_ir_band_metrics(const float *irs, int32_t n_capsules, int32_t n_sources, 
   return check_launch("k_irm_columns");
 }
 
+// ---- pairs of rows (IACC, ITD, ILD): DESIGN.md "IR metrics: channel pairs"
+int64_t al_ir_pair_metrics_workspace_bytes(int32_t n_pairs, int32_t n_sources, int32_t ir_len, int32_t max_lag) {
+  return al::irp_workspace_bytes(n_pairs, n_sources, ir_len, max_lag);
+}
+
+int al_ir_pair_metrics(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len, double fs,
+                       const double *rows, const int32_t *pairs, int32_t n_pairs, int32_t max_lag, void *workspace,
+                       int64_t workspace_bytes, double *out, double *xcorr, al_stream_t stream) {
+  al::IrpJob job;
+  if (int rc = al::irp_prepare(irs, n_capsules, n_sources, stride_c, pitch, ir_len, fs, rows, pairs, n_pairs, max_lag, workspace,
+                               workspace_bytes, out, xcorr, &job))
+    return rc;
+  al::launch_ir_pair_metrics(job, (hipStream_t)stream);
+  return check_launch("k_irp_columns");
+}
+
 int al_resample_poly(const float *x, int32_t rows, int64_t n_in, const float *taps, int32_t half_len, int32_t up, int32_t down,
                      float *out, int64_t n_out, int64_t out_pitch, al_stream_t stream) {
   if (!x || !taps || !out || rows <= 0 || rows > 65535 || n_in <= 0 || half_len < 0 || up <= 0 || down <= 0 || n_out <= 0 ||

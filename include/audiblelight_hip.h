@@ -829,6 +829,40 @@ int al_ir_band_metrics(const float *irs, int32_t n_capsules, int32_t n_sources, 
                        double fs, const double *filters, int32_t n_bands, int32_t half, void *workspace, int64_t workspace_bytes,
                        double *out, double *edc, al_stream_t stream);
 
+/* PAIRS OF ROWS: inter-aural cross-correlation (ISO 3382-1 Annex B), the lag of its peak (ITD of a binaural pair, TDOA of a capsule
+ * pair) and the level difference (DESIGN.md "IR metrics: channel pairs").  The view is al_ir_metrics' (irs, n_capsules, n_sources,
+ * stride_c, pitch, ir_len = L: float32 h[c, n, t] at c * stride_c + n * pitch + t, samples [L, pitch) never read, any alignment).
+ * rows: the float64 DEVICE table (n_capsules * n_sources, 16) al_ir_metrics wrote for the same view; only its columns bad, energy and
+ * t0 are read, and t0 is only ever compared with t, never used to form an address.  pairs: DEVICE int32 table (n_pairs, 2) of capsule
+ * indices (a, b).  max_lag = J in 0 .. 1024.  w_80 = rint(0.08 fs), round-half-even, formed once on the host as al_ir_metrics forms it.
+ * Per (pair p, source n), x = h[a, n, :] and y = h[b, n, :] widened to float64, y taken as +0 outside [0, L):
+ *   T0 = min(t0_a, t0_b);   windows E = [T0, min(L, T0 + w_80)), Lw = [min(L, T0 + w_80), L)
+ *   for W in (E, Lw) and j = -J .. J:  r_W[j] = sum_{t in W} x[t] y[t + j]  (the window limits t, not t + j: ISO's integral),
+ *                                      exx_W = sum_{t in W} x[t]^2,  eyy_W = sum_{t in W} y[t]^2
+ *   the whole window A, one float64 addition each:  r_A[j] = r_E[j] + r_L[j],  exx_A = exx_E + exx_L,  eyy_A = eyy_E + eyy_L
+ *   per window: lag_W = the first j, ascending from -J, at which |r_W[j]| is largest;  peak_W = r_W[lag_W] / sqrt(exx_W eyy_W), signed
+ *   and not clamped (IACC is its absolute value; a lag moves energy of y across the window's edge, so it can pass 1 slightly);
+ *   ild_db_W = 10 log10(exx_W / eyy_W) with the IEEE results at 0.  A positive lag: the sound reaches row a first.
+ *   either row with bad > 0: bad = the sum of the two, NaN in every other column.  Either row silent (energy == 0): bad = 0, NaN in
+ *   every other column.  An empty window, or exx_W eyy_W == 0: peak_W and lag_W NaN, the other three as computed.  A pair index outside
+ *   [0, n_capsules): NaN in every column, and the view is not touched for that pair.
+ * out: float64 DEVICE table (n_pairs * n_sources, 17), line = p * n_sources + n, columns in this order:
+ *   bad, t0 (= T0; NaN where a table al_ir_metrics did not write holds an infinity), then peak, lag, ild_db, exx, eyy of E, the same
+ *   five of Lw, the same five of A
+ * xcorr: NULL, or a float64 DEVICE table (n_pairs * n_sources, 2, 2 J + 1) of r_E[j] and r_L[j] (NaN for a line that is NaN by its
+ * state).  The table has the same bits with and without it.
+ * workspace: DEVICE, 16-byte aligned, workspace_bytes >= al_ir_pair_metrics_workspace_bytes(n_pairs, n_sources, ir_len, max_lag)
+ * (2 (2 J + 1) + 4 float64 per (pair x source, 1024-sample tile); negative, AL_E_BADARG, for what is refused).  Two launches on `stream`.
+ * Every product is exact in float64 and every sum is float64 in an order that depends on (ir_len, max_lag) alone
+ * (csrc/al_irmetrics.h), so a line has the same bits alone, among other pairs, at any pitch or stride_c, with and without xcorr and
+ * in two runs.  No allocation, no synchronisation, no atomics.
+ * AL_E_BADARG: what al_ir_metrics refuses for irs, out, workspace, the view and fs; null rows or pairs; n_pairs < 1; max_lag outside
+ * 0 .. 1024; more than 2^31 - 1 (pair x source, tile) workgroups; a workspace that is too small.  A refused call writes nothing. */
+int64_t al_ir_pair_metrics_workspace_bytes(int32_t n_pairs, int32_t n_sources, int32_t ir_len, int32_t max_lag);
+int al_ir_pair_metrics(const float *irs, int32_t n_capsules, int32_t n_sources, int64_t stride_c, int64_t pitch, int32_t ir_len, double fs,
+                       const double *rows, const int32_t *pairs, int32_t n_pairs, int32_t max_lag, void *workspace,
+                       int64_t workspace_bytes, double *out, double *xcorr, al_stream_t stream);
+
 /* dst[t] = src[t mod m] for t < n: np.pad(..., mode="wrap") of Augmentation.process. */
 int al_wrap_copy(const float *src, int64_t m, float *dst, int64_t n, al_stream_t stream);
 
