@@ -220,6 +220,10 @@ SYMBOLS = {
     "al_ism_shoebox_src": (ct.c_int, [_P, ct.c_int32, _P, _P, ct.c_int32, _P, ct.c_int32, ct.POINTER(ct.c_double), ct.POINTER(ct.c_double),
                                   ct.c_double, ct.c_double, ct.c_double, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int64, ct.c_int64,
                                   ct.c_uint64, ct.c_int64, ct.c_int64, _P, ct.c_int32, _P, _S]),
+    "al_ism_shoebox_coherent": (ct.c_int, [_P, ct.c_int32, _P, _P, ct.c_int32, _P, ct.c_int32, ct.POINTER(ct.c_double),
+                                       ct.POINTER(ct.c_double), ct.c_double, ct.c_double, ct.c_double, ct.c_int32, ct.c_int32, ct.c_int32,
+                                       ct.c_int64, ct.c_int64, ct.c_uint64, ct.c_int64, ct.c_int64, _P, ct.c_int32, _P, _P, ct.c_int32,
+                                       ct.c_int32, ct.c_int64, _P, _S]),
     "al_ism_shoebox_bands_src": (ct.c_int, [_P, ct.c_int32, _P, _P, ct.c_int32, ct.POINTER(ct.c_double), ct.POINTER(ct.c_double), ct.c_int32,
                                         _P, ct.c_int32, ct.POINTER(ct.c_double), ct.c_double, ct.c_double, ct.c_int32, ct.c_int32,
                                         ct.c_int32, ct.c_int64, ct.c_int64, ct.c_uint64, ct.c_int64, ct.c_int64, _P, ct.c_int32, _P,

@@ -340,6 +340,8 @@ class ShoeboxIRState:
     generation per microphone; the tensors stay in HBM.
     ``tail``: a ``shoebox.ShoeboxTail`` (or its dictionary) gives every row a diffuse tail past the mixing time; channels are
     numbered through the microphones in their order, so no two rows of the state share noise.
+    With ``tail.coherent`` every microphone of point capsules is one group whose tails are coherent as a diffuse field's are
+    (DESIGN.md "Shoebox IRs: the coherent tail"); its first channel's number is the group's id.
     ``bands``: a ``shoebox.ShoeboxBands`` (or its dictionary) gives the walls a reflection coefficient per band (DESIGN.md "Shoebox
     IRs: frequency-dependent walls"): ``betas`` then has shape (6, B), or ``materials`` names six walls (or one name for all) in
     ``material_table`` (``shoebox.load_materials``), read at the band centres.  The names are kept with the betas in ``to_dict``;
@@ -449,6 +451,8 @@ class ShoeboxIRState:
 
         if self.bands is not None:
             raise ValueError("bands together with a rigid sphere are not yet supported (B x n_orders rows per capsule)")
+        if self.tail is not None and self.tail.coherent:
+            raise ValueError("a coherent tail on a rigid sphere is not yet supported (its rows are independent draws)")
         centre, radius = shoebox.check_sphere(self.room, centre, radius, self.emitter_positions)
         _, _, _, n_orders, half, _ = shoebox._sphere_plan(radius, float(self.sample_rate), self.c, n_orders, half)
         positions = centre[None, :] + radius * directions

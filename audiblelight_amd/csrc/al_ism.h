@@ -82,6 +82,16 @@ constexpr uint32_t ISM_TAIL_TAG = 4u;                 // third counter word of t
 constexpr int ISM_TAIL_THREADS = 256;
 constexpr int ISM_TAIL_QUADS = 4;                     // 16-byte stores per lane of k_ism_tail, ISM_TAIL_THREADS quads apart
 constexpr int ISM_TAIL_SPAN = ISM_TAIL_THREADS * 4 * ISM_TAIL_QUADS;   // samples per workgroup of k_ism_tail
+constexpr uint32_t ISM_CTAIL_TAG = 5u;                // low byte of the third counter word of the coherent tail's draws: 5 + 256 p for plane wave p
+constexpr int ISM_CTAIL_MAX_WAVES = 256, ISM_CTAIL_MAX_TAPS = 32;
+constexpr int ISM_CTAIL_REACH = 256;                  // every tap of a table reads s(t - d) with -256 <= d <= 256
+constexpr int ISM_CTAIL_THREADS = 64;                 // one wave, as the image kernels: its __syncthreads() order LDS traffic only
+constexpr int ISM_CTAIL_PER_LANE = 8;                 // consecutive samples of a lane: two 16-byte stores per row
+constexpr int ISM_CTAIL_TILE = ISM_CTAIL_THREADS * ISM_CTAIL_PER_LANE;   // samples per workgroup of k_ism_ctail
+constexpr int ISM_CTAIL_WINDOW = ISM_CTAIL_TILE + 2 * ISM_CTAIL_REACH;   // draws of one plane wave a tile can read
+constexpr int ISM_CTAIL_PLANE = ISM_CTAIL_WINDOW / ISM_CTAIL_PER_LANE;   // words of one of the window's eight planes
+constexpr int ISM_CTAIL_CHUNK = 4;                    // plane waves in LDS at a time: 4 x 1024 x 4 B = 16 KiB, ten workgroups per CU
+constexpr int ISM_CTAIL_ROWS = 8;                     // rows of the group per workgroup: 64 float64 accumulators per lane
 
 // the diffuse tail of a row (all zero for al_ism_shoebox)
 struct IsmTail {
@@ -93,6 +103,12 @@ struct IsmTail {
   uint32_t seed_lo, seed_hi, source_id0, capsule_id0;
   uint32_t env_stride;    // knots between the tables of two rows c (al_ism_shoebox_dir_tail: n_knots); 0: one table serves every row
   uint32_t env_src_stride;   // knots between the tables of two sources n (al_ism_shoebox_src: n_knots); 0: one table serves every source
+  // the coherent tail (al_ism_shoebox_coherent; null and 0 for every other entry)
+  const double *taps;        // (rows, n_waves, n_taps), device
+  const int32_t *delays;     // (rows, n_waves), device
+  int32_t n_waves, n_taps;   // P, J
+  uint32_t group_id;
+  int32_t ctail_blocks;      // workgroups of k_ism_ctail per (source, block of ISM_CTAIL_ROWS rows)
 };
 
 struct IsmJob {
@@ -183,6 +199,42 @@ __device__ __forceinline__ void ism_fade(const IsmTail &tail, int ts, double &w_
   const double x = ((double)ts - (double)tail.mix) / (double)tail.fade;
   w_e = 0.0, w_l = 1.0;
   if (x < 1.0) sincospi(0.5 * x, &w_l, &w_e);
+}
+
+// THE COHERENT TAIL (al_ism_shoebox_coherent; DESIGN.md "Shoebox IRs: the coherent tail").  g(t) of row `row` and source n is a sum of
+// P plane waves shared by the rows of the call: g = sum_p sum_j taps[row][p][j] s_{n,p}(t - delays[row][p] - j), p ascending outside,
+// j ascending inside, one fma per term into a float64 accumulator that starts at 0.  s_{n,p}(m) is normal m & 3 of the Philox block
+// ((uint32)(m >> 2), source_id0 + n, 5 + 256 p, group_id): m may be negative, and its counter word then wraps to one no sample index
+// reaches.  Two paths form the same sum in the same order from the same float32 normals, so their bits agree:
+//   ism_ctail_g   one sample, the blocks regenerated as it goes (the image kernels' epilogue: the faded samples below the split);
+//   k_ism_ctail   every sample from the split on.  One workgroup of one wave per (source, tile of ISM_CTAIL_TILE samples, block of
+//     ISM_CTAIL_ROWS rows): the draws of ISM_CTAIL_CHUNK plane waves over the tile's window go to LDS once and every row of the block
+//     reads them, each lane sliding the n_taps + 7 words its eight samples need through registers.
+// the four normals s(4 q) .. s(4 q + 3) of plane wave p for source n
+__device__ __forceinline__ float4 ism_ctail_normal4(const IsmTail &tail, uint32_t q, int n, int p) {
+  const Philox4 x = philox4x32_10(q, tail.source_id0 + (uint32_t)n, ISM_CTAIL_TAG + 256u * (uint32_t)p, tail.group_id, tail.seed_lo, tail.seed_hi);
+  const float2 a = box_muller(x.x, x.y), b = box_muller(x.z, x.w);
+  return make_float4(a.x, a.y, b.x, b.y);
+}
+__device__ __forceinline__ double ism_ctail_g(const IsmTail &tail, int row, int n, int t) {
+  const int P = tail.n_waves, J = tail.n_taps;
+  double g = 0.0;
+  for (int p = 0; p < P; ++p) {
+    const int64_t wave = (int64_t)row * P + p;
+    const double *taps = tail.taps + wave * J;
+    int64_t m = (int64_t)t - tail.delays[wave];
+    int64_t have = m >> 2;
+    float4 s4 = ism_ctail_normal4(tail, (uint32_t)have, n, p);
+    for (int j = 0; j < J; ++j, --m) {
+      if ((m >> 2) != have) {
+        have = m >> 2;
+        s4 = ism_ctail_normal4(tail, (uint32_t)have, n, p);
+      }
+      const float s = (m & 2) ? ((m & 1) ? s4.w : s4.z) : ((m & 1) ? s4.y : s4.x);
+      g = fma(taps[j], (double)s, g);
+    }
+  }
+  return g;
 }
 
 // what every list entry holds beside its gains: the tap's shape of an image of amplitude a
@@ -398,7 +450,8 @@ __device__ __forceinline__ const double *ism_tail_table(const IsmTail &tail, int
   return tail.ln_env + ((int64_t)c * tail.env_stride + (int64_t)n * tail.env_src_stride);
 }
 
-template <bool TAIL, bool SRC = false>
+// COH: the noise term of the epilogue is the coherent tail's (TAIL and SRC set: al_ism_shoebox_coherent takes the arguments of _src)
+template <bool TAIL, bool SRC = false, bool COH = false>
 __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
   __shared__ IsmEntry list[ISM_LIST];
   __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];
@@ -432,7 +485,10 @@ __global__ __launch_bounds__(ISM_THREADS) void k_ism_shoebox(IsmJob job) {
         double w_e, w_l;
         ism_fade(job.tail, ts, w_e, w_l);
         const double *ln_env = SRC ? ism_tail_table(job.tail, cap, n) : job.tail.ln_env;   // SRC: a table per pair
-        v = w_e * v + w_l * ism_envelope(ln_env, ts) * (double)ism_tail_normal(job.tail, ts, n, cap);
+        if constexpr (COH)
+          v = w_e * v + w_l * ism_envelope(ln_env, ts) * ism_ctail_g(job.tail, cap, n, ts);
+        else
+          v = w_e * v + w_l * ism_envelope(ln_env, ts) * (double)ism_tail_normal(job.tail, ts, n, cap);
       }
     }
     row[ts] = ts < job.ir_len ? (float)v : 0.f;
@@ -477,6 +533,103 @@ __global__ __launch_bounds__(ISM_TAIL_THREADS) void k_ism_tail(IsmJob job) {
       if (t + 3 < job.ir_len) v.w = (float)(e3 * (double)g.w);
     }
     *reinterpret_cast<float4 *>(row + t) = v;
+  }
+}
+
+// one (row, plane wave) of k_ism_ctail: the lane's eight accumulators take the J taps tp[0 .. J) in order.  planes: the plane wave's
+// window, word u at planes[(u & 7) * PLANE + (u >> 3)]; first: the word of s(t - D) of the lane's first sample WITHOUT the lane's
+// 8 lane (uniform over the wave, so the plane and the offset of every word are scalar and the lanes read consecutive LDS words: no
+// bank conflict).  The n_taps + 7 words slide through eight float64 registers, each converted once: a tap costs one LDS word, one
+// conversion and eight fma.  JT: n_taps when it is known at compile time (the loop unrolls and the taps come in one scalar load),
+// 0: J of the call.
+template <int JT>
+__device__ __forceinline__ void ism_ctail_wave(const float *planes, const double *__restrict__ tp, int first, int J, int lane,
+                                               double (&acc)[ISM_CTAIL_PER_LANE]) {
+  auto word = [&](int u) { return (double)planes[(u & 7) * ISM_CTAIL_PLANE + (u >> 3) + lane]; };
+  double x[ISM_CTAIL_PER_LANE];
+#pragma unroll
+  for (int i = 0; i < ISM_CTAIL_PER_LANE; ++i) x[i] = word(first + i);
+  const int n_taps = JT ? JT : J;
+#pragma unroll
+  for (int j = 0; j < n_taps; ++j) {
+    const double a = tp[j];
+#pragma unroll
+    for (int i = 0; i < ISM_CTAIL_PER_LANE; ++i) acc[i] = fma(a, x[i], acc[i]);
+#pragma unroll
+    for (int i = ISM_CTAIL_PER_LANE - 1; i > 0; --i) x[i] = x[i - 1];
+    if (j + 1 < n_taps) x[0] = word(first - (j + 1));
+  }
+}
+
+// the samples [split, pitch) of every row under the coherent tail: envelope times g(t), pad zeros.  grid: ctail_blocks tiles per
+// (source, block of ISM_CTAIL_ROWS rows), ONE WAVE each (the __syncthreads() below order LDS traffic only, as in ism_gather).  The
+// window of plane wave p holds s_{n,p}(m) for m in [tile - 256, tile + 512 + 256): every m a table within its contract can ask for,
+// word u = m - (tile - 256) in plane u & 7 (eight planes of WINDOW / 8 words: a lane owns eight consecutive samples for its 16-byte
+// stores, and the planes keep the lanes' reads of one word apart by one LDS word, not eight).
+__global__ __launch_bounds__(ISM_CTAIL_THREADS) void k_ism_ctail(IsmJob job) {
+  __shared__ float win[ISM_CTAIL_CHUNK][ISM_CTAIL_PER_LANE][ISM_CTAIL_PLANE];
+  const IsmTail &tail = job.tail;
+  const int lane = threadIdx.x;
+  const int tile = (int)(blockIdx.x % (unsigned)tail.ctail_blocks);
+  const int64_t rest = blockIdx.x / (unsigned)tail.ctail_blocks;   // row block * N + n
+  const int n = (int)(rest % job.n_sources), row0 = (int)(rest / job.n_sources) * ISM_CTAIL_ROWS;
+  const int n_rows = min(ISM_CTAIL_ROWS, job.n_capsules - row0);
+  const int P = tail.n_waves, J = tail.n_taps;
+  const int64_t t_tile = (int64_t)tail.split + (int64_t)tile * ISM_CTAIL_TILE, t64 = t_tile + ISM_CTAIL_PER_LANE * lane;
+  const int64_t w0 = t_tile - ISM_CTAIL_REACH;   // a multiple of 8: the split is one of ISM_TILE
+  // the draws a sample below ir_len can read end REACH past the last of them
+  const int64_t live = min((int64_t)ISM_CTAIL_TILE, (int64_t)job.ir_len - t_tile);
+  const int n_quads = live > 0 ? (int)((live + 2 * ISM_CTAIL_REACH + 3) / 4) : 0;
+  const bool mine = t64 < job.ir_len;   // the lane has a sample of the row (ir_len < 2^31: t64 fits an int then)
+  const double *__restrict__ taps = tail.taps;
+  const int32_t *__restrict__ delays = tail.delays;
+  double acc[ISM_CTAIL_ROWS][ISM_CTAIL_PER_LANE] = {};
+  for (int p0 = 0; p0 < P && n_quads > 0; p0 += ISM_CTAIL_CHUNK) {
+    const int n_p = min(ISM_CTAIL_CHUNK, P - p0);
+    for (int i = lane; i < n_p * n_quads; i += ISM_CTAIL_THREADS) {
+      const int pp = i / n_quads, q = i % n_quads;   // words 4 q .. 4 q + 3: planes 4 (q & 1) .., offset q >> 1
+      const float4 s4 = ism_ctail_normal4(tail, (uint32_t)((w0 >> 2) + q), n, p0 + pp);
+      float *w = &win[pp][4 * (q & 1)][q >> 1];
+      w[0] = s4.x;
+      w[ISM_CTAIL_PLANE] = s4.y;
+      w[2 * ISM_CTAIL_PLANE] = s4.z;
+      w[3 * ISM_CTAIL_PLANE] = s4.w;
+    }
+    __syncthreads();
+    if (mine) {
+      for (int pp = 0; pp < n_p; ++pp) {
+#pragma unroll
+        for (int r = 0; r < ISM_CTAIL_ROWS; ++r) {
+          if (r >= n_rows) continue;
+          const int64_t wave = (int64_t)(row0 + r) * P + (p0 + pp);
+          const int first = ISM_CTAIL_REACH - delays[wave];   // >= n_taps - 1 and <= 512 by the tables' contract
+          if (J == 8)
+            ism_ctail_wave<8>(&win[pp][0][0], taps + wave * 8, first, 8, lane, acc[r]);
+          else
+            ism_ctail_wave<0>(&win[pp][0][0], taps + wave * J, first, J, lane, acc[r]);
+        }
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int h = 0; h < ISM_CTAIL_PER_LANE / 4; ++h) {
+    const int64_t tq = t64 + 4 * h;
+    if (tq >= job.pitch) break;   // pitch is a multiple of 4: a quad is inside the row or outside it
+    const int t = (int)tq;
+#pragma unroll
+    for (int r = 0; r < ISM_CTAIL_ROWS; ++r) {
+      if (r >= n_rows) continue;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (t < job.ir_len) {
+        const double *ln_env = ism_tail_table(tail, row0 + r, n);
+        v.x = (float)(ism_envelope(ln_env, t) * acc[r][4 * h]);
+        if (t + 1 < job.ir_len) v.y = (float)(ism_envelope(ln_env, t + 1) * acc[r][4 * h + 1]);
+        if (t + 2 < job.ir_len) v.z = (float)(ism_envelope(ln_env, t + 2) * acc[r][4 * h + 2]);
+        if (t + 3 < job.ir_len) v.w = (float)(ism_envelope(ln_env, t + 3) * acc[r][4 * h + 3]);
+      }
+      *reinterpret_cast<float4 *>(job.out + ((int64_t)(row0 + r) * job.n_sources + n) * (int64_t)job.pitch + t) = v;
+    }
   }
 }
 
@@ -624,8 +777,8 @@ struct IsmDirSrc : IsmDir<K> {
 
 // (waves per SIMD: with SRC and K = 4 hipcc lands a few registers past the 128 of four waves and then stops trying, 166 VGPRs; asked
 // for four it finds 128 without scratch.  1 is the default: the other instantiations are compiled as before.)
-template <int K, bool TAIL, bool SRC = false>
-__global__ __launch_bounds__(ISM_THREADS) ISM_WAVES_PER_SIMD(SRC && K == 4 ? 4 : 1) void k_ism_shoebox_dir(IsmDirJob dj) {
+template <int K, bool TAIL, bool SRC = false, bool COH = false>
+__global__ __launch_bounds__(ISM_THREADS) ISM_WAVES_PER_SIMD(SRC && K == 4 && !COH ? 4 : 1) void k_ism_shoebox_dir(IsmDirJob dj) {
   __shared__ IsmDirEntry<K> list[ISM_DIR_LIST];
   __shared__ double win_c[ISM_TAPS], win_s[ISM_TAPS];
   __shared__ int wave_total[2];
@@ -670,7 +823,10 @@ __global__ __launch_bounds__(ISM_THREADS) ISM_WAVES_PER_SIMD(SRC && K == 4 ? 4 :
         if (mixed) {
           const int c = pos * K + k;   // the row: its own noise stream and its own knot table
           const double *ln_env = SRC ? ism_tail_table(job.tail, c, n) : job.tail.ln_env + (int64_t)c * job.tail.env_stride;
-          v = w_e * v + w_l * ism_envelope(ln_env, ts) * (double)ism_tail_normal(job.tail, ts, n, c);
+          if constexpr (COH)
+            v = w_e * v + w_l * ism_envelope(ln_env, ts) * ism_ctail_g(job.tail, c, n, ts);
+          else
+            v = w_e * v + w_l * ism_envelope(ln_env, ts) * (double)ism_tail_normal(job.tail, ts, n, c);
         }
       }
       row[k * row_stride + ts] = ts < job.ir_len ? (float)v : 0.f;
@@ -715,16 +871,48 @@ inline int ism_images_prepare(const double *sources, int32_t n_sources, const do
   return AL_OK;
 }
 
+// the coherent tail of a job that ism_images_prepare has filled with a tail: the two tables, and k_ism_ctail's grid in place of
+// k_ism_tail's.  The delays' limit (-256 <= D, D + n_taps - 1 <= 256) is the tables' contract: they are not read here
+inline int ism_coherent_prepare(const double *taps, const int32_t *delays, int32_t n_waves, int32_t n_taps, int64_t group_id, IsmJob *job) {
+  if (!taps || !delays) return fail(AL_E_BADARG, "al_ism_shoebox_coherent: null tap or delay table");
+  if (n_waves < 1 || n_waves > ISM_CTAIL_MAX_WAVES) return fail(AL_E_BADARG, "al_ism_shoebox_coherent: n_waves must be in 1 .. 256");
+  if (n_taps < 1 || n_taps > ISM_CTAIL_MAX_TAPS) return fail(AL_E_BADARG, "al_ism_shoebox_coherent: n_taps must be in 1 .. 32");
+  if (group_id < 0 || group_id > 0xffffffffll) return fail(AL_E_BADARG, "al_ism_shoebox_coherent: group_id must be in [0, 2^32)");
+  IsmTail &tail = job->tail;
+  tail.taps = taps;
+  tail.delays = delays;
+  tail.n_waves = n_waves;
+  tail.n_taps = n_taps;
+  tail.group_id = (uint32_t)group_id;
+  tail.tail_blocks = 0;   // k_ism_tail has no sample of these rows
+  tail.ctail_blocks = tail.split < job->pitch ? (job->pitch - tail.split + ISM_CTAIL_TILE - 1) / ISM_CTAIL_TILE : 0;
+  const int64_t row_blocks = ((int64_t)job->n_capsules + ISM_CTAIL_ROWS - 1) / ISM_CTAIL_ROWS;
+  if ((int64_t)tail.ctail_blocks * job->n_sources * row_blocks > 0x7fffffff)
+    return fail(AL_E_BADARG, "al_ism_shoebox_coherent: more than 2^31 - 1 workgroups (tiles of 512 samples x sources x blocks of 8 rows): split the call");
+  return AL_OK;
+}
+
 // the image kernel of a job: k_ism_shoebox for omni capsules, k_ism_shoebox_dir<K> for a pattern table
-template <bool TAIL, bool SRC>
+template <bool TAIL, bool SRC, bool COH = false>
 inline void launch_ism_image_kernel(const IsmDirJob &dj, hipStream_t stream) {
   const dim3 grid((unsigned)((int64_t)dj.base.n_tiles * dj.base.n_sources * dj.n_positions)), block(ISM_THREADS);
   switch (dj.patterns ? dj.n_channels : 0) {
-    case 0: hipLaunchKernelGGL((k_ism_shoebox<TAIL, SRC>), grid, block, 0, stream, dj.base); break;
-    case 1: hipLaunchKernelGGL((k_ism_shoebox_dir<1, TAIL, SRC>), grid, block, 0, stream, dj); break;
-    case 2: hipLaunchKernelGGL((k_ism_shoebox_dir<2, TAIL, SRC>), grid, block, 0, stream, dj); break;
-    case 3: hipLaunchKernelGGL((k_ism_shoebox_dir<3, TAIL, SRC>), grid, block, 0, stream, dj); break;
-    default: hipLaunchKernelGGL((k_ism_shoebox_dir<4, TAIL, SRC>), grid, block, 0, stream, dj); break;
+    case 0: hipLaunchKernelGGL((k_ism_shoebox<TAIL, SRC, COH>), grid, block, 0, stream, dj.base); break;
+    case 1: hipLaunchKernelGGL((k_ism_shoebox_dir<1, TAIL, SRC, COH>), grid, block, 0, stream, dj); break;
+    case 2: hipLaunchKernelGGL((k_ism_shoebox_dir<2, TAIL, SRC, COH>), grid, block, 0, stream, dj); break;
+    case 3: hipLaunchKernelGGL((k_ism_shoebox_dir<3, TAIL, SRC, COH>), grid, block, 0, stream, dj); break;
+    default: hipLaunchKernelGGL((k_ism_shoebox_dir<4, TAIL, SRC, COH>), grid, block, 0, stream, dj); break;
+  }
+}
+
+// THE LAUNCH OF al_ism_shoebox_coherent: the image kernel with the coherent epilogue below the split, k_ism_ctail past it
+inline void launch_ism_coherent(const IsmDirJob &dj, hipStream_t stream) {
+  launch_ism_image_kernel<true, true, true>(dj, stream);
+  const IsmJob &job = dj.base;
+  if (job.tail.ctail_blocks > 0) {
+    const int64_t row_blocks = ((int64_t)job.n_capsules + ISM_CTAIL_ROWS - 1) / ISM_CTAIL_ROWS;
+    hipLaunchKernelGGL(k_ism_ctail, dim3((unsigned)((int64_t)job.tail.ctail_blocks * job.n_sources * row_blocks)), dim3(ISM_CTAIL_THREADS), 0,
+                       stream, job);
   }
 }
 

@@ -706,6 +706,24 @@ int al_ism_shoebox_src(const double *sources, int32_t n_sources, const double *s
   return check_launch("k_ism_shoebox_src");
 }
 
+// ---- the same with a diffuse tail that is coherent between the rows of the call: DESIGN.md "Shoebox IRs: the coherent tail"
+int al_ism_shoebox_coherent(const double *sources, int32_t n_sources, const double *source_patterns, const double *receivers,
+                            int32_t n_receivers, const double *patterns, int32_t n_channels, const double *L, const double *beta,
+                            double air, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade,
+                            uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots,
+                            const double *taps, const int32_t *delays, int32_t n_waves, int32_t n_taps, int64_t group_id, float *out,
+                            al_stream_t stream) {
+  al::IsmDirJob job;   // ln_env: (rows, N, n_knots), as al_ism_shoebox_src
+  if (mix < 0) return al::fail(AL_E_BADARG, "al_ism_shoebox_coherent: mix must be >= 0");
+  if (int rc = al::ism_images_prepare(sources, n_sources, source_patterns, receivers, n_receivers, patterns, n_channels, L, beta, air, c, fs,
+                                      max_order, ir_len, pitch, mix, fade, seed, source_id0, capsule_id0, ln_env, n_knots,
+                                      (int64_t)n_knots * n_sources, n_knots, out, &job))
+    return rc;
+  if (int rc = al::ism_coherent_prepare(taps, delays, n_waves, n_taps, group_id, &job.base)) return rc;
+  al::launch_ism_coherent(job, (hipStream_t)stream);
+  return check_launch("k_ism_ctail");
+}
+
 int al_ism_shoebox_bands_src(const double *sources, int32_t n_sources, const double *source_patterns, const double *capsules,
                              int32_t n_capsules, const double *L, const double *beta, int32_t n_bands, const double *filters,
                              int32_t half, const double *air, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch,

@@ -91,21 +91,31 @@ class ShoeboxTail:
     over ``fade_time`` seconds (None: a quarter of the mix time; at least one sample) into seeded Gaussian noise.  The noise decays
     as the image-source field of the room does (``tail_envelope``), or, with ``rt60`` given, exponentially at that reverberation
     time from the image field's level at the mixing time.  ``seed``: 64 bits; a row's noise is a function of the seed and of its
-    source and capsule numbers alone.  Validated by ``check_arguments``."""
+    source and capsule numbers alone.  ``coherent``: the rows of one call (one microphone of a state) share their noise as a
+    diffuse field does: ``n_waves`` plane waves (even, 2 .. 256) from ``diffuse_directions``, each heard by a row with the delay of
+    its position through ``2 half_taps`` interpolation taps and the weight of its pattern (``coherent_tail_tables``,
+    ``al_ism_shoebox_coherent``; DESIGN.md "Shoebox IRs: the coherent tail").  Validated by ``check_arguments``."""
 
     mix_time: Optional[float] = None
     fade_time: Optional[float] = None
     rt60: Optional[float] = None
     seed: int = 0
+    coherent: bool = False
+    n_waves: int = 64
+    half_taps: int = 4
 
     def to_dict(self) -> dict:
-        return dict(mix_time=self.mix_time, fade_time=self.fade_time, rt60=self.rt60, seed=int(self.seed))
+        d = dict(mix_time=self.mix_time, fade_time=self.fade_time, rt60=self.rt60, seed=int(self.seed))
+        if self.coherent:      # a tail without it keeps the dictionary it always had
+            d.update(coherent=True, n_waves=int(self.n_waves), half_taps=int(self.half_taps))
+        return d
 
     @classmethod
     def from_dict(cls, d) -> "ShoeboxTail":
         if isinstance(d, cls):
             return d
-        return cls(mix_time=d.get("mix_time"), fade_time=d.get("fade_time"), rt60=d.get("rt60"), seed=d.get("seed", 0))
+        return cls(mix_time=d.get("mix_time"), fade_time=d.get("fade_time"), rt60=d.get("rt60"), seed=d.get("seed", 0),
+                   coherent=d.get("coherent", False), n_waves=d.get("n_waves", 64), half_taps=d.get("half_taps", 4))
 
 
 def default_mix_time(room, c: float = SPEED_OF_SOUND) -> float:
@@ -136,6 +146,84 @@ def _check_tail(tail, betas: np.ndarray) -> None:
         raise ValueError("tail.rt60 must be None or a finite reverberation time > 0 in seconds")
     if isinstance(tail.seed, (bool, np.bool_)) or not isinstance(tail.seed, (int, np.integer)) or not 0 <= int(tail.seed) < 1 << 64:
         raise ValueError("tail.seed must be an integer in [0, 2^64)")
+    if not isinstance(tail.coherent, (bool, np.bool_)):
+        raise ValueError("tail.coherent must be True or False")
+    _check_waves(tail.n_waves, tail.half_taps)
+
+
+MAX_WAVES = 256          # plane waves of al_ism_shoebox_coherent
+MAX_HALF_TAPS = 16       # its 32 taps per plane wave, two per half
+COHERENT_REACH = 256     # samples a tap of its tables may lie before or after the sample it serves
+
+
+def _check_waves(n_waves, half_taps) -> None:
+    if isinstance(n_waves, (bool, np.bool_)) or not isinstance(n_waves, (int, np.integer)) or not 2 <= int(n_waves) <= MAX_WAVES or int(n_waves) % 2:
+        raise ValueError(f"n_waves must be an even integer in 2 .. {MAX_WAVES}")
+    if isinstance(half_taps, (bool, np.bool_)) or not isinstance(half_taps, (int, np.integer)) or not 1 <= int(half_taps) <= MAX_HALF_TAPS:
+        raise ValueError(f"half_taps must be an integer in 1 .. {MAX_HALF_TAPS}")
+
+
+def diffuse_directions(n_waves: int) -> np.ndarray:
+    """The ``n_waves`` (even) unit vectors ``(P, 3)`` the coherent tail's plane waves arrive from: THE TABLE THIS RETURNS IS THE
+    DEFINITION.  With ``h = P / 2`` and ``i = k + 0.5`` for ``k < h``: ``z = 1 - 2 i / h``, ``phi = pi (1 + sqrt 5) i``,
+    ``u_k = (sqrt(1 - z^2) cos phi, sqrt(1 - z^2) sin phi, z)`` (a Fibonacci spiral over the sphere) and ``u_{k+h} = -u_k``: the set
+    is antipodal, so the model's cross-spectrum between two omnidirectional capsules is real."""
+    _check_waves(n_waves, 1)
+    h = int(n_waves) // 2
+    i = np.arange(h, dtype=np.float64) + 0.5
+    z = 1.0 - 2.0 * i / h
+    phi = np.pi * (1.0 + np.sqrt(5.0)) * i
+    rho = np.sqrt(1.0 - z * z)
+    u = np.stack([rho * np.cos(phi), rho * np.sin(phi), z], axis=1)
+    return np.ascontiguousarray(np.concatenate([u, -u], axis=0))
+
+
+def coherent_tail_tables(positions, patterns=None, origin=None, sample_rate: float = 48000.0, c: float = SPEED_OF_SOUND,
+                         n_waves: int = 64, half_taps: int = 4) -> Tuple[np.ndarray, np.ndarray]:
+    """``(taps, delays)`` of ``al_ism_shoebox_coherent`` for rows at ``positions`` (rows, 3) with the first-order patterns
+    ``patterns`` (rows, 4) in room axes (None: omni): float64 ``(rows, P, J)`` and int32 ``(rows, P)``, ``P = n_waves``,
+    ``J = 2 half_taps``.  THE TABLES THIS RETURNS ARE THE DEFINITION the kernels are handed.
+
+    Plane wave ``p`` arrives from ``u_p = diffuse_directions(P)[p]`` and reaches row ``c`` at ``delta = -(r_c - origin) . u_p fs / c``
+    samples (``origin``: a point, default the centroid of the positions).  With ``D0 = floor(delta)``, ``f = delta - D0`` and
+    ``H = half_taps``: ``k_j = sinc(x) 0.5 (1 + cos(pi x / H))`` at ``x = j - (H - 1) - f``, zero for ``|x| >= H``, divided by
+    ``sqrt(sum_j k_j^2)``; ``delays[c, p] = D0 - (H - 1)`` and ``taps[c, p, j] = a_cp k_j`` with
+    ``a_cp = w_c(u_p) / sqrt(sum_p w_c(u_p)^2)``, ``w_c(u) = w + v . u`` (1 for an omni).  Every plane wave is unit white noise, so
+    ``Var g = 1`` for every row and the envelope keeps its meaning.  ValueError: a row whose weights all vanish; a delay outside
+    what the entry takes (every tap within 256 samples of the sample it serves)."""
+    _check_waves(n_waves, half_taps)
+    if not (isinstance(sample_rate, _REAL) and np.isfinite(sample_rate) and sample_rate > 0.0 and isinstance(c, _REAL) and np.isfinite(c)
+            and c > 0.0):
+        raise ValueError("sample_rate and c must be finite and positive")
+    positions = np.ascontiguousarray(positions, dtype=np.float64)
+    if positions.ndim != 2 or positions.shape[1] != 3 or len(positions) < 1 or not np.all(np.isfinite(positions)):
+        raise ValueError("positions must be finite with shape (rows >= 1, 3)")
+    rows, P, H = len(positions), int(n_waves), int(half_taps)
+    if patterns is None:
+        patterns = np.tile(omni(), (rows, 1))
+    patterns = np.asarray(patterns, dtype=np.float64)
+    if patterns.shape != (rows, 4) or not np.all(np.isfinite(patterns)):
+        raise ValueError(f"patterns must be None or finite with shape ({rows} rows, 4)")
+    origin = positions.mean(axis=0) if origin is None else np.asarray(origin, dtype=np.float64)
+    if origin.shape != (3,) or not np.all(np.isfinite(origin)):
+        raise ValueError("origin must be three finite numbers")
+    u = diffuse_directions(P)
+    weight = patterns[:, :1] + patterns[:, 1:] @ u.T      # (rows, P)
+    norm = np.sqrt((weight * weight).sum(axis=1))
+    if np.any(norm == 0.0):
+        raise ValueError("a row's pattern is zero towards every plane wave: it has no diffuse tail")
+    delta = -((positions - origin[None, :]) @ u.T) * (float(sample_rate) / float(c))
+    d0 = np.floor(delta)
+    limit = COHERENT_REACH - H
+    if np.any(d0 - (H - 1) < -COHERENT_REACH) or np.any(d0 + H > COHERENT_REACH):
+        raise ValueError(f"a capsule lies {np.abs(delta).max():.1f} samples from the origin along a plane wave: with half_taps = {H} the "
+                         f"coherent tail takes at most {limit}, an array within {limit * float(c) / float(sample_rate):.3g} m of its "
+                         f"origin at this sample rate")
+    x = np.arange(2 * H, dtype=np.float64)[None, None, :] - (H - 1) - (delta - d0)[:, :, None]
+    k = np.where(np.abs(x) < H, np.sinc(x) * 0.5 * (1.0 + np.cos(np.pi * x / H)), 0.0)
+    k = k / np.sqrt((k * k).sum(axis=2))[:, :, None]
+    taps = (weight / norm[:, None])[:, :, None] * k
+    return np.ascontiguousarray(taps), np.ascontiguousarray((d0 - (H - 1)).astype(np.int32))
 
 
 def tail_samples(tail: ShoeboxTail, room, sample_rate: float, c: float = SPEED_OF_SOUND) -> Tuple[int, int]:
@@ -531,7 +619,7 @@ def check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c=SPEED
 def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sample_rate: float, c: float = SPEED_OF_SOUND,
                        max_order: Optional[int] = None, tail: Optional[ShoeboxTail] = None, source_id0: int = 0,
                        capsule_id0: int = 0, patterns=None, bands: Optional[ShoeboxBands] = None,
-                       workspace_cap: int = BAND_WORKSPACE_CAP, source_patterns=None, air=None):
+                       workspace_cap: int = BAND_WORKSPACE_CAP, source_patterns=None, air=None, origin=None):
     """The IRs of ``sources`` (N, 3) at ``capsules`` (C, 3) in the room ``(Lx, Ly, Lz)`` with wall reflection coefficients
     ``betas = (x0, x1, y0, y1, z0, z1)``: ``(device buffer, (stride_c, stride_n), ir_len)`` as ``ingest.pack_ragged_irs`` returns
     it, enqueued on the renderer's stream.  The two coordinate tables are all that is uploaded.  With ``tail`` (a ``ShoeboxTail``)
@@ -557,7 +645,14 @@ def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sa
     attenuation in Np/m (``air_absorption``), one number, or ``(B,)`` with bands.  With either the call goes to
     ``al_ism_shoebox_src`` or ``al_ism_shoebox_bands_src`` (DESIGN.md "Shoebox IRs: directional sources and air"), and a tail takes
     an envelope per distinct (receiver pattern, source pattern) or (source pattern, band); with both None the calls above, bit
-    for bit."""
+    for bit.
+
+    ``tail.coherent``: the rows of the call are ONE GROUP whose tails share ``tail.n_waves`` plane waves, with
+    ``group_id = capsule_id0`` (``al_ism_shoebox_coherent``; DESIGN.md "Shoebox IRs: the coherent tail"); the two tables of
+    ``coherent_tail_tables`` are uploaded.  ``origin``: the point the plane waves' delays are counted from, default the centroid of
+    ``capsules``; a caller that splits a microphone over several calls gives every call the same ``origin`` and ``capsule_id0``.
+    A call with one row goes to the entries above, bit for bit: one row has nobody to be coherent with.  Not yet together with
+    ``bands`` (ValueError)."""
     room, betas, sources, capsules, ir_len, fs, c, order = check_arguments(room, betas, sources, capsules, ir_len, sample_rate, c,
                                                                           max_order, tail, patterns, bands, source_patterns, air)
     if bands is not None:
@@ -569,10 +664,17 @@ def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sa
     n_rows = n_cap * K
     if tail is not None:
         _check_ids(source_id0, capsule_id0, n, n_rows)
+    coherent = None      # the two tables of a coherent tail
+    if tail is not None and tail.coherent:
+        if bands is not None:
+            raise ValueError("bands together with a coherent tail are not yet supported")
+        if n_rows > 1:
+            coherent = coherent_tail_tables(np.repeat(capsules, K, axis=0), None if patterns is None else patterns.reshape(-1, 4), origin,
+                                            fs, c, tail.n_waves, tail.half_taps)
     mem, lib = renderer.mem, renderer.lib
     mix, fade = (-1, 0) if tail is None else tail_samples(tail, room, fs, c)
     # the entries with the source side take its arguments whether or not there is a tail; the others have a name per combination
-    src = source_patterns is not None or air is not None
+    src = source_patterns is not None or air is not None or coherent is not None      # the coherent entry takes the arguments of _src
     spat = None if source_patterns is None else check_source_patterns(source_patterns, n)
     air = check_air(0.0 if air is None else air, None if bands is None else betas.shape[1])
     keep = []      # device tables, alive until the call is enqueued
@@ -606,9 +708,12 @@ def shoebox_irs_device(renderer, room, betas, sources, capsules, ir_len: int, sa
     if tail is not None:
         ln_env = _envelope_tables(room, betas, ir_len, fs, mix, c, tail.rt60, air, keys)
         tail_block = (mix, fade, int(tail.seed), int(source_id0), int(capsule_id0), ptr_of(ln_env), ln_env.shape[-1])
+    if coherent is not None:
+        taps, delays = coherent
+        tail_block += (ptr_of(taps), ptr_of(delays), taps.shape[1], taps.shape[2], int(capsule_id0))
     out = mem.empty(n_rows * n * pitch)
-    lib.call(entry + ("_src" if src else "_tail" if tail is not None else ""), *head, *middle, c, fs, order, ir_len, pitch, *tail_block,
-             *workspace_pair, mem.ptr(out), mem.stream())
+    lib.call(entry + ("_coherent" if coherent is not None else "_src" if src else "_tail" if tail is not None else ""), *head, *middle, c, fs,
+             order, ir_len, pitch, *tail_block, *workspace_pair, mem.ptr(out), mem.stream())
     return out, (n * pitch, pitch), ir_len
 
 
@@ -864,6 +969,8 @@ def shoebox_sphere_irs_device(renderer, room, betas, sources, centre, directions
     centre, radius = check_sphere(room, centre, radius, sources)
     directions = check_directions(directions)
     _check_workspace_cap(workspace_cap)
+    if tail is not None and tail.coherent:
+        raise ValueError("a coherent tail on a rigid sphere is not yet supported (its rows are independent draws)")
     table = sphere_filters(radius, fs, c, n_orders, half)
     n_orders, half = table.shape[0], (table.shape[1] - 1) // 2
     n, n_cap, pitch = len(sources), len(directions), pitch_of(ir_len)

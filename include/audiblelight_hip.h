@@ -721,6 +721,28 @@ int al_ism_shoebox_src(const double *sources, int32_t n_sources, const double *s
                        int32_t n_receivers, const double *patterns, int32_t n_channels, const double *L, const double *beta, double air,
                        double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade, uint64_t seed,
                        int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots, float *out, al_stream_t stream);
+/* al_ism_shoebox_src with a diffuse tail that is COHERENT between the rows of the call (DESIGN.md "Shoebox IRs: the coherent tail"): the
+ * rows are one group, and the noise g(t) of the tail's definition becomes a sum of n_waves plane waves the group shares,
+ *   g(t) = sum_{p < n_waves} sum_{j < n_taps} taps[c][p][j] s_{n,p}(t - delays[c][p] - j)        for row c and source n,
+ * in float64, p ascending outside and j ascending inside, each term one fma into an accumulator that starts at 0.  s_{n,p}(m) is
+ * normal m & 3 of the Philox-4x32-10 block with counter ((uint32)(m >> 2), source_id0 + n, 5 + 256 p, group_id) and key (seed lo,
+ * seed hi), formed in float32 as the tail's normals are and widened; the shift is arithmetic, so a negative m wraps to counter words no
+ * sample index reaches.  Mixing sample, fade, envelope (ln_env as al_ism_shoebox_src: a table per (row, source)), the one rounding to
+ * float32 and the pads are those of al_ism_shoebox_tail; capsule_id0 is range-checked as there and enters no draw.
+ *   taps:   float64 DEVICE table (n_receivers * n_channels, n_waves, n_taps);
+ *   delays: int32 DEVICE table (n_receivers * n_channels, n_waves).  THE TABLES' CONTRACT: every entry D satisfies -256 <= D and
+ *           D + n_taps - 1 <= 256.  The tables are not read on the host; the caller answers for the limit.
+ * A row's bits depend on the room, the pair, the seed, source_id0 + n, group_id and its own rows of the two tables alone; with
+ * mix >= ir_len they are those of al_ism_shoebox_src.  Every sample is written once and out is never read.
+ * AL_E_BADARG: everything al_ism_shoebox_src refuses; mix < 0; n_waves outside 1 .. 256; n_taps outside 1 .. 32; a null table;
+ * group_id outside [0, 2^32).  Two launches (the image kernel below ceil((M + F) / 256) * 256, one kernel past it); no allocation, no
+ * synchronisation, no atomics. */
+int al_ism_shoebox_coherent(const double *sources, int32_t n_sources, const double *source_patterns, const double *receivers,
+                            int32_t n_receivers, const double *patterns, int32_t n_channels, const double *L, const double *beta,
+                            double air, double c, double fs, int32_t max_order, int32_t ir_len, int32_t pitch, int64_t mix, int64_t fade,
+                            uint64_t seed, int64_t source_id0, int64_t capsule_id0, const double *ln_env, int32_t n_knots,
+                            const double *taps, const int32_t *delays, int32_t n_waves, int32_t n_taps, int64_t group_id, float *out,
+                            al_stream_t stream);
 /* al_ism_shoebox_bands (mix < 0) or al_ism_shoebox_bands_tail (mix >= 0) with source_patterns as above and air a HOST array of n_bands
  * coefficients m_b: the image sum y_b of band b carries (w_s + v_s . e) exp(-m_b d) per image.  With a tail ln_env is a DEVICE table
  * (n_sources, n_bands, n_knots): source n's band b reads table n * n_bands + b.  The workspace is sized by
